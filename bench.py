@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - frames/s of the FullSubNet enhancement path (BASELINE.json configs[1]) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the whole hot path (STFT -> FullSubNet -> cIRM decompress/apply -> iSTFT,
@@ -10,15 +10,23 @@ one batch of 64 utterances (BASELINE config 2).  Utterances (and with them the b
 sub-band model) are independent, so with N ranks that ONE batch is sharded - 64 / N whole utterances per rank (or
 contiguous slices of the B F sub-band rows, --shard rows) - every rank runs the unchanged single-GPU path on its
 share with no data-path collective, and one RCCL all-gather re-assembles the node batch: total work is fixed ->
-"scaling": "strong", the north-star target (>= 6x at 8 GPUs).  The weak form (64 utterances per rank,
-`--scaling weak`) is measured next to it as the side figure `other_scaling`.
+"scaling": "strong", the north-star target (>= 6x at 8 GPUs).
 
-Prints ONE JSON line (rank 0) with the driver's contract keys plus
+A plain run sets up, warms up, times K steps and prints ONE JSON line (rank 0) with the driver's contract keys
+(`ms_per_step` = milliseconds of one timed step) plus
   roofline     - fp32-MFMA roofline fraction of the dominant kernel (the sub-band recurrent kernel,
                  two launches per step) from its algorithmic FLOPs / its HIP-event duration on the
-                 launch stream; `traffic` / `mfma_busy_frac` from the committed rocprofv3 PMC passes of this config
+                 launch stream of the timed steps; `traffic` / `mfma_busy_frac` from the committed rocprofv3 PMC
+                 passes of this config
+--dump-outputs DIR writes what the last timed step returned (the enhanced waveforms [B, L], float32) as
+DIR/enhanced.npy; the inputs are seeded, so two builds can be compared output for output.
+
+--full adds the side measurements, each a run of its own:
+  other_scaling (N > 1: the weak form, 64 utterances per rank), strong_scaling_shares (N = 1: one rank's share at
+  2 / 4 / 8 ranks, measured on this GPU)
   cpu_baseline - the reference's ATen operator sequence (oracle/aten_baseline.py) timed on this box's host cores
-                 on a bounded sample of the same workload (rank 0, N = 1 only); the numpy oracle as `oracle_port`
+                 on a bounded sample of the same workload (rank 0, N = 1 only); the numpy oracle as `oracle_port`,
+                 and `parity` of the timed plan against it
   one_utterance (eager / hipGraph replay latency of one utterance), split_f16x3, train_step, fast_b256, fast_train_b72_amp, improved48_b32 -
   side figures (N = 1): the opt-in split-precision
                  kernels, one training step at BASELINE config 3's per-rank shape, Fast FullSubNet at batch 256
@@ -189,19 +197,20 @@ def collector_paused():
 
 
 def timed_steps(step, fence, steps, read_profile=None):
-    """K steps bracketed by fence() on both sides; returns (seconds, summed stage ms)."""
+    """K steps bracketed by fence() on both sides; returns (seconds, summed stage ms, what the last step returned)."""
     stage_ms = {}
+    last = None
     fence()
     with collector_paused():  # a generation-2 pass of the cyclic collector is a ~40 ms host pause (tools/bench_family.py)
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            last = step()
             if read_profile is not None:
                 for k, v in read_profile().items():  # waits for this step's events only
                     stage_ms[k] = stage_ms.get(k, 0.0) + v
         fence()
         dt = time.perf_counter() - t0
-    return dt, stage_ms
+    return dt, stage_ms, last
 
 
 def amp_step_traffic(saves):
@@ -570,6 +579,27 @@ def hbm_stage_rooflines(stage_ms, b, length, T):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """Each [rows, ...] tensor as directory/<name>.npy, float32.  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of
+    the rows (in their order) is written instead of every row."""
+    os.makedirs(directory, exist_ok=True)
+    per = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > per:
+            row_bytes = a[:1].nbytes
+            if row_bytes > per:  # one row alone is over the limit: its leading elements
+                a = a.reshape(a.shape[0], -1)[:, :per // 4]
+                row_bytes = a[:1].nbytes
+            keep = max(1, per // row_bytes)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=min(keep, a.shape[0]), replace=False))
+            a = a[rows]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -584,12 +614,18 @@ def main():
                     help="strong scaling: whole utterances per rank (all-gather of waveforms), or contiguous slices "
                          "of the batch x frequency rows of the sub-band model (all-gather of the full-band mask; "
                          "balances any batch over any number of ranks).  auto: utterances when they divide evenly")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements, each a run of its own: the other scaling mode / strong-scaling "
+                         "shares, opt-in arithmetic, training steps, sibling models, one-utterance latency, the CPU "
+                         "baseline and the parity of the timed plan against the CPU oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the enhanced waveforms, float32) to DIR/enhanced.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=30.0)
     ap.add_argument("--cpu-all-cores", action="store_true",
-                    help="also time the CPU baseline with every host thread (minutes on a 256-thread box)")
+                    help="--full: also time the CPU baseline with every host thread (minutes on a 256-thread box)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the side measurements (other scaling mode, opt-in arithmetic, training step)")
+                    help="--full: skip the side measurements (other scaling mode, opt-in arithmetic, training step)")
     ap.add_argument("--persistent", choices=["auto", "never"], default="auto",
                     help="never: take the kernels that run a whole recurrence as one launch out of every plan "
                          "(fsn_set_persistent_mode) - for ranks that SHARE a GPU (the gloo control-flow tests on a "
@@ -600,6 +636,10 @@ def main():
     ap.add_argument("--lib", default=None,
                     help="diagnosis: load this build of libfsn_hip.so (tools/build_variant.py) instead of the shipped one; the line says so")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("--steps must be at least 1")
+    if not args.full:  # a plain run measures the headline figure only
+        args.no_extras = args.no_cpu_baseline = True
     if args.lib:
         import fullsubnet_amd
         fullsubnet_amd._lib.LIB_PATH = os.path.abspath(args.lib)
@@ -719,7 +759,7 @@ def main():
         step.reset_all_gather()
         if profile:
             _lib.profile_enable(True, device)  # hipEvents on the launch stream around every stage (no host sync inside)
-        dt, stage_ms = timed_steps(step, fence, steps, (lambda: _lib.profile_read(device)) if profile else None)
+        dt, stage_ms, last = timed_steps(step, fence, steps, (lambda: _lib.profile_read(device)) if profile else None)
         if profile:
             _lib.profile_enable(False, device)
         # what this rank's share runs on: the plan of its B utterances (row shard: of the whole batch it holds)
@@ -744,11 +784,23 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
         return dict(dt=dt, stage_ms={k: v / steps for k, v in stage_ms.items()}, b_total=b_total, b_loc=b_loc,
-                    rows_loc=rows_loc, par=par, steps=steps, plan=plan, per_rank=per_rank)
+                    rows_loc=rows_loc, par=par, steps=steps, plan=plan, per_rank=per_rank, last=last,
+                    row_sharded=step.row_sharded)
 
     scaling = args.scaling if world > 1 else "weak"  # one GPU: the two modes are the same workload
     head = run_mode(scaling, args.steps, args.warmup, profile=True)
     scaling_label = args.scaling  # at N = 1 both modes are the same 64-utterance step
+    if args.dump_outputs and rank == 0:
+        enhanced = head["last"]
+        if world > 1 and not head["row_sharded"]:  # the padded all-gather: rank r's share starts at row r x b_max
+            b_max = shard_bounds(head["b_total"], 0, world)[1]
+            parts = []
+            for r in range(world):
+                lo, hi = shard_bounds(head["b_total"], r, world)
+                parts.append(enhanced[r * b_max:r * b_max + hi - lo])
+            enhanced = torch.cat(parts, dim=0)
+        dump_outputs(args.dump_outputs, {"enhanced": enhanced})
+    head["last"] = None
 
     extras = {}
     if not args.no_extras and world > 1:  # the other mode, a few steps, for the record

@@ -55,7 +55,7 @@ def test_bench_two_ranks_as_the_driver_launches_it(fsn, shard, batch, extras):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
            "--warmup", "1", "--batch", str(batch), "--seconds", "1", "--shard", shard, "--persistent", "never",
-           "--no-cpu-baseline"] + ([] if extras else ["--no-extras"])
+           "--no-cpu-baseline"] + (["--full"] if extras else ["--no-extras"])
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]

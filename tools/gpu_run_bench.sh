@@ -10,7 +10,7 @@ if [ "${SKIP_PYTEST:-0}" != "1" ]; then
   echo "pytest rc=$?" >> $O/pytest.log
   grep -E "passed|failed|rc=|^E  |FAILED|margins" $O/pytest.log | tail -14
 fi
-(time timeout 900 python bench.py --steps ${STEPS:-10} --warmup 3 ${BENCH_ARGS:-}) > $O/bench.json 2> $O/bench.err
+(time timeout 900 python bench.py --full --steps ${STEPS:-10} --warmup 3 ${BENCH_ARGS:-}) > $O/bench.json 2> $O/bench.err
 python - <<PY
 import json
 d = json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

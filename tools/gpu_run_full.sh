@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 (time timeout 1500 python -m pytest tests -m gpu -q -rP) > $O/pytest.log 2>&1
 echo "pytest rc=$?" >> $O/pytest.log
 grep -E "passed|failed|rc=|^E  |FAILED" $O/pytest.log | tail -8
-(time timeout 900 python bench.py --steps 10 --warmup 3) > $O/bench.json 2> $O/bench.err
+(time timeout 900 python bench.py --full --steps 10 --warmup 3) > $O/bench.json 2> $O/bench.err
 tail -c 600 $O/bench.json; tail -3 $O/bench.err
 B="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace -- $B > $O/trace.log 2>&1
