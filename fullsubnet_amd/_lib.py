@@ -83,7 +83,7 @@ class TrainDims(ctypes.Structure):  # fsn_train_dims
                 ("nb", ctypes.c_int), ("groups", ctypes.c_int), ("norm", ctypes.c_int)]
 
 
-ABI_VERSION = 117  # FSN_ABI_VERSION of include/fsn_hip.h these signatures were written against
+ABI_VERSION = 118  # FSN_ABI_VERSION of include/fsn_hip.h these signatures were written against
 
 
 class MaskSection(ctypes.Structure):  # fsn_mask_section
@@ -124,6 +124,8 @@ SIGNATURES = {
     "fsn_enhance_workspace_bytes": (_c.c_size_t, [_c.POINTER(Cfg), _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "fsn_enhance": (_c.c_int, [_c.POINTER(Cfg), _c.c_void_p, _f32p, _f32p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                _f32p, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_enhance_ragged": (_c.c_int, [_c.POINTER(Cfg), _c.c_void_p, _f32p, _f32p, _c.c_void_p, _c.c_int, _c.c_int,
+                                      _c.c_int, _c.c_int, _f32p, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "fsn_fullsubnet_stream_state_bytes": (_c.c_size_t, [_c.POINTER(Cfg), _c.c_int]),
     "fsn_fullsubnet_stream_workspace_bytes": (_c.c_size_t, [_c.POINTER(Cfg), _c.c_int, _c.c_int]),
     "fsn_fullsubnet_stream_step": (_c.c_int, [_c.POINTER(Cfg), _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _f32p,

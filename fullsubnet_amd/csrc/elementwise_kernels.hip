@@ -41,12 +41,15 @@ __global__ void build_cirm_kernel(const float* __restrict__ nr, const float* __r
 }
 
 // ---- batched 2-D transpose with zero fill: out[b][c][r] = in[b][r][c] ----------------------
-// (r < R_valid, c < C_valid come from `in`, the rest of the R x C output tile is zero)
+// (r < R_valid, c < C_valid come from `in`, the rest of the R x C output tile is zero; lengths: a ragged batch of
+// R_valid frames, rows r >= fsn_row_frames(lengths, b, R_valid) of entry b are zero too)
 __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                         int R, int C, long ld_in, long bs_in, long ld_out,
-                                                        long bs_out, int R_valid, int C_valid) {
+                                                        long bs_out, int R_valid, int C_valid,
+                                                        const int* __restrict__ lengths) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z;
+    R_valid = fsn_row_frames(lengths, b, R_valid);
     const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
     for (int i = ty; i < 32; i += 8) {
@@ -117,17 +120,22 @@ __device__ __forceinline__ double block_sum(double v, double* scratch) {
 //   which == 1: den_sb[b] = mean over the concatenated [F, 2nb+2, Tp] sub-band tensor + 1e-5
 //               (model.py:110-111) = (sum_f m[f] binsum[f] + sum fb_out) / (F (2nb+2) Tp) with
 //               m[f] = number of (unit, row) pairs of freq_unfold (base_model.py:31-44) hitting bin f.
+// lengths (may be NULL): ragged batch of T frames - utterance b is T_b + Tp - T frames long (its look-ahead included):
+// the divisors count those frames, the fb_out sum stops there (mag is zero from frame T_b on, stft_kernel, so binsum
+// needs no bound).
 __global__ __launch_bounds__(256) void offline_den_kernel(const double* __restrict__ binsum,
                                                           const float* __restrict__ fb_out,
                                                           float* __restrict__ den_fb, float* __restrict__ den_sb,
-                                                          int Tp, int F, int FP, int nb, int which) {
+                                                          int Tp, int F, int FP, int nb, int which,
+                                                          const int* __restrict__ lengths, int T) {
     __shared__ double scratch[4];
     const int b = blockIdx.x;
+    const int Tpb = lengths ? fsn_row_frames(lengths, b, T) + (Tp - T) : Tp;  // this utterance's frames
     double acc = 0.0;
     if (which == 0) {
         for (int f = threadIdx.x; f < F; f += blockDim.x) acc += binsum[(long)b * FP + f];
         const double tot = block_sum(acc, scratch);
-        if (threadIdx.x == 0) den_fb[b] = (float)(tot / ((double)F * Tp)) + 1e-5f;
+        if (threadIdx.x == 0) den_fb[b] = (float)(tot / ((double)F * Tpb)) + 1e-5f;
     } else {
         for (int f = threadIdx.x; f < F; f += blockDim.x) {
             // m[f] in closed form: pairs (u, k), u in [0, F), k in [-nb, nb], whose source bin is f -
@@ -140,12 +148,12 @@ __global__ __launch_bounds__(256) void offline_den_kernel(const double* __restri
         }
         // columns F..FP-1 of fb_out are written as zeros by the output layer: whole rows can be summed
         const f32x4* p = reinterpret_cast<const f32x4*>(fb_out + (long)b * Tp * FP);
-        for (long i = threadIdx.x; i < (long)Tp * FP / 4; i += blockDim.x) {
+        for (long i = threadIdx.x; i < (long)Tpb * FP / 4; i += blockDim.x) {
             const f32x4 v = p[i];
             acc += ((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3]);
         }
         const double tot = block_sum(acc, scratch);
-        if (threadIdx.x == 0) den_sb[b] = (float)(tot / ((double)F * (2 * nb + 2) * Tp)) + 1e-5f;
+        if (threadIdx.x == 0) den_sb[b] = (float)(tot / ((double)F * (2 * nb + 2) * Tpb)) + 1e-5f;
     }
 }
 
@@ -240,10 +248,10 @@ int fsn_launch_build_cirm(const float* nr, const float* ni, const float* cr, con
     return fsn_check_launch("build_cirm_kernel");
 }
 int fsn_launch_transpose(const float* in, float* out, int batch, int R, int C, long ld_in, long bs_in, long ld_out,
-                         long bs_out, int R_valid, int C_valid, hipStream_t s) {
+                         long bs_out, int R_valid, int C_valid, hipStream_t s, const int* lengths) {
     dim3 grid((C + 31) / 32, (R + 31) / 32, batch);
     hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, s, in, out, R, C, ld_in, bs_in, ld_out, bs_out, R_valid,
-                       C_valid);
+                       C_valid, lengths);
     return fsn_check_launch("transpose_kernel");
 }
 int fsn_launch_crm_rows(const float* crm_r, const float* crm_i, float* out, long r0, long n, int F, int FP, int T,
@@ -257,9 +265,9 @@ int fsn_launch_binsum(const float* mag, double* binsum, int B, int Tp, int FP, h
     return fsn_check_launch("binsum_kernel");
 }
 int fsn_launch_offline_den(const double* binsum, const float* fb_out, float* den_fb, float* den_sb, int B, int Tp,
-                           int F, int FP, int nb, int which, hipStream_t s) {
+                           int F, int FP, int nb, int which, hipStream_t s, const int* lengths, int T) {
     hipLaunchKernelGGL(offline_den_kernel, dim3(B), dim3(256), 0, s, binsum, fb_out, den_fb, den_sb, Tp, F, FP, nb,
-                       which);
+                       which, lengths, T);
     return fsn_check_launch("offline_den_kernel");
 }
 int fsn_launch_cumulative_den_fb(const float* mag, float* den, int B, int Tp, int F, int FP, hipStream_t s,

@@ -125,12 +125,15 @@ __device__ __forceinline__ void wave_lds_sync() {
 // y [B][L] -> re, im [B][T][FP] (frame-major) or [B][F][T] (reference layout); mag likewise, with
 // Tp >= T frames in the frame-major layout (frames >= T are the look-ahead zeros of
 // fullsubnet/model.py:85).  Columns F..FP-1 of the frame-major rows are written as zeros.
+// lengths (may be NULL): ragged batch - row b reflects at its own end L_b (the row stride stays L) and its frames
+// t >= T_b = 1 + L_b / 256 transform a zero frame, i.e. are written as zeros (in `mag` they are the utterance's own
+// look-ahead frames).
 // ---------------------------------------------------------------------------------------------
 template <bool FRAME_MAJOR>
 __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ y, const float* __restrict__ window,
                                                    float* __restrict__ re, float* __restrict__ im,
                                                    float* __restrict__ mag, int B, int L, int T, int Tp, int F,
-                                                   int FP) {
+                                                   int FP, const int* __restrict__ lengths) {
     __shared__ double lds[kWavesPerBlock][2][kLdsPoints];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int pairs_per_b = (Tp + 1) >> 1;
@@ -138,6 +141,8 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ y, 
     const int b = (int)(p / pairs_per_b);
     const int tA = 2 * (int)(p % pairs_per_b), tB = tA + 1;
     const bool live = b < B;
+    const int Lb = live ? fsn_row_samples(lengths, b, L) : L;
+    const int Tb = live ? fsn_row_frames(lengths, b, T) : T;
     double* sre = lds[wave][0];
     double* sim = lds[wave][1];
 
@@ -147,16 +152,16 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ y, 
         const int n = lane + 64 * r;
         const float w = window[n];
         float xa = 0.f, xb = 0.f;
-        if (live && tA < T) {
+        if (live && tA < Tb) {
             int j = 256 * tA + n - 256;
             j = j < 0 ? -j : j;
-            j = j >= L ? 2 * (L - 1) - j : j;
+            j = j >= Lb ? 2 * (Lb - 1) - j : j;
             xa = y[(long)b * L + j] * w;
         }
-        if (live && tB < T) {
+        if (live && tB < Tb) {
             int j = 256 * tB + n - 256;
             j = j < 0 ? -j : j;
-            j = j >= L ? 2 * (L - 1) - j : j;
+            j = j >= Lb ? 2 * (Lb - 1) - j : j;
             xb = y[(long)b * L + j] * w;
         }
         v[r] = cd{(double)xa, (double)xb};
@@ -233,13 +238,15 @@ __device__ __forceinline__ float decompress1(float m) {
 // re/im (and optionally crm_r/crm_i) -> wframes [B][T][512] = irfft(S) * window, rounded to fp32
 // after the irfft and after the window product like ATen does.
 // inferencer.py:137-140 + feature.py:84-91 (torch.istft up to the overlap-add).
+// lengths (may be NULL): ragged batch - frames t >= T_b of row b are taken as zero spectra (their mask is never read).
 // ---------------------------------------------------------------------------------------------
 template <bool FRAME_MAJOR>
 __global__ __launch_bounds__(256) void mask_irfft_kernel(const float* __restrict__ re, const float* __restrict__ im,
                                                          const float* __restrict__ crm_r,
                                                          const float* __restrict__ crm_i,
                                                          const float* __restrict__ window,
-                                                         float* __restrict__ wframes, int B, int T, int F, int FP) {
+                                                         float* __restrict__ wframes, int B, int T, int F, int FP,
+                                                         const int* __restrict__ lengths) {
     __shared__ double lds[kWavesPerBlock][2][kLdsPoints];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int pairs_per_b = (T + 1) >> 1;
@@ -247,6 +254,7 @@ __global__ __launch_bounds__(256) void mask_irfft_kernel(const float* __restrict
     const int b = (int)(p / pairs_per_b);
     const int tA = 2 * (int)(p % pairs_per_b), tB = tA + 1;
     const bool live = b < B;
+    const int Tb = live ? fsn_row_frames(lengths, b, T) : T;
     double* sre = lds[wave][0];
     double* sim = lds[wave][1];
 
@@ -258,7 +266,7 @@ __global__ __launch_bounds__(256) void mask_irfft_kernel(const float* __restrict
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int t = q ? tB : tA;
-            if (live && t < T) {
+            if (live && t < Tb) {
                 const long o = FRAME_MAJOR ? ((long)b * T + t) * FP + k : ((long)b * F + k) * T + t;
                 const float xr = re[o], xi = im[o];
                 if (crm_r) {
@@ -311,25 +319,28 @@ __global__ __launch_bounds__(256) void mask_irfft_kernel(const float* __restrict
 
 // Overlap-add of the windowed frames, division by the overlap-added squared window, centre trim
 // and length handling of torch.istft (feature.py:84-91).  y [B][length].
+// lengths (may be NULL): ragged batch - row b is the iSTFT of its own T_b frames at its own length L_b (frames >= T_b
+// add nothing to the sum or to the window envelope); samples j >= L_b are zeros.
 __global__ __launch_bounds__(256) void ola_kernel(const float* __restrict__ wframes,
                                                   const float* __restrict__ window, float* __restrict__ y, int B,
-                                                  int T, int length) {
+                                                  int T, int length, const int* __restrict__ lengths) {
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long)B * length) return;
     const int b = (int)(gid / length), j = (int)(gid % length);
+    const int Lb = fsn_row_samples(lengths, b, length), Tb = fsn_row_frames(lengths, b, T);
     const int p = j + 256;
-    const int total = 512 + 256 * (T - 1);
+    const int total = 512 + 256 * (Tb - 1);
     float out = 0.f;
-    if (p < total) {
+    if (p < total && j < Lb) {
         const int t_hi = p >> 8, t_lo = t_hi - 1;
         float acc = 0.f, env = 0.f;
-        if (t_lo >= 0 && t_lo < T) {
+        if (t_lo >= 0 && t_lo < Tb) {
             const int n = p - 256 * t_lo;
             const float w = window[n];
             acc = wframes[((long)b * T + t_lo) * 512 + n];
             env = w * w;
         }
-        if (t_hi < T) {
+        if (t_hi < Tb) {
             const int n = p - 256 * t_hi;
             const float w = window[n];
             acc = acc + wframes[((long)b * T + t_hi) * 512 + n];
@@ -343,34 +354,36 @@ __global__ __launch_bounds__(256) void ola_kernel(const float* __restrict__ wfra
 }  // namespace
 
 int fsn_launch_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag, int T,
-                    int Tp, int F, int FP, bool frame_major, hipStream_t s) {
+                    int Tp, int F, int FP, bool frame_major, hipStream_t s, const int* lengths) {
     const long pairs = (long)B * ((Tp + 1) / 2);
     const unsigned grid = (unsigned)((pairs + kWavesPerBlock - 1) / kWavesPerBlock);
     if (frame_major)
         hipLaunchKernelGGL(stft_kernel<true>, dim3(grid), dim3(256), 0, s, y, window, re, im, mag, B, L, T, Tp, F,
-                           FP);
+                           FP, lengths);
     else
         hipLaunchKernelGGL(stft_kernel<false>, dim3(grid), dim3(256), 0, s, y, window, re, im, mag, B, L, T, Tp, F,
-                           FP);
+                           FP, lengths);
     return fsn_check_launch("stft_kernel");
 }
 
 int fsn_launch_mask_irfft(const float* re, const float* im, const float* crm_r, const float* crm_i, int B, int T,
-                          int F, int FP, bool frame_major, const float* window, float* wframes, hipStream_t s) {
+                          int F, int FP, bool frame_major, const float* window, float* wframes, hipStream_t s,
+                          const int* lengths) {
     const long pairs = (long)B * ((T + 1) / 2);
     const unsigned grid = (unsigned)((pairs + kWavesPerBlock - 1) / kWavesPerBlock);
     if (frame_major)
         hipLaunchKernelGGL(mask_irfft_kernel<true>, dim3(grid), dim3(256), 0, s, re, im, crm_r, crm_i, window,
-                           wframes, B, T, F, FP);
+                           wframes, B, T, F, FP, lengths);
     else
         hipLaunchKernelGGL(mask_irfft_kernel<false>, dim3(grid), dim3(256), 0, s, re, im, crm_r, crm_i, window,
-                           wframes, B, T, F, FP);
+                           wframes, B, T, F, FP, lengths);
     return fsn_check_launch("mask_irfft_kernel");
 }
 
-int fsn_launch_ola(const float* wframes, const float* window, int B, int T, int length, float* y, hipStream_t s) {
+int fsn_launch_ola(const float* wframes, const float* window, int B, int T, int length, float* y, hipStream_t s,
+                   const int* lengths) {
     const long n = (long)B * length;
     const unsigned grid = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(ola_kernel, dim3(grid), dim3(256), 0, s, wframes, window, y, B, T, length);
+    hipLaunchKernelGGL(ola_kernel, dim3(grid), dim3(256), 0, s, wframes, window, y, B, T, length, lengths);
     return fsn_check_launch("ola_kernel");
 }

@@ -897,8 +897,11 @@ static int run_sb_recurrence(const float* gx, const FsnSbInput* xin, const float
                           bias_main, hseq_left);
 }
 
+// lengths (device, [d.B], may be NULL): a ragged batch (fsn_enhance_ragged) - only the offline norm's divisors depend on
+// an utterance's length (magT is zero past its frames); the cumulative norm and the models are causal and run to d.Tp.
 static int run_core(const fsn_fullsubnet_cfg* cfg, const float* pk, const float* magT, const CoreDims& d,
-                    const CoreWs& w, float* crm_r, float* crm_i, hipStream_t s, bool fullband_only = false) {
+                    const CoreWs& w, float* crm_r, float* crm_i, hipStream_t s, bool fullband_only = false,
+                    const int* lengths = nullptr) {
     const Packed p = packed_layout(cfg);
     const bool cum = cfg->norm_type == FSN_NORM_CUMULATIVE_LAPLACE;
 
@@ -909,7 +912,8 @@ static int run_core(const fsn_fullsubnet_cfg* cfg, const float* pk, const float*
             FSN_TRY(fsn_launch_cumulative_den_fb(magT, w.den_fb, d.B, d.Tp, d.F, d.FP, s));
         } else {
             FSN_TRY(fsn_launch_binsum(magT, w.binsum, d.B, d.Tp, d.FP, s));
-            FSN_TRY(fsn_launch_offline_den(w.binsum, nullptr, w.den_fb, nullptr, d.B, d.Tp, d.F, d.FP, d.nb, 0, s));
+            FSN_TRY(fsn_launch_offline_den(w.binsum, nullptr, w.den_fb, nullptr, d.B, d.Tp, d.F, d.FP, d.nb, 0, s,
+                                           lengths, d.T));
         }
     }
     // full-band model (model.py:95): 2 LSTM layers + Linear + ReLU
@@ -974,7 +978,8 @@ static int run_core(const fsn_fullsubnet_cfg* cfg, const float* pk, const float*
         if (cum) {
             FSN_TRY(fsn_launch_cumulative_den_sb(magT, w.fb_out, w.den_sb, d.B, d.Tp, d.F, d.FP, d.nb, d.den_stride, s));
         } else {
-            FSN_TRY(fsn_launch_offline_den(w.binsum, w.fb_out, nullptr, w.den_sb, d.B, d.Tp, d.F, d.FP, d.nb, 1, s));
+            FSN_TRY(fsn_launch_offline_den(w.binsum, w.fb_out, nullptr, w.den_sb, d.B, d.Tp, d.F, d.FP, d.nb, 1, s,
+                                           lengths, d.T));
         }
     }
     if (d.grp_clusters > 0) {
@@ -1349,9 +1354,9 @@ static void core_carve_chunks(Carver& cv, const fsn_fullsubnet_cfg* cfg, int B, 
     }
     cv.take<char>(most);
 }
-// run_core over the chunks; `scratch` = a region of at least core_carve_chunks' size
+// run_core over the chunks; `scratch` = a region of at least core_carve_chunks' size; lengths: see run_core
 static int run_core_chunks(const fsn_fullsubnet_cfg* cfg, const float* pk, const float* magT, int B, int T, void* scratch,
-                           float* crm_r, float* crm_i, hipStream_t s) {
+                           float* crm_r, float* crm_i, hipStream_t s, const int* lengths = nullptr) {
     int sizes[kMaxChunks];
     const int n = core_chunks(cfg, B, sizes, kMaxChunks);
     int b0 = 0;
@@ -1361,7 +1366,7 @@ static int run_core_chunks(const fsn_fullsubnet_cfg* cfg, const float* pk, const
         Carver cv(scratch);
         const CoreWs w = core_carve(cv, d, cfg->norm_type);
         FSN_TRY(run_core(cfg, pk, magT + (size_t)b0 * d.Tp * d.FP, d, w, crm_r + (size_t)b0 * d.T * d.FP,
-                         crm_i + (size_t)b0 * d.T * d.FP, s, false));
+                         crm_i + (size_t)b0 * d.T * d.FP, s, false, lengths ? lengths + b0 : nullptr));
         b0 += b;
     }
     FSN_REQUIRE(b0 == B, "internal: the chunks cover %d of %d utterances", b0, B);
@@ -1798,10 +1803,10 @@ extern "C" size_t fsn_enhance_workspace_bytes(const fsn_fullsubnet_cfg* cfg, int
     return fsn_round_up_sz(cv.off, 256);
 }
 
-extern "C" int fsn_enhance(const fsn_fullsubnet_cfg* cfg, const void* packed, const float* window,
-                           const float* noisy, int B, int L, int n_fft, int hop, float* enhanced, float* crm_out,
-                           void* workspace, size_t workspace_bytes, void* stream) {
-    CallScope scope(stream);
+// fsn_enhance and fsn_enhance_ragged: lengths == NULL is the rectangular batch
+static int enhance(const fsn_fullsubnet_cfg* cfg, const void* packed, const float* window, const float* noisy,
+                   const int* lengths, int B, int L, int n_fft, int hop, float* enhanced, float* crm_out, void* workspace,
+                   size_t workspace_bytes, hipStream_t s) {
     FSN_TRY(check_cfg(cfg));
     FSN_TRY(check_fft(n_fft, hop, n_fft));
     FSN_REQUIRE(packed && window && noisy && enhanced && workspace, "NULL pointer argument");
@@ -1814,7 +1819,6 @@ extern "C" int fsn_enhance(const fsn_fullsubnet_cfg* cfg, const void* packed, co
         fsn_set_error("workspace too small: %zu < %zu bytes", workspace_bytes, need);
         return FSN_ERR_WORKSPACE;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const CoreDims d = core_dims(cfg, B, T);
     Carver cv(workspace);
     float* magT = cv.take<float>((size_t)B * d.Tp * d.FP);
@@ -1827,21 +1831,39 @@ extern "C" int fsn_enhance(const fsn_fullsubnet_cfg* cfg, const void* packed, co
     prof_reset();
     {
         StageTimer st(ST_STFT, s);
-        FSN_TRY(fsn_launch_stft(noisy, B, L, window, re, im, magT, d.T, d.Tp, d.F, d.FP, true, s));
+        FSN_TRY(fsn_launch_stft(noisy, B, L, window, re, im, magT, d.T, d.Tp, d.F, d.FP, true, s, lengths));
     }
-    FSN_TRY(run_core_chunks(cfg, static_cast<const float*>(packed), magT, B, T, scratch, crm_r, crm_i, s));
+    FSN_TRY(run_core_chunks(cfg, static_cast<const float*>(packed), magT, B, T, scratch, crm_r, crm_i, s, lengths));
     {
         StageTimer st(ST_MASK_ISTFT, s);
-        FSN_TRY(fsn_launch_mask_irfft(re, im, crm_r, crm_i, B, d.T, d.F, d.FP, true, window, wf, s));
-        FSN_TRY(fsn_launch_ola(wf, window, B, d.T, L, enhanced, s));
+        FSN_TRY(fsn_launch_mask_irfft(re, im, crm_r, crm_i, B, d.T, d.F, d.FP, true, window, wf, s, lengths));
+        FSN_TRY(fsn_launch_ola(wf, window, B, d.T, L, enhanced, s, lengths));
     }
     if (crm_out) {
         FSN_TRY(fsn_launch_transpose(crm_r, crm_out, B, d.T, d.F, d.FP, (long)d.T * d.FP, d.T, 2L * d.F * d.T, d.T,
-                                     d.F, s));
+                                     d.F, s, lengths));
         FSN_TRY(fsn_launch_transpose(crm_i, crm_out + (size_t)d.F * d.T, B, d.T, d.F, d.FP, (long)d.T * d.FP, d.T,
-                                     2L * d.F * d.T, d.T, d.F, s));
+                                     2L * d.F * d.T, d.T, d.F, s, lengths));
     }
     return FSN_OK;
+}
+
+extern "C" int fsn_enhance(const fsn_fullsubnet_cfg* cfg, const void* packed, const float* window,
+                           const float* noisy, int B, int L, int n_fft, int hop, float* enhanced, float* crm_out,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    return enhance(cfg, packed, window, noisy, nullptr, B, L, n_fft, hop, enhanced, crm_out, workspace, workspace_bytes,
+                   static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fsn_enhance_ragged(const fsn_fullsubnet_cfg* cfg, const void* packed, const float* window,
+                                  const float* noisy, const int* lengths, int B, int L_max, int n_fft, int hop,
+                                  float* enhanced, float* crm_out, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(lengths, "NULL pointer argument");
+    return enhance(cfg, packed, window, noisy, lengths, B, L_max, n_fft, hop, enhanced, crm_out, workspace,
+                   workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 // ---- training step: one nn.LSTM layer, forward with saved activations + BPTT ---------------------

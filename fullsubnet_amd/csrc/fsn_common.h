@@ -19,6 +19,21 @@ static inline int fsn_fpad(int F) { return fsn_round_up(F, 16); }
 
 void fsn_set_error(const char* fmt, ...);
 
+// Ragged batches (fsn_enhance_ragged, 512 / 256 transform): row b of a [B][L] signal holds lengths[b] samples, the rest
+// of the row is padding.  A value outside [n_fft / 2 + 1, L] is clamped into it, so that no length can index outside the
+// row; lengths == NULL: every row is L samples long.  The row's frames: 1 + L_b / hop, never more than T = 1 + L / hop.
+__device__ __forceinline__ int fsn_row_samples(const int* lengths, int b, int L) {
+    if (!lengths) return L;
+    const int l = lengths[b];
+    return l < 257 ? 257 : (l > L ? L : l);
+}
+__device__ __forceinline__ int fsn_row_frames(const int* lengths, int b, int T) {
+    if (!lengths) return T;
+    const int l = lengths[b];
+    const int t = 1 + (l < 257 ? 257 : l) / 256;
+    return t < T ? t : T;
+}
+
 // Opened by every entry point that enqueues work (fsn_api.hip): makes the device of the caller's stream the
 // current one for the duration of the call and selects the per-(device, stream) record of the library.
 struct FsnCallScope {
@@ -217,14 +232,15 @@ struct FsnStream {
     hipStream_t s;
 };
 
-// fft_kernels.hip
+// fft_kernels.hip.  lengths (device, [B], may be NULL): per-row sample counts of a ragged batch (fsn_row_samples); L /
+// length is then the row stride and the longest row, T its frame count.
 int fsn_launch_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag,
-                    int T, int Tp, int F, int FP, bool frame_major, hipStream_t s);
+                    int T, int Tp, int F, int FP, bool frame_major, hipStream_t s, const int* lengths = nullptr);
 int fsn_launch_mask_irfft(const float* re, const float* im, const float* crm_r, const float* crm_i,
                           int B, int T, int F, int FP, bool frame_major, const float* window,
-                          float* wframes, hipStream_t s);
+                          float* wframes, hipStream_t s, const int* lengths = nullptr);
 int fsn_launch_ola(const float* wframes, const float* window, int B, int T, int length, float* y,
-                   hipStream_t s);
+                   hipStream_t s, const int* lengths = nullptr);
 
 // dft_kernels.hip (any even n_fft / any hop: direct fp64 DFT; reference layout [B][F][T] only)
 int fsn_launch_dft_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag, int T,
@@ -237,13 +253,17 @@ int fsn_launch_decompress(const float* in, float* out, size_t n, hipStream_t s);
 int fsn_launch_compress(const float* in, float* out, size_t n, hipStream_t s);
 int fsn_launch_build_cirm(const float* nr, const float* ni, const float* cr, const float* ci, float* out,
                           size_t n, hipStream_t s);
+// lengths (may be NULL): ragged batch, rows r >= fsn_row_frames(lengths, b, R_valid) of batch entry b are zero too
 int fsn_launch_transpose(const float* in, float* out, int batch, int R, int C, long ld_in, long bs_in,
-                         long ld_out, long bs_out, int R_valid, int C_valid, hipStream_t s);
+                         long ld_out, long bs_out, int R_valid, int C_valid, hipStream_t s,
+                         const int* lengths = nullptr);
 int fsn_launch_crm_rows(const float* crm_r, const float* crm_i, float* out, long r0, long n, int F, int FP, int T,
                         hipStream_t s);
 int fsn_launch_binsum(const float* mag, double* binsum, int B, int Tp, int FP, hipStream_t s);
+// lengths (may be NULL): ragged batch of T frames; utterance b's mean covers its own fsn_row_frames + Tp - T frames
 int fsn_launch_offline_den(const double* binsum, const float* fb_out, float* den_fb, float* den_sb, int B,
-                           int Tp, int F, int FP, int nb, int which, hipStream_t s);
+                           int Tp, int F, int FP, int nb, int which, hipStream_t s, const int* lengths = nullptr,
+                           int T = 0);
 // carry / t0: streaming continuation (running sums of the t0 frames already seen, updated in place); NULL / 0 offline
 int fsn_launch_cumulative_den_fb(const float* mag, float* den, int B, int Tp, int F, int FP, hipStream_t s,
                                  double* carry = nullptr, int t0 = 0);

@@ -14,6 +14,7 @@ import torch
 
 from .acoustics.feature import istft, stft
 from .acoustics.mask import decompress_cIRM
+from .ragged import pad_utterances, trim_rows
 
 
 def initialize_module(path, args=None, initialize=True):
@@ -96,10 +97,25 @@ class Inferencer:
         return enhanced.detach().squeeze(0).cpu().numpy()
 
     @torch.no_grad()
-    def enhance_batch(self, noisy):
+    def enhance_batch(self, noisy, lengths=None):
         """noisy [B, L] (device) -> enhanced [B, L] (device): the fused single-call path
-        (libfsn_hip ``fsn_enhance``) for B independent utterances."""
-        return self.model.enhance(noisy.to(self.device), n_fft=self.n_fft, hop_length=self.hop_length)
+        (libfsn_hip ``fsn_enhance``) for B independent utterances.  ``lengths``: a ragged batch, row b holds
+        ``lengths[b]`` samples (``Model.enhance``; libfsn_hip ``fsn_enhance_ragged``)."""
+        return self.model.enhance(noisy.to(self.device), n_fft=self.n_fft, hop_length=self.hop_length, lengths=lengths)
+
+    @torch.no_grad()
+    def enhance_utterances(self, utterances):
+        """1-D utterances of any lengths -> their enhanced 1-D waveforms (device), in ONE ragged call: padded to the
+        longest, enhanced with their lengths, cut back."""
+        noisy, lengths = pad_utterances(utterances, device=self.device)
+        return trim_rows(self.enhance_batch(noisy, lengths=lengths), lengths)
+
+    def _ragged_ok(self, items):
+        """Whether a group of loader items runs as one ragged call: 1-D utterances (one channel) on the model's fused
+        single call, long enough for the STFT's reflect padding."""
+        return (self.fused_call and getattr(self.model, "_fused", False) and self.n_fft == self.win_length == 512
+                and self.hop_length == 256
+                and all(n.dim() == 2 and n.shape[0] == 1 and n.shape[1] > self.n_fft // 2 for n, _ in items))
 
     def __getattr__(self, name):
         if name in ("mag", "scaled_mask", "sub_band_crm_mask", "overlapped_chunk", "time_domain"):
@@ -112,14 +128,42 @@ class Inferencer:
         inference_type = self.inference_config["type"]
         assert inference_type == "full_band_crm_mask", f"Not implemented Inferencer type: {inference_type}"
         inference_args = self.inference_config.get("args", {})
+        # [inferencer] batch_size (optional, default 1 = the reference's loop): enhance that many loader items per call
+        batch_size = int(self.inference_config.get("batch_size", 1))
+        if batch_size < 1:
+            raise ValueError(f"[inferencer] batch_size must be >= 1, got {batch_size}")
+        group = []
         for noisy, name in self.dataloader:
             assert len(name) == 1, "The batch size of inference stage must 1."
-            name = name[0]
-            enhanced = getattr(self, inference_type)(noisy.to(self.device), inference_args)
-            amp = np.iinfo(np.int16).max
-            enhanced = np.int16(0.8 * amp * enhanced / np.max(np.abs(enhanced)))
-            _write_wav(self.enhanced_dir / f"{name}.wav", enhanced, self.sr)
-            noisy = noisy.detach().squeeze(0).numpy()
-            if np.ndim(noisy) > 1:
-                noisy = noisy[0, :]
-            _write_wav(self.noisy_dir / f"{name}.wav", noisy[: enhanced.shape[-1]], self.sr)
+            if batch_size == 1:
+                enhanced = getattr(self, inference_type)(noisy.to(self.device), inference_args)
+                self._write_item(name[0], noisy, enhanced)
+                continue
+            group.append((noisy, name[0]))
+            if len(group) == batch_size:
+                self._enhance_group(group, inference_type, inference_args)
+                group = []
+        if group:  # the last, partial group
+            self._enhance_group(group, inference_type, inference_args)
+
+    def _enhance_group(self, items, inference_type, inference_args):
+        """Several loader items as ONE ragged call of the library where the model has one; otherwise one
+        ``full_band_crm_mask`` each.  Every file is written exactly as the one-item loop writes it."""
+        if self._ragged_ok(items):
+            outs = self.enhance_utterances([n[0] for n, _ in items])
+            outs = [o.detach().cpu().numpy() for o in outs]
+        else:
+            outs = [getattr(self, inference_type)(n.to(self.device), inference_args) for n, _ in items]
+        for (noisy, name), enhanced in zip(items, outs):
+            self._write_item(name, noisy, enhanced)
+
+    def _write_item(self, name, noisy, enhanced):
+        """base_inferencer.py:178-195: the enhanced waveform peak-normalised to 0.8 of int16 full scale, the noisy
+        input beside it trimmed to the same length."""
+        amp = np.iinfo(np.int16).max
+        enhanced = np.int16(0.8 * amp * enhanced / np.max(np.abs(enhanced)))
+        _write_wav(self.enhanced_dir / f"{name}.wav", enhanced, self.sr)
+        noisy = noisy.detach().squeeze(0).numpy()
+        if np.ndim(noisy) > 1:
+            noisy = noisy[0, :]
+        _write_wav(self.noisy_dir / f"{name}.wav", noisy[: enhanced.shape[-1]], self.sr)

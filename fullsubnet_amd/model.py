@@ -261,11 +261,20 @@ class Model(nn.Module):
         return output[:, :, :, self.look_ahead:]
 
     @torch.no_grad()
-    def enhance(self, noisy, n_fft=512, hop_length=256, return_crm=False):
+    def enhance(self, noisy, n_fft=512, hop_length=256, return_crm=False, lengths=None):
         """Whole path of inferencer.py:130-145 in one call: noisy [B, L] -> enhanced [B, L]
-        (full-band masks for every sample, i.e. B independent utterances)."""
+        (full-band masks for every sample, i.e. B independent utterances).
+
+        ``lengths`` (a sequence of ints or a 1-D integer tensor, one per row, each in ``(n_fft // 2, L]``): a ragged
+        batch - row b holds an utterance of ``lengths[b]`` samples, the rest of the row is never read.  Row b of the
+        result is what enhancing ``noisy[b, :lengths[b]]`` alone gives (within fp32 rounding), zero from
+        ``lengths[b]`` on; the mask (``return_crm``) is [B, 2, F, 1 + L // hop] with frames from
+        ``1 + lengths[b] // hop`` on zero.  Fused configurations at n_fft 512 / hop 256 make ONE library call
+        (``fsn_enhance_ragged``); every other configuration enhances the rows one by one (correct, not faster)."""
         from .acoustics.feature import hann_window
         assert noisy.dim() == 2
+        if lengths is not None:
+            return self._enhance_ragged(noisy, lengths, n_fft, hop_length, return_crm)
         y = noisy.contiguous()
         B, Ls = y.shape
         if not self._fused:  # composed configuration: the same stages as separate calls, no band dropping
@@ -291,4 +300,34 @@ class Model(nn.Module):
                                  _lib.dev_ptr(hann_window(n_fft, y.device)), _lib.dev_ptr(y, "noisy"), B, Ls, n_fft,
                                  hop_length, _lib.dev_ptr(out), _lib.dev_ptr(crm, allow_none=True), ws.data_ptr(),
                                  ws.numel(), _lib.stream_ptr(y.device)))
+        return (out, crm) if return_crm else out
+
+    def _enhance_ragged(self, noisy, lengths, n_fft, hop_length, return_crm):
+        from .acoustics.feature import hann_window
+        from .ragged import check_lengths, frames
+        B, Ls = noisy.shape
+        lens = check_lengths(lengths, B, Ls, n_fft)  # before anything is launched
+        T = frames(Ls, hop_length)
+        if not (self._fused and n_fft == 512 and hop_length == 256):
+            # no single-call form: each row alone through enhance, padded back into the batch's shape
+            out = noisy.new_zeros((B, Ls), dtype=torch.float32)
+            crm = noisy.new_zeros((B, 2, self.num_freqs, T), dtype=torch.float32) if return_crm else None
+            for b, n in enumerate(lens):
+                r = self.enhance(noisy[b:b + 1, :n], n_fft=n_fft, hop_length=hop_length, return_crm=return_crm)
+                if return_crm:
+                    r, c = r
+                    crm[b, :, :, :c.shape[-1]] = c[0]
+                out[b, :n] = r[0]
+            return (out, crm) if return_crm else out
+        y = noisy.contiguous()
+        L = _lib.lib()
+        lens_dev = torch.tensor(lens, dtype=torch.int32, device=y.device)
+        out = torch.empty_like(y)
+        crm = torch.empty((B, 2, self.num_freqs, T), dtype=torch.float32, device=y.device) if return_crm else None
+        ws = _lib.workspace(L.fsn_enhance_workspace_bytes(ctypes.byref(self._cfg), B, Ls, n_fft, hop_length), y.device)
+        _lib.check(L.fsn_enhance_ragged(ctypes.byref(self._cfg), self.packed_weights().data_ptr(),
+                                        _lib.dev_ptr(hann_window(n_fft, y.device)), _lib.dev_ptr(y, "noisy"),
+                                        lens_dev.data_ptr(), B, Ls, n_fft, hop_length, _lib.dev_ptr(out),
+                                        _lib.dev_ptr(crm, allow_none=True), ws.data_ptr(), ws.numel(),
+                                        _lib.stream_ptr(y.device)))
         return (out, crm) if return_crm else out

@@ -60,7 +60,7 @@ const char* fsn_last_error(void);
 /* The ABI revision this header describes.  fsn_version() returns the revision the LIBRARY was built with: a caller
  * compares the two once after loading (fullsubnet_amd/_lib.py raises on a mismatch) - argument lists changed between
  * revisions (116: + fsn_lstm_layer_plan_rows; 115: + fsn_train_rows_pieces; 114: + fsn_lstm2_train_is_persistent; 113: + fsn_gru2_forward; 112: + FSN_ARITH_SAVES16; 111: + the composed families' glue entries; 110: fsn_train_dims.norm, fsn_train_den_elems; 100 -> 101 of round 4: fsn_clip_adam_step's found_inf). */
-#define FSN_ABI_VERSION 117
+#define FSN_ABI_VERSION 118
 int fsn_version(void);
 
 /* ---- STFT / iSTFT : audio_zen/acoustics/feature.py ------------------------------------- */
@@ -169,6 +169,21 @@ size_t fsn_enhance_workspace_bytes(const fsn_fullsubnet_cfg* cfg, int B, int L, 
 int fsn_enhance(const fsn_fullsubnet_cfg* cfg, const void* packed, const float* window,
                 const float* noisy, int B, int L, int n_fft, int hop, float* enhanced, float* crm_out,
                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* fsn_enhance on a RAGGED batch: row b of noisy [B][L_max] holds an utterance of lengths[b] samples (lengths: device
+ * memory, [B]; values are clamped to [n_fft/2 + 1, L_max]).  Row b of the result is, within fp32 rounding, fsn_enhance
+ * of noisy[b][0 .. lengths[b]) alone: the STFT reflects at the row's own end, the offline norm averages over the row's
+ * own T_b + look_ahead frames (T_b = 1 + lengths[b] / hop) and the iSTFT uses only its T_b frames.  Beyond each row's
+ * end:
+ *   - noisy[b][lengths[b] ..] is never read (it may hold anything);
+ *   - enhanced[b][lengths[b] ..] is written as zeros;
+ *   - crm_out (optional) [B][2][F][T_max], T_max = 1 + L_max / hop: frames t >= T_b of row b are zeros.
+ * The models run every row to T_max (the padded steps are the price of one call).  Same arguments, checks, 512 / 256
+ * transform and workspace (fsn_enhance_workspace_bytes(cfg, B, L_max, n_fft, hop)) as fsn_enhance; with every length
+ * equal to L_max the result is bit-identical to fsn_enhance's. */
+int fsn_enhance_ragged(const fsn_fullsubnet_cfg* cfg, const void* packed, const float* window,
+                       const float* noisy, const int* lengths, int B, int L_max, int n_fft, int hop,
+                       float* enhanced, float* crm_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- streaming: the model on k more frames with carried state --------------------------------- */
 
