@@ -102,6 +102,10 @@ SIGNATURES = {
     "fsn_version": (_c.c_int, []),
     "fsn_stft": (_c.c_int, [_f32p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _f32p, _f32p, _f32p, _f32p,
                             _c.c_void_p]),
+    "fsn_stft_ragged": (_c.c_int, [_f32p, _c.c_void_p] + [_c.c_int] * 5 + [_f32p, _f32p, _f32p, _f32p, _c.c_void_p]),
+    "fsn_mask_istft_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "fsn_mask_istft": (_c.c_int, [_f32p, _f32p, _f32p, _c.c_void_p] + [_c.c_int] * 6 + [_f32p, _c.c_int, _f32p, _c.c_void_p,
+                                                                                         _c.c_size_t, _c.c_void_p]),
     "fsn_istft_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
     "fsn_istft": (_c.c_int, [_f32p, _f32p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_int, _f32p,
                              _c.c_void_p, _c.c_size_t, _c.c_void_p]),
@@ -220,6 +224,12 @@ SIGNATURES = {
                                              _c.c_size_t, _c.c_void_p]),
     "fsn_fast_decoder_input": (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _c.c_long] + [_c.c_int] * 6 + [_f32p, _c.c_void_p]),
     "fsn_fast_mask_out": (_c.c_int, [_f32p, _c.c_long] + [_c.c_int] * 5 + [_f32p, _c.c_void_p]),
+    "fsn_fast_spec_rows_ragged": (_c.c_int, [_f32p, _c.c_void_p] + [_c.c_int] * 4 + [_f32p, _c.c_int, _c.c_int, _c.c_void_p]),
+    "fsn_fast_norm_rows_ragged": (_c.c_int, [_f32p, _c.c_void_p] + [_c.c_int] * 5 + [_f32p, _c.c_void_p, _c.c_size_t,
+                                                                                     _c.c_void_p]),
+    "fsn_fast_bottleneck_input_ragged": (_c.c_int, [_f32p, _f32p, _c.c_long, _c.c_void_p] + [_c.c_int] * 8
+                                         + [_f32p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_fast_mask_out_ragged": (_c.c_int, [_f32p, _c.c_long, _c.c_void_p] + [_c.c_int] * 5 + [_f32p, _c.c_void_p]),
     "fsn_profile_enable": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "fsn_stream_timeout_policy": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "fsn_debug_g16_kernels": (_c.c_int, [_c.c_int]),

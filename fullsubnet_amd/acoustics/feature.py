@@ -44,6 +44,38 @@ def stft(y, n_fft, hop_length, win_length, return_phase=True):
     return mag, phase, real, imag
 
 
+def stft_ragged(y, lengths, n_fft, hop_length, win_length):
+    """A ragged batch y [B, L_max] (row b: ``lengths[b]`` samples, device int32 [B]) -> (mag, real, imag) [B, F, T_max]:
+    row b is ``stft(y[b:b + 1, :lengths[b]])`` in its first ``1 + lengths[b] // hop`` frames, zeros after them
+    (libfsn_hip ``fsn_stft_ragged``: n_fft 512 / hop 256 only)."""
+    y = y.contiguous()
+    B, num_samples = y.shape
+    F, T = n_fft // 2 + 1, 1 + num_samples // hop_length
+    real = torch.empty((B, F, T), dtype=torch.float32, device=y.device)
+    imag = torch.empty_like(real)
+    mag = torch.empty_like(real)
+    _lib.check(_lib.lib().fsn_stft_ragged(_lib.dev_ptr(y, "y"), lengths.data_ptr(), B, num_samples, n_fft, hop_length, win_length,
+                                          _lib.dev_ptr(hann_window(n_fft, y.device)), _lib.dev_ptr(real), _lib.dev_ptr(imag),
+                                          _lib.dev_ptr(mag), _lib.stream_ptr(y.device)))
+    return mag, real, imag
+
+
+def mask_istft(crm, real, imag, n_fft, hop_length, win_length, length, lengths=None):
+    """inferencer.py:134-141 in one library call (``fsn_mask_istft``, n_fft 512 / hop 256 only): a model's compressed
+    cIRM [B, 2, F, T] (read in place) on the noisy spectrum real / imag [B, F, T] -> enhanced [B, length].  ``lengths``
+    (device int32 [B], optional): a ragged batch, row b enhanced over its own frames at its own length, zero after it."""
+    crm, real, imag = crm.contiguous(), real.contiguous(), imag.contiguous()
+    B, F, T = real.shape
+    y = torch.empty((B, length), dtype=torch.float32, device=real.device)
+    L = _lib.lib()
+    ws = _lib.workspace(L.fsn_mask_istft_workspace_bytes(B, T, n_fft), real.device)
+    _lib.check(L.fsn_mask_istft(_lib.dev_ptr(crm, "crm"), _lib.dev_ptr(real, "real"), _lib.dev_ptr(imag, "imag"),
+                                None if lengths is None else lengths.data_ptr(), B, F, T, n_fft, hop_length, win_length,
+                                _lib.dev_ptr(hann_window(n_fft, real.device)), length, _lib.dev_ptr(y), ws.data_ptr(),
+                                ws.numel(), _lib.stream_ptr(real.device)))
+    return y
+
+
 def istft(features, n_fft, hop_length, win_length, length=None, input_type="complex"):
     """feature.py:53-91.  features: complex [B, F, T] | (real, imag) | (mag, phase) -> [B, length]."""
     if input_type == "real_imag":

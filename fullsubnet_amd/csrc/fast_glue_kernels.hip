@@ -16,6 +16,12 @@
 //   decoder_input   out[t][b] = enc[t][b] | bottleneck output held for `shrink` frames (frame t takes low-rate frame t / s)
 //   mask_out        [T][Bp][2F] -> [B][2][F][T - look_ahead] (the first look_ahead frames dropped)
 // Statistics in fp64 with a fixed summation order: two runs are bit-identical.
+//
+// Ragged batches (the *_ragged entries): `frames` (device, [B], may be NULL) holds utterance b's STFT frame count T_b
+// before the look-ahead; the row then behaves as a batch of one of T_b + look_ahead frames (fast_row_frames clamps it
+// into [1, T0] so that no value indexes outside a row).  The LSTM blocks are causal, so a row's first T_b + look_ahead
+// steps never see the padded ones; only the glue below depends on a row's length.  NULL is the rectangular path, bit for
+// bit.
 #include "fsn_common.h"
 #include "../../include/fsn_hip.h"
 
@@ -26,6 +32,13 @@ constexpr float kFastEps = 1e-5f;  // offline_laplace_norm's epsilon
 __device__ __forceinline__ int fast_reflect(int j, int M) {
     j = j < 0 ? -j : j;
     return j > M - 1 ? 2 * (M - 1) - j : j;
+}
+
+// utterance b's frames before the look-ahead: frames[b] clamped into [1, T0]; T0 without `frames`
+__device__ __forceinline__ int fast_row_frames(const int* frames, int b, int T0) {
+    if (!frames) return T0;
+    const int t = frames[b];
+    return t < 1 ? 1 : (t > T0 ? T0 : t);
 }
 
 // fixed-order sum of one fp64 value per thread of a 256-thread workgroup; the result in every thread
@@ -39,16 +52,19 @@ __device__ __forceinline__ double fast_block_sum(double v, double* sh) {
     return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
-// [B][F][T0] -> [T][Bp][Fp]; zero beyond (T0, B, F): transposing copy through LDS, both sides coalesced
+// [B][F][T0] -> [T][Bp][Fp]; zero beyond (T0, B, F): transposing copy through LDS, both sides coalesced.
+// frames: row b's frames t >= T_b are written as zeros (the row's own look-ahead frames); they are never read
 __global__ __launch_bounds__(256) void fast_spec_rows_kernel(const float* __restrict__ mag, float* __restrict__ rows, int B,
-                                                             int F, int T0, int T, int Bp, int Fp) {
+                                                             int F, int T0, int T, int Bp, int Fp,
+                                                             const int* __restrict__ frames) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z, f0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int Tb = b < B ? fast_row_frames(frames, b, T0) : T0;
 #pragma unroll
     for (int j = ty; j < 32; j += 8) {
         const int f = f0 + j, t = t0 + tx;
-        tile[j][tx] = (b < B && f < F && t < T0) ? mag[((size_t)b * F + f) * T0 + t] : 0.f;
+        tile[j][tx] = (b < B && f < F && t < Tb) ? mag[((size_t)b * F + f) * T0 + t] : 0.f;
     }
     __syncthreads();
 #pragma unroll
@@ -58,13 +74,14 @@ __global__ __launch_bounds__(256) void fast_spec_rows_kernel(const float* __rest
     }
 }
 
-// den[b] = float(sum of x[t][b][c] / (T C)) + eps, one workgroup per utterance
+// den[b] = float(sum of x[t][b][c] / (T C)) + eps, one workgroup per utterance.
+// frames: the sum and the count cover row b's own T_b + la frames only
 __global__ __launch_bounds__(256) void fast_mean_kernel(const float* __restrict__ x, float* __restrict__ den, int T, int Bp,
-                                                        int C) {
+                                                        int C, const int* __restrict__ frames, int la) {
     __shared__ double sh[4];
     const int b = blockIdx.x;
     double s = 0.0;
-    const long n = (long)T * C;
+    const long n = (long)(fast_row_frames(frames, b, T - la) + la) * C;
     for (long p = threadIdx.x; p < n; p += 256) {
         const long t = p / C, c = p % C;
         s += (double)x[(t * Bp + b) * C + c];
@@ -83,12 +100,18 @@ __global__ __launch_bounds__(256) void fast_scale_kernel(const float* __restrict
 }
 
 struct FastUnits {
-    int T, Ts, B, Bp, M, n_mel, n_enc, shrink;
+    int T, Ts, B, Bp, M, n_mel, n_enc, shrink, la;
 };
 
-// ds[src][ts][b][m] and den[b]: one workgroup per utterance
+__host__ __device__ inline int fast_low_rate_frames(int T, int shrink) { return 1 + (T - 1 + shrink - 1) / shrink; }
+
+// ds[src][ts][b][m] and den[b]: one workgroup per utterance.
+// frames: row b is an utterance of Tr = T_b + la frames with Ts_b = fast_low_rate_frames(Tr) low-rate frames - its last
+// block ends at Tr (short when (Tr - 1) % shrink != 0, averaged on its own either way, model.py:108-129), the mean
+// divides by M W Ts_b, and its low-rate frames ts >= Ts_b are written as zeros (finite, deterministic, never used)
 __global__ __launch_bounds__(256) void fast_ds_kernel(const float* __restrict__ mel, const float* __restrict__ enc, long ld_enc,
-                                                      float* __restrict__ ds, float* __restrict__ den, const FastUnits a) {
+                                                      float* __restrict__ ds, float* __restrict__ den, const FastUnits a,
+                                                      const int* __restrict__ frames) {
     extern __shared__ int mult[];  // [2][M]: how many (unit, window column) pairs read band m
     __shared__ double sh[4];
     const int b = blockIdx.x, M = a.M;
@@ -103,11 +126,18 @@ __global__ __launch_bounds__(256) void fast_ds_kernel(const float* __restrict__ 
     __syncthreads();
     double s = 0.0;
     const size_t half = (size_t)a.Ts * a.B * M;
+    const int Tr = frames ? fast_row_frames(frames, b, a.T - a.la) + a.la : a.T;
+    const int Tsb = frames ? fast_low_rate_frames(Tr, a.shrink) : a.Ts;
     for (int p = threadIdx.x; p < a.Ts * M; p += 256) {
         const int ts = p / M, m = p % M;
+        if (ts >= Tsb) {
+            ds[((size_t)ts * a.B + b) * M + m] = 0.f;
+            ds[half + ((size_t)ts * a.B + b) * M + m] = 0.f;
+            continue;
+        }
         const int f0 = ts == 0 ? 0 : 1 + (ts - 1) * a.shrink;
         int f1 = ts == 0 ? 1 : f0 + a.shrink;
-        f1 = f1 < a.T ? f1 : a.T;
+        f1 = f1 < Tr ? f1 : Tr;
         float sm = 0.f, se = 0.f;
         for (int t = f0; t < f1; ++t) {
             sm += mel[((size_t)t * a.Bp + b) * M + m];
@@ -120,7 +150,7 @@ __global__ __launch_bounds__(256) void fast_ds_kernel(const float* __restrict__ 
         s += (double)mult[m] * (double)vm + (double)mult[M + m] * (double)ve;
     }
     const double tot = fast_block_sum(s, sh);
-    if (threadIdx.x == 0) den[b] = (float)(tot / ((double)M * (w_mel + w_enc) * a.Ts)) + kFastEps;
+    if (threadIdx.x == 0) den[b] = (float)(tot / ((double)M * (w_mel + w_enc) * Tsb)) + kFastEps;
 }
 
 // out[ts][b M + m][w]: one workgroup per (ts, utterance); rows beyond B M are zeroed by the last utterance's workgroup
@@ -149,7 +179,10 @@ __global__ __launch_bounds__(256) void fast_units_kernel(const float* __restrict
     }
 }
 
-// out[t][b][0 .. M) = enc[t][b]; out[t][b][M .. 2M) = slow[t / shrink][b M + m]; rows beyond B zero
+// out[t][b][0 .. M) = enc[t][b]; out[t][b][M .. 2M) = slow[t / shrink][b M + m]; rows beyond B zero.
+// Ragged batches need no change here: for every frame t < Tr = T_b + la of row b, t / shrink <= (Tr - 1) / shrink <
+// 1 + ceil((Tr - 1) / shrink) = Ts_b, so a row's own frames only take its own low-rate frames; frames t >= Tr take the
+// bottleneck's output on the zeroed units, which is finite and reaches only the row's dropped mask frames (causal LSTMs).
 __global__ __launch_bounds__(256) void fast_decoder_input_kernel(const float* __restrict__ enc, long ld_enc,
                                                                  const float* __restrict__ slow, long ld_slow_t, long ld_slow_r,
                                                                  float* __restrict__ out, int T, int B, int Bp, int M,
@@ -171,16 +204,18 @@ __global__ __launch_bounds__(256) void fast_decoder_input_kernel(const float* __
     out[(size_t)t * per_t + i] = v;
 }
 
-// o[T][Bp][ld] (2F columns used) -> mask[B][2F][T0], T0 = T - la, frame t0 of the mask = frame t0 + la of o
+// o[T][Bp][ld] (2F columns used) -> mask[B][2F][T0], T0 = T - la, frame t0 of the mask = frame t0 + la of o.
+// frames: row b's mask frames t0 >= T_b are written as zeros
 __global__ __launch_bounds__(256) void fast_mask_out_kernel(const float* __restrict__ o, long ld, float* __restrict__ mask, int T0,
-                                                            int la, int Bp, int cols) {
+                                                            int la, int Bp, int cols, const int* __restrict__ frames) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z, c0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int Tb = fast_row_frames(frames, b, T0);
 #pragma unroll
     for (int j = ty; j < 32; j += 8) {
         const int t = t0 + j, c = c0 + tx;
-        tile[j][tx] = (t < T0 && c < cols) ? o[((size_t)(t + la) * Bp + b) * ld + c] : 0.f;
+        tile[j][tx] = (t < Tb && c < cols) ? o[((size_t)(t + la) * Bp + b) * ld + c] : 0.f;
     }
     __syncthreads();
 #pragma unroll
@@ -189,8 +224,6 @@ __global__ __launch_bounds__(256) void fast_mask_out_kernel(const float* __restr
         if (c < cols && t < T0) mask[((size_t)b * cols + c) * T0 + t] = tile[tx][j];
     }
 }
-
-int fast_low_rate_frames(int T, int shrink) { return 1 + (T - 1 + shrink - 1) / shrink; }
 
 }  // namespace
 
@@ -202,44 +235,69 @@ extern "C" size_t fsn_fast_glue_workspace_bytes(int T, int B, int num_mels, int 
     return fsn_round_up_sz(2 * Ts * B * num_mels * sizeof(float), 256) + fsn_round_up_sz((size_t)B * sizeof(float), 256);
 }
 
-extern "C" int fsn_fast_spec_rows(const float* mag, int B, int F, int T0, int look_ahead, float* rows, int Bp, int Fp, void* stream) {
+// The entries below and their *_ragged forms share one body each; frames == NULL is the rectangular batch.
+static int fast_spec_rows(const float* mag, const int* frames, int B, int F, int T0, int look_ahead, float* rows, int Bp, int Fp,
+                          void* stream) {
     FsnCallScope scope(stream);
     FSN_REQUIRE(mag && rows, "NULL pointer argument");
     FSN_REQUIRE(B >= 1 && F >= 1 && T0 >= 1 && look_ahead >= 0 && Bp >= B && Fp >= F && Bp <= 65535,
                 "fast spec rows: need B, F, T0 >= 1, look_ahead >= 0 and padded sizes not below (B, F)");
     const int T = T0 + look_ahead;
     hipLaunchKernelGGL(fast_spec_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)((Fp + 31) / 32), (unsigned)Bp), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), mag, rows, B, F, T0, T, Bp, Fp);
+                       static_cast<hipStream_t>(stream), mag, rows, B, F, T0, T, Bp, Fp, frames);
     return fsn_check_launch("fast_spec_rows_kernel");
 }
 
-extern "C" int fsn_fast_norm_rows(const float* x, int T, int B, int Bp, int C, float* out, void* workspace, size_t workspace_bytes,
-                                  void* stream) {
+extern "C" int fsn_fast_spec_rows(const float* mag, int B, int F, int T0, int look_ahead, float* rows, int Bp, int Fp, void* stream) {
+    return fast_spec_rows(mag, nullptr, B, F, T0, look_ahead, rows, Bp, Fp, stream);
+}
+
+extern "C" int fsn_fast_spec_rows_ragged(const float* mag, const int* frames, int B, int F, int T0, int look_ahead, float* rows,
+                                         int Bp, int Fp, void* stream) {
+    FSN_REQUIRE(frames, "NULL pointer argument");
+    return fast_spec_rows(mag, frames, B, F, T0, look_ahead, rows, Bp, Fp, stream);
+}
+
+static int fast_norm_rows(const float* x, const int* frames, int T, int B, int Bp, int C, int look_ahead, float* out,
+                          void* workspace, size_t workspace_bytes, void* stream) {
     FsnCallScope scope(stream);
     FSN_REQUIRE(x && out && workspace, "NULL pointer argument");
     FSN_REQUIRE(T >= 1 && B >= 1 && Bp >= B && C >= 1, "fast norm rows: need T, B, C >= 1 and Bp >= B");
+    FSN_REQUIRE(look_ahead >= 0 && look_ahead < T, "fast norm rows: need 0 <= look_ahead < T");
     if (workspace_bytes < fsn_round_up_sz((size_t)B * sizeof(float), 256)) {
         fsn_set_error("fast norm rows: workspace too small");
         return FSN_ERR_WORKSPACE;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* den = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(fast_mean_kernel, dim3((unsigned)B), dim3(256), 0, s, x, den, T, Bp, C);
+    hipLaunchKernelGGL(fast_mean_kernel, dim3((unsigned)B), dim3(256), 0, s, x, den, T, Bp, C, frames, look_ahead);
     FSN_TRY_LAUNCH("fast_mean_kernel");
     const long n = (long)T * Bp * C;
     hipLaunchKernelGGL(fast_scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, den, out, n, B, Bp, C);
     return fsn_check_launch("fast_scale_kernel");
 }
 
-extern "C" int fsn_fast_bottleneck_input(const float* mel, const float* enc, long ld_enc, int T, int B, int Bp, int num_mels,
-                                         int mel_neighbors, int enc_neighbors, int shrink, float* out, int Np, int Wp,
+extern "C" int fsn_fast_norm_rows(const float* x, int T, int B, int Bp, int C, float* out, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    return fast_norm_rows(x, nullptr, T, B, Bp, C, 0, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fsn_fast_norm_rows_ragged(const float* x, const int* frames, int look_ahead, int T, int B, int Bp, int C, float* out,
                                          void* workspace, size_t workspace_bytes, void* stream) {
+    FSN_REQUIRE(frames, "NULL pointer argument");
+    return fast_norm_rows(x, frames, T, B, Bp, C, look_ahead, out, workspace, workspace_bytes, stream);
+}
+
+static int fast_bottleneck_input(const float* mel, const float* enc, long ld_enc, const int* frames, int look_ahead, int T, int B,
+                                 int Bp, int num_mels, int mel_neighbors, int enc_neighbors, int shrink, float* out, int Np, int Wp,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
     FsnCallScope scope(stream);
     FSN_REQUIRE(mel && enc && out && workspace, "NULL pointer argument");
     FSN_REQUIRE(T >= 2 && B >= 1 && Bp >= B && B <= 65535 && num_mels >= 2 && num_mels <= 4096 && ld_enc >= num_mels && shrink >= 1,
                 "fast bottleneck input: need T >= 2, 1 <= B <= Bp, 2 <= num_mels <= 4096, ld_enc >= num_mels, shrink >= 1");
     FSN_REQUIRE(mel_neighbors >= 0 && enc_neighbors >= 0 && mel_neighbors < num_mels && enc_neighbors < num_mels,
                 "fast bottleneck input: neighbours must be in [0, num_mels)");
+    FSN_REQUIRE(look_ahead >= 0 && look_ahead < T, "fast bottleneck input: need 0 <= look_ahead < T");
     const int W = 2 * mel_neighbors + 1 + 2 * enc_neighbors + 1;
     FSN_REQUIRE(Wp >= W && (long)Np >= (long)B * num_mels, "fast bottleneck input: padded sizes below (B num_mels, unit width %d)", W);
     if (workspace_bytes < fsn_fast_glue_workspace_bytes(T, B, num_mels, shrink)) {
@@ -256,13 +314,29 @@ extern "C" int fsn_fast_bottleneck_input(const float* mel, const float* enc, lon
     a.n_mel = mel_neighbors;
     a.n_enc = enc_neighbors;
     a.shrink = shrink;
+    a.la = look_ahead;
     float* ds = static_cast<float*>(workspace);
     float* den = reinterpret_cast<float*>(static_cast<char*>(workspace) + fsn_round_up_sz((size_t)2 * a.Ts * B * num_mels * sizeof(float), 256));
     const size_t lds = (size_t)2 * num_mels * sizeof(float);
-    hipLaunchKernelGGL(fast_ds_kernel, dim3((unsigned)B), dim3(256), lds, s, mel, enc, ld_enc, ds, den, a);
+    hipLaunchKernelGGL(fast_ds_kernel, dim3((unsigned)B), dim3(256), lds, s, mel, enc, ld_enc, ds, den, a, frames);
     FSN_TRY_LAUNCH("fast_ds_kernel");
     hipLaunchKernelGGL(fast_units_kernel, dim3((unsigned)a.Ts, (unsigned)B), dim3(256), lds, s, ds, den, out, a, Np, Wp);
     return fsn_check_launch("fast_units_kernel");
+}
+
+extern "C" int fsn_fast_bottleneck_input(const float* mel, const float* enc, long ld_enc, int T, int B, int Bp, int num_mels,
+                                         int mel_neighbors, int enc_neighbors, int shrink, float* out, int Np, int Wp,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+    return fast_bottleneck_input(mel, enc, ld_enc, nullptr, 0, T, B, Bp, num_mels, mel_neighbors, enc_neighbors, shrink, out, Np, Wp,
+                                 workspace, workspace_bytes, stream);
+}
+
+extern "C" int fsn_fast_bottleneck_input_ragged(const float* mel, const float* enc, long ld_enc, const int* frames, int look_ahead,
+                                                int T, int B, int Bp, int num_mels, int mel_neighbors, int enc_neighbors, int shrink,
+                                                float* out, int Np, int Wp, void* workspace, size_t workspace_bytes, void* stream) {
+    FSN_REQUIRE(frames, "NULL pointer argument");
+    return fast_bottleneck_input(mel, enc, ld_enc, frames, look_ahead, T, B, Bp, num_mels, mel_neighbors, enc_neighbors, shrink, out,
+                                 Np, Wp, workspace, workspace_bytes, stream);
 }
 
 extern "C" int fsn_fast_decoder_input(const float* enc, long ld_enc, const float* slow, long ld_slow_frame, long ld_slow_row, int relu,
@@ -278,13 +352,24 @@ extern "C" int fsn_fast_decoder_input(const float* enc, long ld_enc, const float
     return fsn_check_launch("fast_decoder_input_kernel");
 }
 
-extern "C" int fsn_fast_mask_out(const float* o, long ld, int T, int B, int Bp, int F, int look_ahead, float* mask, void* stream) {
+static int fast_mask_out(const float* o, long ld, const int* frames, int T, int B, int Bp, int F, int look_ahead, float* mask,
+                         void* stream) {
     FsnCallScope scope(stream);
     FSN_REQUIRE(o && mask, "NULL pointer argument");
     FSN_REQUIRE(B >= 1 && Bp >= B && B <= 65535 && F >= 1 && ld >= 2 * (long)F && look_ahead >= 0 && T > look_ahead,
                 "fast mask out: need 1 <= B <= Bp, ld >= 2 F, 0 <= look_ahead < T");
     const int T0 = T - look_ahead;
     hipLaunchKernelGGL(fast_mask_out_kernel, dim3((unsigned)((T0 + 31) / 32), (unsigned)((2 * F + 31) / 32), (unsigned)B), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), o, ld, mask, T0, look_ahead, Bp, 2 * F);
+                       static_cast<hipStream_t>(stream), o, ld, mask, T0, look_ahead, Bp, 2 * F, frames);
     return fsn_check_launch("fast_mask_out_kernel");
+}
+
+extern "C" int fsn_fast_mask_out(const float* o, long ld, int T, int B, int Bp, int F, int look_ahead, float* mask, void* stream) {
+    return fast_mask_out(o, ld, nullptr, T, B, Bp, F, look_ahead, mask, stream);
+}
+
+extern "C" int fsn_fast_mask_out_ragged(const float* o, long ld, const int* frames, int T, int B, int Bp, int F, int look_ahead,
+                                        float* mask, void* stream) {
+    FSN_REQUIRE(frames, "NULL pointer argument");
+    return fast_mask_out(o, ld, frames, T, B, Bp, F, look_ahead, mask, stream);
 }

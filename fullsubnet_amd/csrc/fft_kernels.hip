@@ -217,10 +217,13 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ y, 
                 if (mag) mag[o] = am;
             }
             if (tB < T) {
+                // ragged: frame B past the row's end transforms a zero frame, zero up to the split's rounding (~1e-16
+                // next to a live frame A); the reference layout (fsn_stft_ragged) writes exact zeros there
+                const bool on = tB < Tb;
                 const long o = ((long)b * F + k) * T + tB;
-                if (re) re[o] = br;
-                if (im) im[o] = bi;
-                if (mag) mag[o] = bm;
+                if (re) re[o] = on ? br : 0.f;
+                if (im) im[o] = on ? bi : 0.f;
+                if (mag) mag[o] = on ? bm : 0.f;
             }
         }
     }
@@ -239,6 +242,8 @@ __device__ __forceinline__ float decompress1(float m) {
 // after the irfft and after the window product like ATen does.
 // inferencer.py:137-140 + feature.py:84-91 (torch.istft up to the overlap-add).
 // lengths (may be NULL): ragged batch - frames t >= T_b of row b are taken as zero spectra (their mask is never read).
+// crm_bs: the batch stride of crm_r / crm_i in the reference layout (F T: [B][F][T] planes; 2 F T: a model's [B][2][F][T]
+// output read in place); the frame-major layout reads them like re / im.
 // ---------------------------------------------------------------------------------------------
 template <bool FRAME_MAJOR>
 __global__ __launch_bounds__(256) void mask_irfft_kernel(const float* __restrict__ re, const float* __restrict__ im,
@@ -246,7 +251,7 @@ __global__ __launch_bounds__(256) void mask_irfft_kernel(const float* __restrict
                                                          const float* __restrict__ crm_i,
                                                          const float* __restrict__ window,
                                                          float* __restrict__ wframes, int B, int T, int F, int FP,
-                                                         const int* __restrict__ lengths) {
+                                                         const int* __restrict__ lengths, long crm_bs) {
     __shared__ double lds[kWavesPerBlock][2][kLdsPoints];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int pairs_per_b = (T + 1) >> 1;
@@ -270,7 +275,8 @@ __global__ __launch_bounds__(256) void mask_irfft_kernel(const float* __restrict
                 const long o = FRAME_MAJOR ? ((long)b * T + t) * FP + k : ((long)b * F + k) * T + t;
                 const float xr = re[o], xi = im[o];
                 if (crm_r) {
-                    const float mr = decompress1(crm_r[o]), mi = decompress1(crm_i[o]);
+                    const long oc = FRAME_MAJOR ? o : (long)b * crm_bs + (long)k * T + t;
+                    const float mr = decompress1(crm_r[oc]), mi = decompress1(crm_i[oc]);
                     s[q][0] = mr * xr - mi * xi;
                     s[q][1] = mi * xr + mr * xi;
                 } else {
@@ -368,15 +374,16 @@ int fsn_launch_stft(const float* y, int B, int L, const float* window, float* re
 
 int fsn_launch_mask_irfft(const float* re, const float* im, const float* crm_r, const float* crm_i, int B, int T,
                           int F, int FP, bool frame_major, const float* window, float* wframes, hipStream_t s,
-                          const int* lengths) {
+                          const int* lengths, long crm_batch_stride) {
     const long pairs = (long)B * ((T + 1) / 2);
     const unsigned grid = (unsigned)((pairs + kWavesPerBlock - 1) / kWavesPerBlock);
+    const long crm_bs = crm_batch_stride > 0 ? crm_batch_stride : (long)F * T;
     if (frame_major)
         hipLaunchKernelGGL(mask_irfft_kernel<true>, dim3(grid), dim3(256), 0, s, re, im, crm_r, crm_i, window,
-                           wframes, B, T, F, FP, lengths);
+                           wframes, B, T, F, FP, lengths, crm_bs);
     else
         hipLaunchKernelGGL(mask_irfft_kernel<false>, dim3(grid), dim3(256), 0, s, re, im, crm_r, crm_i, window,
-                           wframes, B, T, F, FP, lengths);
+                           wframes, B, T, F, FP, lengths, crm_bs);
     return fsn_check_launch("mask_irfft_kernel");
 }
 

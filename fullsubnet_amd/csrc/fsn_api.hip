@@ -1765,6 +1765,49 @@ extern "C" int fsn_istft(const float* real, const float* imag, int B, int T, int
     return fsn_launch_ola(wf, window, B, T, length, y, s);
 }
 
+// ragged batches in the reference layout: 512 / 256 only (the radix-8 kernels' lengths path)
+extern "C" int fsn_stft_ragged(const float* y, const int* lengths, int B, int L_max, int n_fft, int hop, int win_length,
+                               const float* window, float* real, float* imag, float* mag, void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(fast_fft(n_fft, hop) && win_length == n_fft,
+                "fsn_stft_ragged: only n_fft = win_length = 512, hop = 256 is built (got %d/%d/%d)", n_fft, win_length, hop);
+    FSN_REQUIRE(y && lengths && window, "NULL pointer argument");
+    FSN_REQUIRE(B >= 1 && L_max > n_fft / 2, "need B >= 1 and L_max > n_fft/2 (reflect padding), got B=%d L_max=%d", B, L_max);
+    const int T = 1 + L_max / hop, F = n_fft / 2 + 1;
+    FSN_REQUIRE((long)B * T <= 0x7fffffffL, "too many frames");
+    return fsn_launch_stft(y, B, L_max, window, real, imag, mag, T, T, F, fsn_fpad(F), false, static_cast<hipStream_t>(stream),
+                           lengths);
+}
+
+extern "C" size_t fsn_mask_istft_workspace_bytes(int B, int T, int n_fft) {
+    if (B < 1 || T < 1 || n_fft != 512) return 0;
+    return fsn_istft_workspace_bytes(B, T, n_fft);
+}
+
+// inferencer.py:134-141 on a model's output: decompress_cIRM + complex mask + iSTFT, the [B][2][F][T] mask read in place
+extern "C" int fsn_mask_istft(const float* crm, const float* real, const float* imag, const int* lengths, int B, int F, int T,
+                              int n_fft, int hop, int win_length, const float* window, int length, float* y, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(fast_fft(n_fft, hop) && win_length == n_fft,
+                "fsn_mask_istft: only n_fft = win_length = 512, hop = 256 is built (got %d/%d/%d)", n_fft, win_length, hop);
+    FSN_TRY(check_bt(B, T));
+    FSN_REQUIRE(F == n_fft / 2 + 1, "fsn_mask_istft: F = %d, need n_fft / 2 + 1 = %d", F, n_fft / 2 + 1);
+    FSN_REQUIRE(crm && real && imag && window && y && workspace, "NULL pointer argument");
+    FSN_REQUIRE(length >= 1, "length %d < 1", length);
+    FSN_REQUIRE(!lengths || (length > n_fft / 2 && T == 1 + length / hop),
+                "fsn_mask_istft: with lengths, need length > n_fft/2 and T = 1 + length / hop (got length %d, T %d)", length, T);
+    if (workspace_bytes < fsn_mask_istft_workspace_bytes(B, T, n_fft)) {
+        fsn_set_error("workspace too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* wf = static_cast<float*>(workspace);
+    FSN_TRY(fsn_launch_mask_irfft(real, imag, crm, crm + (size_t)F * T, B, T, F, fsn_fpad(F), false, window, wf, s, lengths,
+                                  2L * F * T));
+    return fsn_launch_ola(wf, window, B, T, length, y, s, lengths);
+}
+
 // ---- elementwise boundary --------------------------------------------------------------------
 extern "C" int fsn_decompress_cirm(const float* mask, float* out, size_t n, void* stream) {
     CallScope scope(stream);

@@ -236,9 +236,10 @@ struct FsnStream {
 // length is then the row stride and the longest row, T its frame count.
 int fsn_launch_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag,
                     int T, int Tp, int F, int FP, bool frame_major, hipStream_t s, const int* lengths = nullptr);
+// crm_batch_stride: the reference layout's batch stride of crm_r / crm_i (0: F T, separate [B][F][T] planes)
 int fsn_launch_mask_irfft(const float* re, const float* im, const float* crm_r, const float* crm_i,
                           int B, int T, int F, int FP, bool frame_major, const float* window,
-                          float* wframes, hipStream_t s, const int* lengths = nullptr);
+                          float* wframes, hipStream_t s, const int* lengths = nullptr, long crm_batch_stride = 0);
 int fsn_launch_ola(const float* wframes, const float* window, int B, int T, int length, float* y,
                    hipStream_t s, const int* lengths = nullptr);
 

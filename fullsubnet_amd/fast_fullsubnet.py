@@ -126,11 +126,22 @@ class Model(BaseModel):
         enc0, enc1 = self.encoder
         dec0, dec1 = self.decoder_lstm
         B = mix_mag.shape[0]
+        return (self._rows_config_ok(mix_mag.shape[2]) and pair_fusable(enc0, enc1, B) and pair_fusable(dec0, dec1, B)
+                and mix_mag.shape[3] + self.look_ahead >= 2 and mix_mag.dtype == torch.float32)
+
+    def _rows_config_ok(self, n_bins):
+        """The part of ``_rows_path_ok`` that depends on the configuration alone (not on the batch)."""
+        enc0, enc1 = self.encoder
+        dec0, dec1 = self.decoder_lstm
         return (getattr(self, "rows_path", True) and self.norm == self.offline_laplace_norm and self.num_mels % 16 == 0
                 and self.num_mels == enc0.input_size == enc1.output_size and dec0.input_size == 2 * self.num_mels
-                and dec1.output_size == 2 * mix_mag.shape[2] and self.bottleneck.cell == "LSTM"
-                and self.bottleneck.output_size == 1 and pair_fusable(enc0, enc1, B) and pair_fusable(dec0, dec1, B)
-                and mix_mag.shape[3] + self.look_ahead >= 2 and mix_mag.dtype == torch.float32)
+                and dec1.output_size == 2 * n_bins and self.bottleneck.cell == "LSTM"
+                and self.bottleneck.output_size == 1 and pair_fusable(enc0, enc1, 1) and pair_fusable(dec0, dec1, 1))
+
+    def ragged_enhance_ok(self, n_fft, hop_length):
+        """Whether ``enhance(noisy, lengths=...)`` is ONE batched call (not a row-by-row loop) at this transform: the
+        library's 512 / 256 STFT, mask + iSTFT and the time-major glue of ``_forward_rows``."""
+        return n_fft == 512 and hop_length == 256 and self._rows_config_ok(n_fft // 2 + 1)
 
     def _bottleneck_rows(self, units, N):
         """The bottleneck block on time-major rows [Ts, Np, Wp] -> ([Ts, Np(, 1)] output, 1 if it is still the output
@@ -156,9 +167,10 @@ class Model(BaseModel):
             return out, 1
         return bn.forward_time_major(units, N, rows_out=True), 0
 
-    def _forward_rows(self, mix_mag):
+    def _forward_rows(self, mix_mag, frames=None):
         """The inference forward with every tensor between the blocks time-major and the glue on fast_glue_kernels.hip
-        (model.py:143-202 line by line in the comments)."""
+        (model.py:143-202 line by line in the comments).  ``frames`` (validated ints): a ragged batch through the glue's
+        *_ragged entries - the blocks between them are causal and run every row to T."""
         L = _lib.lib()
         dev = mix_mag.device
         st = _lib.stream_ptr(dev)
@@ -169,14 +181,23 @@ class Model(BaseModel):
         Bp, Fp = (B + 15) // 16 * 16, (F + 15) // 16 * 16
         f32 = dict(dtype=torch.float32, device=dev)
         ws = _lib.workspace(L.fsn_fast_glue_workspace_bytes(T, B, M, s), dev)
+        fr = None if frames is None else torch.tensor(frames, dtype=torch.int32, device=dev)
         # :151-157 pad + mel_scale
         rows = torch.empty((T, Bp, Fp), **f32)
-        _lib.check(L.fsn_fast_spec_rows(_lib.dev_ptr(mag, "mix_mag"), B, F, T0, la, _lib.dev_ptr(rows), Bp, Fp, st))
+        if fr is None:
+            _lib.check(L.fsn_fast_spec_rows(_lib.dev_ptr(mag, "mix_mag"), B, F, T0, la, _lib.dev_ptr(rows), Bp, Fp, st))
+        else:
+            _lib.check(L.fsn_fast_spec_rows_ragged(_lib.dev_ptr(mag, "mix_mag"), fr.data_ptr(), B, F, T0, la, _lib.dev_ptr(rows),
+                                                   Bp, Fp, st))
         w, b = self.mel_scale.linear_weights()
         mel = linear_infer(rows.reshape(T * Bp, Fp), w, b, False)                       # [T Bp, M]
         # :160 norm -> encoder
         enc_in = torch.empty((T, Bp, M), **f32)
-        _lib.check(L.fsn_fast_norm_rows(_lib.dev_ptr(mel), T, B, Bp, M, _lib.dev_ptr(enc_in), ws.data_ptr(), ws.numel(), st))
+        if fr is None:
+            _lib.check(L.fsn_fast_norm_rows(_lib.dev_ptr(mel), T, B, Bp, M, _lib.dev_ptr(enc_in), ws.data_ptr(), ws.numel(), st))
+        else:
+            _lib.check(L.fsn_fast_norm_rows_ragged(_lib.dev_ptr(mel), fr.data_ptr(), la, T, B, Bp, M, _lib.dev_ptr(enc_in),
+                                                   ws.data_ptr(), ws.numel(), st))
         enc = pair_forward_rows(*self.encoder, enc_in)                                   # [T, Bp, M]
         # :163-178 unit windows, down-sampling, norm -> bottleneck
         n_mel, n_enc = self.noisy_input_num_neighbors, self.enc_output_num_neighbors
@@ -186,8 +207,13 @@ class Model(BaseModel):
         # utterances x 64 bands = 448 row tiles: 224 workgroups x 2 tiles instead of 256 x 1 + 192 tiles step by step)
         Np, Ts = L.fsn_lstm_layer_plan_rows((N + 15) // 16 * 16, self.bottleneck.hidden_size), L.fsn_fast_low_rate_frames(T, s)
         units = torch.empty((Ts, Np, Wp), **f32)
-        _lib.check(L.fsn_fast_bottleneck_input(_lib.dev_ptr(mel), _lib.dev_ptr(enc), enc.stride(1), T, B, Bp, M, n_mel, n_enc, s,
-                                               _lib.dev_ptr(units), Np, Wp, ws.data_ptr(), ws.numel(), st))
+        if fr is None:
+            _lib.check(L.fsn_fast_bottleneck_input(_lib.dev_ptr(mel), _lib.dev_ptr(enc), enc.stride(1), T, B, Bp, M, n_mel, n_enc,
+                                                   s, _lib.dev_ptr(units), Np, Wp, ws.data_ptr(), ws.numel(), st))
+        else:
+            _lib.check(L.fsn_fast_bottleneck_input_ragged(_lib.dev_ptr(mel), _lib.dev_ptr(enc), enc.stride(1), fr.data_ptr(), la,
+                                                          T, B, Bp, M, n_mel, n_enc, s, _lib.dev_ptr(units), Np, Wp,
+                                                          ws.data_ptr(), ws.numel(), st))
         slow, relu = self._bottleneck_rows(units, N)                                     # [Ts, Np(, 1)]
         # :180-190 up-sampling, cat -> decoder
         dec_in = torch.empty((T, Bp, 2 * M), **f32)
@@ -196,22 +222,44 @@ class Model(BaseModel):
         out = pair_forward_rows(*self.decoder_lstm, dec_in)                              # [T, Bp, 2 F]
         # :200-202 reshape + look-ahead slice
         mask = torch.empty((B, 2, F, T0), **f32)
-        _lib.check(L.fsn_fast_mask_out(_lib.dev_ptr(out), out.stride(1), T, B, Bp, F, la, _lib.dev_ptr(mask), st))
+        if fr is None:
+            _lib.check(L.fsn_fast_mask_out(_lib.dev_ptr(out), out.stride(1), T, B, Bp, F, la, _lib.dev_ptr(mask), st))
+        else:
+            _lib.check(L.fsn_fast_mask_out_ragged(_lib.dev_ptr(out), out.stride(1), fr.data_ptr(), T, B, Bp, F, la,
+                                                  _lib.dev_ptr(mask), st))
         return mask
 
-    def forward(self, mix_mag):
-        """mix_mag [B, 1, F, T] -> [B, 2, F, T] (model.py:143-202)."""
+    def _forward_row_by_row(self, mix_mag, frames):
+        """A ragged batch without the glue's ragged form: each row alone, padded back with zero frames."""
+        T0 = mix_mag.shape[3]
+        rows = [self.forward(mix_mag[b:b + 1, :, :, :t]) for b, t in enumerate(frames)]
+        return torch.cat([nn.functional.pad(r, (0, T0 - t)) for r, t in zip(rows, frames)], dim=0)
+
+    def forward(self, mix_mag, frames=None):
+        """mix_mag [B, 1, F, T] -> [B, 2, F, T] (model.py:143-202).
+
+        ``frames`` (a sequence of ints or a 1-D integer tensor, one per row, each in ``[max(1, 2 - look_ahead), T]``): a
+        ragged batch - row b is an utterance of ``frames[b]`` STFT frames, ``mix_mag[b, :, :, frames[b]:]`` is never read.
+        Row b of the result is what ``forward(mix_mag[b:b + 1, :, :, :frames[b]])`` gives (within fp32 rounding), zero
+        from frame ``frames[b]`` on.  One pass through the glue's ragged entries where ``_forward_rows`` runs; row by row
+        (correct, not faster) elsewhere."""
         if mix_mag.dim() != 4 or mix_mag.shape[1] != 1:
             raise AssertionError(f"{self.__class__.__name__} takes a magnitude feature as the input ([B, 1, F, T]).")
+        if frames is not None:
+            from .ragged import check_frames
+            frames = check_frames(frames, mix_mag.shape[0], mix_mag.shape[3], self.look_ahead)  # before any launch
         if mix_mag.is_cuda and not torch.is_grad_enabled():
             # the model has no cross-utterance term: a batch well beyond ONE round of the bottleneck's persistent kernels
             # (4 row tiles per workgroup: 256 utterances x 64 bands on 256 CUs) runs as whole rounds plus a remainder -
             # 512 utterances 124 -> 2 x 51 ms (the block pairs' per-step launches and the multi-round launch cost more)
             chunk = torch.cuda.get_device_properties(mix_mag.device).multi_processor_count * 4 * 16 // self.num_mels
             if chunk >= 16 and mix_mag.shape[0] >= chunk + chunk // 2:
-                return torch.cat([self.forward(mix_mag[i:i + chunk]) for i in range(0, mix_mag.shape[0], chunk)], dim=0)
+                return torch.cat([self.forward(mix_mag[i:i + chunk], None if frames is None else frames[i:i + chunk])
+                                  for i in range(0, mix_mag.shape[0], chunk)], dim=0)
             if self._rows_path_ok(mix_mag):
-                return self._forward_rows(mix_mag)
+                return self._forward_rows(mix_mag, frames)
+        if frames is not None:
+            return self._forward_row_by_row(mix_mag, frames)
         if torch.is_grad_enabled():
             # the trainer's arithmetic (Model.train_arithmetic: "f16" under use_amp = true, train_shrinkSize2.toml:5) reaches
             # the bottleneck, 90 % of the step's products; the encoder / decoder blocks (72 rows) stay fp32
@@ -232,3 +280,49 @@ class Model(BaseModel):
         dec_in = torch.cat([enc, band_gain], dim=2).reshape(n_batch, -1, n_frames)
         mask = pair_forward(*self.decoder_lstm, dec_in).reshape(n_batch, 2, n_bins, n_frames)
         return mask[..., self.look_ahead:]
+
+    @torch.no_grad()
+    def enhance(self, noisy, n_fft=512, hop_length=256, return_crm=False, lengths=None):
+        """inferencer.py:130-145 for B independent utterances: noisy [B, L] -> enhanced [B, L] (and the compressed mask
+        [B, 2, F, 1 + L // hop] with ``return_crm``).
+
+        ``lengths`` (a sequence of ints or a 1-D integer tensor, one per row, each in ``(n_fft // 2, L]``): a ragged
+        batch - row b holds an utterance of ``lengths[b]`` samples, the rest of the row is never read.  Row b of the
+        result is what enhancing ``noisy[b, :lengths[b]]`` alone gives (within fp32 rounding), zero from ``lengths[b]``
+        on; its mask frames from ``1 + lengths[b] // hop`` on are zero.  At n_fft 512 / hop 256 on the device this is three
+        library stages and no ATen compute: ``fsn_stft`` / ``fsn_stft_ragged``, ``forward(mag, frames)`` and
+        ``fsn_mask_istft``.  Anything else runs stft -> forward -> the reference's tensor algebra, row by row with
+        ``lengths`` (correct, not faster)."""
+        from .acoustics.feature import istft, mask_istft, stft, stft_ragged
+        from .acoustics.mask import decompress_cIRM
+        from .ragged import check_lengths, frames as n_frames
+        assert noisy.dim() == 2
+        B, Ls = noisy.shape
+        lens = None if lengths is None else check_lengths(lengths, B, Ls, n_fft)  # before anything is launched
+        y = noisy.contiguous()
+        if y.is_cuda and y.dtype == torch.float32 and n_fft == 512 and hop_length == 256:
+            lens_dev = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=y.device)
+            if lens is None:
+                mag, _, re, im = stft(y, n_fft, hop_length, n_fft, return_phase=False)
+            else:
+                mag, re, im = stft_ragged(y, lens_dev, n_fft, hop_length, n_fft)
+            crm = self.forward(mag.unsqueeze(1), None if lens is None else [n_frames(n, hop_length) for n in lens])
+            out = mask_istft(crm, re, im, n_fft, hop_length, n_fft, Ls, lengths=lens_dev)
+            return (out, crm) if return_crm else out
+        if lens is None:
+            mag, _, re, im = stft(y, n_fft, hop_length, n_fft, return_phase=False)
+            crm = self.forward(mag.unsqueeze(1))
+            m = decompress_cIRM(crm.permute(0, 2, 3, 1))
+            out = istft((m[..., 0] * re - m[..., 1] * im, m[..., 1] * re + m[..., 0] * im), n_fft, hop_length, n_fft,
+                        length=Ls, input_type="real_imag")
+            return (out, crm) if return_crm else out
+        # no single-call form: each row alone, padded back into the batch's shape
+        T = n_frames(Ls, hop_length)
+        out = y.new_zeros((B, Ls), dtype=torch.float32)
+        crm = y.new_zeros((B, 2, n_fft // 2 + 1, T), dtype=torch.float32) if return_crm else None
+        for b, n in enumerate(lens):
+            e, c = self.enhance(y[b:b + 1, :n], n_fft=n_fft, hop_length=hop_length, return_crm=True)
+            out[b, :n] = e[0]
+            if return_crm:
+                crm[b, :, :, :c.shape[-1]] = c[0]
+        return (out, crm) if return_crm else out

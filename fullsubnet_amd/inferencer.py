@@ -111,10 +111,12 @@ class Inferencer:
         return trim_rows(self.enhance_batch(noisy, lengths=lengths), lengths)
 
     def _ragged_ok(self, items):
-        """Whether a group of loader items runs as one ragged call: 1-D utterances (one channel) on the model's fused
-        single call, long enough for the STFT's reflect padding."""
-        return (self.fused_call and getattr(self.model, "_fused", False) and self.n_fft == self.win_length == 512
-                and self.hop_length == 256
+        """Whether a group of loader items runs as one ragged call: 1-D utterances (one channel) on a model whose
+        ``ragged_enhance_ok`` says it enhances a ragged batch in one call at this transform (FullSubNet's fused
+        configurations, Fast FullSubNet's time-major path), long enough for the STFT's reflect padding."""
+        ragged_ok = getattr(self.model, "ragged_enhance_ok", None)
+        return (self.fused_call and ragged_ok is not None and ragged_ok(self.n_fft, self.hop_length)
+                and self.n_fft == self.win_length
                 and all(n.dim() == 2 and n.shape[0] == 1 and n.shape[1] > self.n_fft // 2 for n, _ in items))
 
     def __getattr__(self, name):

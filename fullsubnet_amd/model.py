@@ -302,13 +302,17 @@ class Model(nn.Module):
                                  ws.numel(), _lib.stream_ptr(y.device)))
         return (out, crm) if return_crm else out
 
+    def ragged_enhance_ok(self, n_fft, hop_length):
+        """Whether ``enhance(noisy, lengths=...)`` is ONE library call (``fsn_enhance_ragged``), not a row-by-row loop."""
+        return self._fused and n_fft == 512 and hop_length == 256
+
     def _enhance_ragged(self, noisy, lengths, n_fft, hop_length, return_crm):
         from .acoustics.feature import hann_window
         from .ragged import check_lengths, frames
         B, Ls = noisy.shape
         lens = check_lengths(lengths, B, Ls, n_fft)  # before anything is launched
         T = frames(Ls, hop_length)
-        if not (self._fused and n_fft == 512 and hop_length == 256):
+        if not self.ragged_enhance_ok(n_fft, hop_length):
             # no single-call form: each row alone through enhance, padded back into the batch's shape
             out = noisy.new_zeros((B, Ls), dtype=torch.float32)
             crm = noisy.new_zeros((B, 2, self.num_freqs, T), dtype=torch.float32) if return_crm else None

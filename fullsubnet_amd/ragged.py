@@ -9,33 +9,52 @@ import numpy as np
 import torch
 
 
+def _integers(values, what):
+    """A sequence of integers or a 1-D integer tensor / array -> a list of Python ints; ValueError naming ``what``."""
+    if isinstance(values, (torch.Tensor, np.ndarray)):
+        if values.ndim != 1:
+            raise ValueError(f"{what} must be 1-D, got shape {tuple(values.shape)}")
+        is_int = (not values.dtype.is_floating_point and not values.dtype.is_complex and values.dtype != torch.bool
+                  if isinstance(values, torch.Tensor) else np.issubdtype(values.dtype, np.integer))
+        if not is_int:
+            raise ValueError(f"{what} must hold integers, got dtype {values.dtype}")
+        return [int(v) for v in values.tolist()]
+    try:
+        out = list(values)
+    except TypeError:
+        raise ValueError(f"{what} must be a sequence of integers, got {type(values).__name__}") from None
+    for v in out:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Integral):
+            raise ValueError(f"{what} must hold integers, got {v!r}")
+    return [int(v) for v in out]
+
+
 def check_lengths(lengths, batch, max_length, n_fft=512):
     """Validated per-row sample counts as a list of Python ints.  ``lengths`` is a sequence of integers or a 1-D integer
     tensor / array with one entry per row; every value must lie in ``(n_fft // 2, max_length]`` (the STFT reflects up
     to ``n_fft // 2`` samples at both ends of an utterance).  Raises ``ValueError`` otherwise."""
-    if isinstance(lengths, (torch.Tensor, np.ndarray)):
-        if lengths.ndim != 1:
-            raise ValueError(f"lengths must be 1-D, got shape {tuple(lengths.shape)}")
-        is_int = (not lengths.dtype.is_floating_point and not lengths.dtype.is_complex and lengths.dtype != torch.bool
-                  if isinstance(lengths, torch.Tensor) else np.issubdtype(lengths.dtype, np.integer))
-        if not is_int:
-            raise ValueError(f"lengths must hold integers, got dtype {lengths.dtype}")
-        values = [int(v) for v in lengths.tolist()]
-    else:
-        try:
-            values = list(lengths)
-        except TypeError:
-            raise ValueError(f"lengths must be a sequence of integers, got {type(lengths).__name__}") from None
-        for v in values:
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Integral):
-                raise ValueError(f"lengths must hold integers, got {v!r}")
-        values = [int(v) for v in values]
+    values = _integers(lengths, "lengths")
     if len(values) != batch:
         raise ValueError(f"{len(values)} lengths for a batch of {batch} rows")
     lo = n_fft // 2
     for b, v in enumerate(values):
         if not lo < v <= max_length:
             raise ValueError(f"lengths[{b}] = {v} is outside ({lo}, {max_length}]")
+    return values
+
+
+def check_frames(frames, batch, max_frames, look_ahead=0):
+    """Validated per-row STFT frame counts of a ragged magnitude batch ``[B, 1, F, T0]`` (Fast FullSubNet's
+    ``forward(mix_mag, frames=...)``), as a list of Python ints.  Same forms as ``check_lengths``; every value must lie
+    in ``[max(1, 2 - look_ahead), max_frames]`` (the model's down-sampling needs two frames with the look-ahead).
+    Raises ``ValueError`` otherwise."""
+    values = _integers(frames, "frames")
+    if len(values) != batch:
+        raise ValueError(f"{len(values)} frames for a batch of {batch} rows")
+    lo = max(1, 2 - look_ahead)
+    for b, v in enumerate(values):
+        if not lo <= v <= max_frames:
+            raise ValueError(f"frames[{b}] = {v} is outside [{lo}, {max_frames}]")
     return values
 
 

@@ -82,6 +82,26 @@ int fsn_istft(const float* real, const float* imag, int B, int T, int n_fft, int
               const float* window, int length, float* y, void* workspace, size_t workspace_bytes,
               void* stream);
 
+/* fsn_stft on a RAGGED batch: row b of y [B][L_max] holds lengths[b] samples (lengths: device memory, [B]; values are
+ * clamped to [n_fft/2 + 1, L_max]); the rest of the row is never read.  real/imag/mag [B, F, T_max], T_max = 1 + L_max / hop
+ * (any of the three may be NULL): row b is the STFT of y[b][0 .. lengths[b]) alone - reflected at its own end - in its
+ * first T_b = 1 + lengths[b] / hop frames, zeros after them.  n_fft = win_length = 512 / hop = 256 only; any other shape
+ * is an error (fsn_last_error). */
+int fsn_stft_ragged(const float* y, const int* lengths, int B, int L_max, int n_fft, int hop, int win_length,
+                    const float* window, float* real, float* imag, float* mag, void* stream);
+
+/* inferencer.py:134-141 as one call on a model's COMPRESSED cIRM: decompress_cIRM (K = 10, limit = 9.9), the complex
+ * mask on the noisy spectrum and the iSTFT, with the fp32 products of the reference's tensor algebra.
+ * crm [B, 2, F, T] as a model's forward returns it (read in place); real/imag [B, F, T] as fsn_stft writes them;
+ * y [B, length].  lengths (device, [B], may be NULL = a rectangular batch): row b is the iSTFT of its own
+ * T_b = 1 + lengths[b] / hop frames at its own length (as fsn_enhance_ragged), zeros from lengths[b] on; frames t >= T_b
+ * of crm / real / imag are never read; then length must be the longest row (T = 1 + length / hop).
+ * n_fft = win_length = 512 / hop = 256 only.  workspace >= fsn_mask_istft_workspace_bytes(B, T, n_fft) (0: unsupported). */
+size_t fsn_mask_istft_workspace_bytes(int B, int T, int n_fft);
+int fsn_mask_istft(const float* crm, const float* real, const float* imag, const int* lengths, int B, int F, int T, int n_fft,
+                   int hop, int win_length, const float* window, int length, float* y, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
 /* ---- cIRM mask algebra : audio_zen/acoustics/mask.py ----------------------------------- */
 
 /* mask.py:47-64  decompress_cIRM(mask, K=10, limit=9.9), elementwise over n floats. */
@@ -520,6 +540,29 @@ int fsn_fast_bottleneck_input(const float* mel, const float* enc, long ld_enc, i
 int fsn_fast_decoder_input(const float* enc, long ld_enc, const float* slow, long ld_slow_frame, long ld_slow_row, int relu, int T,
                            int B, int Bp, int num_mels, int shrink, float* out, void* stream);
 int fsn_fast_mask_out(const float* o, long ld, int T, int B, int Bp, int F, int look_ahead, float* mask, void* stream);
+
+/* The same four glue steps on a RAGGED batch (Model.forward(mix_mag, frames=...)): frames (device, [B], not NULL) holds
+ * utterance b's STFT frame count T_b before the look-ahead (clamped to [1, T0], T0 = T - look_ahead); row b then behaves as
+ * a batch of one utterance of T_b frames - its own look_ahead zero frames, its own norms and down-sampling blocks.  The LSTM
+ * blocks between them are causal and run every row to T: a row's first T_b + look_ahead steps never see the padded ones.
+ * fsn_fast_spec_rows_ragged        mag frames t >= T_b are never read; their rows are written as zeros.
+ * fsn_fast_norm_rows_ragged        the mean covers the row's own (T_b + look_ahead) x C values.
+ * fsn_fast_bottleneck_input_ragged row b has Ts_b = fsn_fast_low_rate_frames(T_b + look_ahead, shrink) low-rate frames: the
+ *                                  last down-sampling block ends at T_b + look_ahead (averaged on its own, short or whole),
+ *                                  the mean divides by num_mels W Ts_b, and units of frames ts >= Ts_b are zeros.
+ * fsn_fast_mask_out_ragged         mask frames t >= T_b of row b are zeros.
+ * (fsn_fast_decoder_input needs no lengths: frame t < T_b + look_ahead takes low-rate frame t / shrink < Ts_b.)
+ * Arguments, checks and workspace (fsn_fast_glue_workspace_bytes) as the plain entries, which are these with frames = NULL;
+ * every frames[b] = T0 gives their result bit for bit. */
+int fsn_fast_spec_rows_ragged(const float* mag, const int* frames, int B, int F, int T0, int look_ahead, float* rows, int Bp, int Fp,
+                              void* stream);
+int fsn_fast_norm_rows_ragged(const float* x, const int* frames, int look_ahead, int T, int B, int Bp, int C, float* out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int fsn_fast_bottleneck_input_ragged(const float* mel, const float* enc, long ld_enc, const int* frames, int look_ahead, int T, int B,
+                                     int Bp, int num_mels, int mel_neighbors, int enc_neighbors, int shrink, float* out, int Np,
+                                     int Wp, void* workspace, size_t workspace_bytes, void* stream);
+int fsn_fast_mask_out_ragged(const float* o, long ld, const int* frames, int T, int B, int Bp, int F, int look_ahead, float* mask,
+                             void* stream);
 
 /* fullsubnet/trainer.py:65-69: torch.nn.utils.clip_grad_norm_(parameters, max_norm) followed by
  * torch.optim.Adam.step() (train.py:55-59: lr, betas, eps 1e-8, no weight decay / amsgrad), fused into
