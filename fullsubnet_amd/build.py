@@ -11,17 +11,20 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libfsn_hip.so")
-HEADERS = [os.path.join(CSRC, "fsn_common.h"), os.path.join(HERE, "..", "include", "fsn_hip.h")]
+HEADERS = [os.path.join(CSRC, "fsn_common.h"), os.path.join(CSRC, "fsn_api_internal.h"),
+           os.path.join(HERE, "..", "include", "fsn_hip.h")]
+EXPORTS = os.path.join(CSRC, "fsn_exports.map")  # the library exports the fsn_* entries of fsn_hip.h and nothing else
 SOURCES = ["fft_kernels.hip", "dft_kernels.hip", "elementwise_kernels.hip", "gemm_kernels.hip",
            "gemm_f16x3_kernels.hip", "lstm_kernels.hip", "lstm_group_kernels.hip",
            "lstm_group_bptt_kernels.hip", "lstm_group16_kernels.hip", "fb_chain_kernels.hip", "fb_chain_bptt_kernels.hip",
            "lstm_f16x3_kernels.hip", "lstm_train_kernels.hip", "gru_kernels.hip", "optim_kernels.hip",
            "norm_kernels.hip", "section_kernels.hip", "train_glue_kernels.hip", "fast_glue_kernels.hip",
-           "fsn_api.hip"]
+           "fsn_api.hip", "fsn_api_fullsubnet.hip", "fsn_api_layers.hip", "fsn_api_gru.hip", "fsn_api_train.hip"]
 # -ffp-contract=off: elementwise code follows the reference's mul/add rounding sequence; fused
 # multiply-adds are written explicitly (fma / MFMA) where they are wanted.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-pass-failed",
          "-Wno-unused-value"]
+LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + EXPORTS]
 
 
 def _sources():
@@ -44,7 +47,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in _sources()] + HEADERS
+    deps = [os.path.join(CSRC, f) for f in _sources()] + HEADERS + [EXPORTS]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -63,7 +66,7 @@ def build(force=False, verbose=True):
 
     with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(len(todo), os.cpu_count() or 1))) as pool:
         list(pool.map(compile_one, todo))
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + [_obj(s) for s in _sources()] + ["-o", LIB]
+    cmd = [hipcc] + LINK_FLAGS + [_obj(s) for s in _sources()] + ["-o", LIB]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)

@@ -1,0 +1,1312 @@
+// C ABI of libfsn_hip.so, the FullSubNet model (fullsubnet/model.py): weight packing, the model core and its batch
+// chunking, the full-band / row-range / streaming forms, the STFT / iSTFT and elementwise boundary and the whole
+// enhancement path (fsn_enhance, fsn_enhance_ragged).
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "fsn_api_internal.h"
+
+static int check_cfg(const fsn_fullsubnet_cfg* cfg) {
+    FSN_REQUIRE(cfg != nullptr, "cfg is NULL");
+    FSN_REQUIRE(cfg->num_freqs >= 17 && cfg->num_freqs <= 4096, "num_freqs %d out of range", cfg->num_freqs);
+    FSN_REQUIRE(cfg->look_ahead >= 0, "look_ahead %d < 0", cfg->look_ahead);
+    FSN_REQUIRE(cfg->sb_num_neighbors >= 0 && cfg->sb_num_neighbors < cfg->num_freqs,
+                "sb_num_neighbors %d must be in [0, num_freqs) (reflect padding)", cfg->sb_num_neighbors);
+    FSN_REQUIRE(cfg->fb_hidden > 0 && cfg->fb_hidden % 64 == 0, "fb_hidden %d must be a multiple of 64",
+                cfg->fb_hidden);
+    FSN_REQUIRE(cfg->sb_hidden == 384, "sb_hidden %d unsupported (the sub-band recurrent kernel is built for 384)",
+                cfg->sb_hidden);
+    FSN_REQUIRE(cfg->norm_type == FSN_NORM_OFFLINE_LAPLACE || cfg->norm_type == FSN_NORM_CUMULATIVE_LAPLACE,
+                "norm_type %d unsupported", cfg->norm_type);
+    FSN_REQUIRE(cfg->arith == FSN_ARITH_F32 || cfg->arith == FSN_ARITH_F16X3, "arith %d unsupported", cfg->arith);
+    return FSN_OK;
+}
+
+// ---- packed weights --------------------------------------------------------------------------
+struct Packed {  // float offsets into the packed blob
+    size_t fb_wih0, fb_whh0, fb_b0, fb_wih1, fb_whh1, fb_b1, fb_fc, fb_fcb;
+    size_t sb_wih0, sb_whh0, sb_b0, sb_wih1, sb_whh1, sb_b1, sb_fc, sb_fcb;
+    size_t fb_b1_frag, sb_b1_frag;  // layer-1 biases as accumulator-fragment tiles (wavefront step kernel)
+    size_t sb_wih1_f16x3;           // experimental: sub-band W_ih of layer 1 split into fp16 halves (FSN_F16X3=1)
+    size_t sb_whh1_f16x3;           // experimental: likewise W_hh of layer 1
+    size_t sb_wih0_f16x3;           // experimental: W_ih of layer 0 (only when its padded width is 32), scale 4096
+    size_t sb_whh0_f16x3;           // experimental: W_hh of layer 0
+    size_t total;
+    int FP, sb_kin_pad;
+};
+static Packed packed_layout(const fsn_fullsubnet_cfg* c) {
+    Packed p;
+    size_t o = 0;
+    auto take = [&](size_t n) {
+        o = fsn_round_up_sz(o, 64);
+        const size_t r = o;
+        o += n;
+        return r;
+    };
+    const size_t Hf = c->fb_hidden, Hs = c->sb_hidden;
+    p.FP = fsn_fpad(c->num_freqs);
+    p.sb_kin_pad = fsn_round_up(2 * c->sb_num_neighbors + 2, 16);
+    p.fb_wih0 = take(4 * Hf * p.FP);
+    p.fb_whh0 = take(4 * Hf * Hf);
+    p.fb_b0 = take(4 * Hf);
+    p.fb_wih1 = take(4 * Hf * Hf);
+    p.fb_whh1 = take(4 * Hf * Hf);
+    p.fb_b1 = take(4 * Hf);
+    p.fb_fc = take((size_t)p.FP * Hf);
+    p.fb_fcb = take(p.FP);
+    p.sb_wih0 = take(4 * Hs * p.sb_kin_pad);
+    p.sb_whh0 = take(4 * Hs * Hs);
+    p.sb_b0 = take(4 * Hs);
+    p.sb_wih1 = take(4 * Hs * Hs);
+    p.sb_whh1 = take(4 * Hs * Hs);
+    p.sb_b1 = take(4 * Hs);
+    p.sb_fc = take(16 * Hs);
+    p.sb_fcb = take(16);
+    p.fb_b1_frag = take(4 * Hf * 16);  // [4H/16 column tiles][64 lanes][4]
+    p.sb_b1_frag = take(4 * Hs * 16);
+    p.sb_wih1_f16x3 = take((fsn_f16x3_packed_halves(4 * (int)Hs, (int)Hs) + 1) / 2);  // halves -> floats
+    p.sb_whh1_f16x3 = take((fsn_f16x3_packed_halves(4 * (int)Hs, (int)Hs) + 1) / 2);
+    p.sb_wih0_f16x3 = take((fsn_f16x3_packed_halves(4 * (int)Hs, 32) + 1) / 2);
+    p.sb_whh0_f16x3 = take((fsn_f16x3_packed_halves(4 * (int)Hs, (int)Hs) + 1) / 2);
+    p.total = fsn_round_up_sz(o, 64);
+    return p;
+}
+
+extern "C" size_t fsn_fullsubnet_packed_bytes(const fsn_fullsubnet_cfg* cfg) {
+    if (check_cfg(cfg) != FSN_OK) return 0;
+    return packed_layout(cfg).total * sizeof(float);
+}
+
+extern "C" int fsn_fullsubnet_pack(const fsn_fullsubnet_cfg* cfg, const fsn_fullsubnet_params* w, void* packed,
+                                   size_t packed_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_cfg(cfg));
+    FSN_REQUIRE(w && packed, "params / packed is NULL");
+    const float* const* all = reinterpret_cast<const float* const*>(w);
+    for (size_t i = 0; i < sizeof(*w) / sizeof(float*); ++i) FSN_REQUIRE(all[i], "params tensor %zu is NULL", i);
+    const Packed p = packed_layout(cfg);
+    FSN_REQUIRE(packed_bytes >= p.total * sizeof(float), "packed buffer too small: %zu < %zu", packed_bytes,
+                p.total * sizeof(float));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* o = static_cast<float*>(packed);
+    const int F = cfg->num_freqs, Hf = cfg->fb_hidden, Hs = cfg->sb_hidden;
+    const int kin = 2 * cfg->sb_num_neighbors + 2;
+    FSN_TRY(fsn_launch_pack(w->fb_w_ih_l0, o + p.fb_wih0, 4 * Hf, F, 4 * Hf, p.FP, s));
+    FSN_TRY(fsn_launch_pack(w->fb_w_hh_l0, o + p.fb_whh0, 4 * Hf, Hf, 4 * Hf, Hf, s));
+    FSN_TRY(fsn_launch_bias_sum(w->fb_b_ih_l0, w->fb_b_hh_l0, o + p.fb_b0, 4 * Hf, 4 * Hf, s));
+    FSN_TRY(fsn_launch_pack(w->fb_w_ih_l1, o + p.fb_wih1, 4 * Hf, Hf, 4 * Hf, Hf, s));
+    FSN_TRY(fsn_launch_pack(w->fb_w_hh_l1, o + p.fb_whh1, 4 * Hf, Hf, 4 * Hf, Hf, s));
+    FSN_TRY(fsn_launch_bias_sum(w->fb_b_ih_l1, w->fb_b_hh_l1, o + p.fb_b1, 4 * Hf, 4 * Hf, s));
+    FSN_TRY(fsn_launch_pack(w->fb_fc_w, o + p.fb_fc, F, Hf, p.FP, Hf, s));
+    FSN_TRY(fsn_launch_bias_sum(w->fb_fc_b, nullptr, o + p.fb_fcb, F, p.FP, s));
+    FSN_TRY(fsn_launch_pack(w->sb_w_ih_l0, o + p.sb_wih0, 4 * Hs, kin, 4 * Hs, p.sb_kin_pad, s));
+    FSN_TRY(fsn_launch_pack(w->sb_w_hh_l0, o + p.sb_whh0, 4 * Hs, Hs, 4 * Hs, Hs, s));
+    FSN_TRY(fsn_launch_bias_sum(w->sb_b_ih_l0, w->sb_b_hh_l0, o + p.sb_b0, 4 * Hs, 4 * Hs, s));
+    FSN_TRY(fsn_launch_pack(w->sb_w_ih_l1, o + p.sb_wih1, 4 * Hs, Hs, 4 * Hs, Hs, s));
+    FSN_TRY(fsn_launch_pack(w->sb_w_hh_l1, o + p.sb_whh1, 4 * Hs, Hs, 4 * Hs, Hs, s));
+    FSN_TRY(fsn_launch_bias_sum(w->sb_b_ih_l1, w->sb_b_hh_l1, o + p.sb_b1, 4 * Hs, 4 * Hs, s));
+    FSN_TRY(fsn_launch_pack(w->sb_fc_w, o + p.sb_fc, 2, Hs, 16, Hs, s));
+    FSN_TRY(fsn_launch_bias_sum(w->sb_fc_b, nullptr, o + p.sb_fcb, 2, 16, s));
+    FSN_TRY(fsn_launch_bias_frag(o + p.fb_b1, o + p.fb_b1_frag, 4 * Hf, s));
+    FSN_TRY(fsn_launch_bias_frag(o + p.sb_b1, o + p.sb_b1_frag, 4 * Hs, s));
+    if (Hs % 32 == 0) {
+        FSN_TRY(fsn_launch_pack_f16x3(w->sb_w_ih_l1, o + p.sb_wih1_f16x3, 4 * Hs, Hs, s));
+        FSN_TRY(fsn_launch_pack_f16x3(w->sb_w_hh_l1, o + p.sb_whh1_f16x3, 4 * Hs, Hs, s));
+        FSN_TRY(fsn_launch_pack_f16x3(w->sb_w_hh_l0, o + p.sb_whh0_f16x3, 4 * Hs, Hs, s));
+        if (kin == 32)
+            FSN_TRY(fsn_launch_pack_f16x3(w->sb_w_ih_l0, o + p.sb_wih0_f16x3, 4 * Hs, 32, s, fsn_f16x3_wih0_scale()));
+    }
+    return FSN_OK;
+}
+
+constexpr int kGroupTwoFromTiles = 224;  // 56+ clusters: two per workgroup set
+constexpr int kGroupMaxTiles = 264;      // 64 clusters + up to 8 left-over tiles
+
+// ---- model core: magT [B][Tp][FP] -> crm_r, crm_i [B][T][FP] ------------------------------------
+struct CoreDims {
+    int B, T, Tp, F, FP, Hf, Hs, nb, la;
+    int Npad_fb;       // full-band rows per step (batch, padded to 16)
+    bool fb_chain;     // the full-band LSTM layers run as one persistent launch (fb_chain_kernels.hip)
+    int N, Npad;       // sub-band rows per step, padded rows (row stride of the [t][n] buffers)
+    FsnRecPlan rec;    // how those rows are spread over the CUs
+    bool fc_fused;     // output layer fused into the layer-1 persistent kernel (its hseq is never stored)
+    bool l1x;          // layer 1 forms its input projection itself (lstm_rec_x_kernel): no projection GEMM, no gx
+    int grp_clusters;  // > 0: the step regime runs on the group kernel (lstm_group_kernels.hip), that many clusters of 64 rows
+    long row0;         // row-range calls: the N sub-band rows are rows row0 .. row0 + N - 1 of the B F rows
+    int den_stride;    // row stride of the per-row (cumulative) sub-band divisors: they are indexed by GLOBAL row
+};
+// n_rows < 0: all B F sub-band rows; otherwise the rows [row0, row0 + n_rows) of the flattened (b, f) index space
+// (the full-band model and the norm statistics always cover the B whole utterances).
+static CoreDims core_dims(const fsn_fullsubnet_cfg* c, int B, int T, long row0 = 0, long n_rows = -1) {
+    CoreDims d;
+    d.B = B;
+    d.T = T;
+    d.la = c->look_ahead;
+    d.Tp = T + c->look_ahead;
+    d.F = c->num_freqs;
+    d.FP = fsn_fpad(d.F);
+    d.Hf = c->fb_hidden;
+    d.Hs = c->sb_hidden;
+    d.nb = c->sb_num_neighbors;
+    d.Npad_fb = fsn_round_up(B, 16);
+    d.fb_chain = fsn_fb_chain_supported(d.Hf, d.Npad_fb) && d.Tp <= fsn_fb_chain_max_steps();
+    d.N = n_rows < 0 ? B * d.F : (int)n_rows;
+    d.row0 = n_rows < 0 ? 0 : row0;
+    d.rec = fsn_lstm_rec_plan(d.N, d.Hs);
+    // 224 - 264 row tiles (14 - 16 utterances: one rank's share of config 2 at 4 GPUs) run on the group kernel with two
+    // clusters per workgroup set (lstm_group_kernels.hip) instead of the persistent kernels at ONE row tile per CU
+    // (every CU streams all weights every step there): 26.5 -> 23.4 ms at 16 utterances
+    const bool grp_shape = d.Hs == 384 && fsn_round_up(2 * c->sb_num_neighbors + 2, 16) == 32 && c->arith == FSN_ARITH_F32;
+    if (grp_shape && d.rec.tiles >= kGroupTwoFromTiles && d.rec.tiles <= kGroupMaxTiles && d.rec.main_wgs > 0 &&
+        4 * fsn_lstm2_group_clusters(d.rec.tiles) + 8 >= d.rec.tiles) {  // ... and the device holds (nearly) all of them
+        d.rec.rt = 1;
+        d.rec.main_wgs = 0;
+        d.rec.left_tiles = d.rec.tiles;
+    }
+    d.Npad = d.rec.npad;
+    d.den_stride = n_rows < 0 ? d.Npad : fsn_round_up(B * d.F, 16);
+    d.fc_fused = d.rec.main_wgs > 0 && fsn_lstm_rec_can_fuse_fc(d.rec.rt, false);
+    d.l1x = d.fc_fused && c->arith == FSN_ARITH_F32 && fsn_lstm_rec_x_supported(d.Hs, d.rec.rt);
+    // 96 - 159 row tiles (6 - 9 utterances; below that the two-layer wavefront of per-step launches is as fast)
+    d.grp_clusters = 0;
+    if (d.rec.main_wgs == 0 && d.rec.left_tiles >= kWavefrontBelowTiles && grp_shape)  // fp32 only: the group kernel has no f16x3 form
+        d.grp_clusters = fsn_lstm2_group_clusters(d.rec.left_tiles);
+    return d;
+}
+struct CoreWs {
+    float *gx_fb, *hseq_fb0, *hseq_fb1, *c_fb, *fb_out, *den_fb, *den_sb, *gx_sb, *hseq_sb0, *hseq_sb1, *c_left;
+    float* hseq_left0;  // l1x: layer-0 hidden sequence of the left-over rows, compact [t][left rows][H]
+    float* grp_exchange;  // group kernel: h exchange buffers of the clusters
+    unsigned* grp_flags;
+    float* fb_exchange;   // full-band chain kernel: per-step h / projection hand-off buffers
+    unsigned* fb_flags;
+    double* binsum;
+};
+static CoreWs core_carve(Carver& cv, const CoreDims& d, int norm_type) {
+    CoreWs w;
+    const size_t rows_fb = (size_t)d.Tp * d.Npad_fb, rows_sb = (size_t)d.Tp * d.Npad;
+    w.gx_fb = cv.take<float>(rows_fb * 4 * d.Hf);
+    w.hseq_fb0 = cv.take<float>(rows_fb * d.Hf);
+    w.hseq_fb1 = cv.take<float>(rows_fb * d.Hf);
+    w.c_fb = cv.take<float>((size_t)2 * d.Npad_fb * d.Hf);  // one cell state per layer (wavefront)
+    w.fb_out = cv.take<float>((size_t)d.B * d.Tp * d.FP);
+    w.binsum = cv.take<double>((size_t)d.B * d.FP);
+    const bool cum = norm_type == FSN_NORM_CUMULATIVE_LAPLACE;
+    w.den_fb = cv.take<float>(cum ? (size_t)d.B * d.Tp : (size_t)d.B);
+    w.den_sb = cv.take<float>(cum ? (size_t)d.Tp * d.den_stride : (size_t)d.B);
+    // l1x: only the left-over rows (which run step by step) still need a precomputed projection
+    const size_t rows_left = (size_t)d.Tp * (d.rec.left_tiles > 0 ? d.rec.left_tiles : 1) * 16;
+    if (d.grp_clusters > 0) {
+        // group kernel: projections and hidden sequences only exist for the rows that do not fill a cluster
+        const int aux_tiles = d.rec.tiles - 4 * d.grp_clusters;
+        const size_t rows_aux = (size_t)d.Tp * (aux_tiles > 0 ? aux_tiles : 1) * 16;
+        w.gx_sb = cv.take<float>(rows_aux * 4 * d.Hs);
+        w.hseq_sb0 = cv.take<float>(rows_aux * d.Hs);
+        w.hseq_left0 = nullptr;
+        w.hseq_sb1 = cv.take<float>(rows_aux * d.Hs);
+    } else {
+        w.gx_sb = cv.take<float>((d.l1x ? rows_left : rows_sb) * 4 * d.Hs);
+        w.hseq_sb0 = cv.take<float>(rows_sb * d.Hs);
+        w.hseq_left0 = d.l1x ? cv.take<float>(rows_left * d.Hs) : nullptr;
+        // fused output layer: only the left-over rows of layer 1 are ever stored, [t][left rows][H]
+        w.hseq_sb1 = cv.take<float>(d.fc_fused ? (size_t)d.Tp * (d.rec.left_tiles > 0 ? d.rec.left_tiles : 1) * 16 * d.Hs
+                                               : rows_sb * d.Hs);
+    }
+    w.c_left = cv.take<float>((size_t)2 * (d.rec.left_tiles > 0 ? d.rec.left_tiles : 1) * 16 * d.Hs);
+    w.grp_exchange = d.grp_clusters ? cv.take<float>(fsn_lstm2_group_exchange_floats(d.grp_clusters)) : nullptr;
+    w.grp_flags = d.grp_clusters ? cv.take<unsigned>(fsn_lstm2_group_flag_words(d.grp_clusters)) : nullptr;
+    w.fb_exchange = d.fb_chain ? cv.take<float>(fsn_fb_chain_exchange_floats(d.Tp, d.Npad_fb)) : nullptr;
+    w.fb_flags = d.fb_chain ? cv.take<unsigned>(fsn_fb_chain_flag_words()) : nullptr;
+    return w;
+}
+
+// One sub-band LSTM layer over all Tp steps: the persistent kernel on `s` and, concurrently, the
+// few left-over row tiles as per-step launches on the auxiliary stream.
+// Main kernel: input projection either precomputed (`gx`, tile (t, i) at t * tiles + i) or built
+// in-kernel from `xin`.  Left-over tiles: projection tiles in `gx_left` at t * left_stride + left_off + i.
+// x_main (with wih_main, bias_main): the main rows run on lstm_rec_x_kernel, which reads the hidden sequence of the
+// layer below (x_main [Tp][Npad][H]) and forms its input projection itself.  hseq_left: the left-over rows' hidden
+// sequence goes to this compact [t][left rows][H] buffer instead of rows [main rows, Npad) of hseq.
+int run_recurrence(const float* gx, const FsnSbInput* xin, const float* gx_left, long left_stride, long left_off,
+                   const float* whh, float* hseq, float* c_left, int Tp, int Npad, int H, const FsnRecPlan& r, hipStream_t s,
+                   const FsnRecFc* fc, long left_hs_stride, const void* whh_f16x3, const void* wih_f16x3,
+                   const float* x_main, const float* wih_main, const float* bias_main, float* hseq_left) {
+    // No persistent part (fewer than ~160 tiles): the steps run on `s` itself - groups of four tiles through the
+    // one-workgroup-per-CU step kernel, the up to three tiles that do not fill a group beside it on the
+    // auxiliary stream (a 33rd group of 8 workgroups would be a second round on 8 CUs and double the step).
+    const int cu_tiles = r.main_wgs == 0 && r.left_tiles >= 8 ? r.left_tiles / 4 * 4 : 0;
+    const int aux_tiles = r.left_tiles - cu_tiles;
+    const bool fork = aux_tiles > 0 && (r.main_wgs > 0 || cu_tiles > 0);
+    hipStream_t ls = s;
+    StreamCtx* cx = nullptr;
+    if (fork) {
+        cx = cur_ctx();
+        FSN_TRY(aux_init(cx));
+        if (hipEventRecord(cx->ev_fork, s) != hipSuccess || hipStreamWaitEvent(cx->aux, cx->ev_fork, 0) != hipSuccess) {
+            fsn_set_error("aux stream fork failed");
+            return FSN_ERR_LAUNCH;
+        }
+        ls = cx->aux;
+    }
+    if (r.main_wgs > 0) {
+        if (x_main)
+            FSN_TRY(fsn_launch_lstm_rec_x(x_main, wih_main, whh, bias_main, Tp, Npad, H, r.rt, r.main_wgs, s, fc,
+                                          fc ? nullptr : hseq));  // no output layer: a layer inside a stack, h_t stored
+        else if (xin && !fc && !whh_f16x3 && fsn_lstm_rec_in_supported(xin, whh, H, r.rt))
+            FSN_TRY(fsn_launch_lstm_rec_in(xin, whh, hseq, Tp, Npad, H, r.rt, r.main_wgs, s));
+        else if (whh_f16x3 && fc && !xin && r.rt >= 2)  // experimental split-precision persistent kernel (FSN_F16X3=1)
+            FSN_TRY(fsn_launch_lstm_rec_f16x3(gx, whh_f16x3, Tp, Npad, H, r.rt, r.main_wgs, fc, s));
+        else if (whh_f16x3 && wih_f16x3 && xin && !xin->x_rows && xin->kin_chunks == 2 && r.rt >= 2)
+            FSN_TRY(fsn_launch_lstm_rec_xin_f16x3(xin, wih_f16x3, whh_f16x3, hseq, Tp, Npad, H, r.rt, r.main_wgs, s));
+        else
+            FSN_TRY(fsn_launch_lstm_rec(gx, xin, whh, hseq, Tp, Npad, H, r.rt, r.main_wgs, s, fc));
+    }
+    if (r.left_tiles > 0) {
+        // left-over rows of step t: rows [main_rows, Npad) of the full [t][Npad] matrix, or - when the
+        // persistent part stores nothing (fused output layer) - a compact [t][left rows] matrix
+        if (hseq_left) left_hs_stride = (long)r.left_tiles * 16;
+        float* hl = hseq_left ? hseq_left : hseq;
+        const long hs_stride = left_hs_stride >= 0 ? left_hs_stride : Npad;
+        const long hs_off = left_hs_stride >= 0 ? 0 : (long)r.main_wgs * r.rt * 16;
+        for (int t = 0; t < Tp; ++t) {
+            float* h_out = hl + ((size_t)t * hs_stride + hs_off) * H;
+            const float* h_prev = t ? hl + ((size_t)(t - 1) * hs_stride + hs_off) * H : h_out;
+            const long gx_rt0 = (long)t * left_stride + left_off;
+            if (cu_tiles > 0)
+                FSN_TRY(fsn_launch_lstm_step_cu(gx_left, whh, h_prev, h_out, c_left, gx_rt0, cu_tiles, H, t == 0, s));
+            if (aux_tiles > 0) {
+                const size_t ro = (size_t)cu_tiles * 16 * H;
+                FSN_TRY(fsn_launch_lstm_step(gx_left, whh, h_prev + ro, h_out + ro, c_left + ro, gx_rt0 + cu_tiles,
+                                             aux_tiles, H, t == 0, ls, fork ? 1 : 0));
+            }
+        }
+    }
+    if (fork) {
+        if (hipEventRecord(cx->ev_join, cx->aux) != hipSuccess || hipStreamWaitEvent(s, cx->ev_join, 0) != hipSuccess) {
+            fsn_set_error("aux stream join failed");
+            return FSN_ERR_LAUNCH;
+        }
+    }
+    return FSN_OK;
+}
+
+static int run_sb_recurrence(const float* gx, const FsnSbInput* xin, const float* gx_left, long left_stride,
+                             long left_off, const float* whh, float* hseq, float* c_left, const CoreDims& d,
+                             hipStream_t s, const FsnRecFc* fc = nullptr, const void* whh_f16x3 = nullptr,
+                             const void* wih_f16x3 = nullptr, const float* x_main = nullptr,
+                             const float* wih_main = nullptr, const float* bias_main = nullptr,
+                             float* hseq_left = nullptr) {
+    return run_recurrence(gx, xin, gx_left, left_stride, left_off, whh, hseq, c_left, d.Tp, d.Npad, d.Hs, d.rec, s,
+                          fc, fc ? (long)d.rec.left_tiles * 16 : -1, whh_f16x3, wih_f16x3, x_main, wih_main,
+                          bias_main, hseq_left);
+}
+
+// lengths (device, [d.B], may be NULL): a ragged batch (fsn_enhance_ragged) - only the offline norm's divisors depend on
+// an utterance's length (magT is zero past its frames); the cumulative norm and the models are causal and run to d.Tp.
+static int run_core(const fsn_fullsubnet_cfg* cfg, const float* pk, const float* magT, const CoreDims& d,
+                    const CoreWs& w, float* crm_r, float* crm_i, hipStream_t s, bool fullband_only = false,
+                    const int* lengths = nullptr) {
+    const Packed p = packed_layout(cfg);
+    const bool cum = cfg->norm_type == FSN_NORM_CUMULATIVE_LAPLACE;
+
+    // full-band norm divisor (fullsubnet/model.py:92)
+    {
+        StageTimer st(ST_NORM, s);
+        if (cum) {
+            FSN_TRY(fsn_launch_cumulative_den_fb(magT, w.den_fb, d.B, d.Tp, d.F, d.FP, s));
+        } else {
+            FSN_TRY(fsn_launch_binsum(magT, w.binsum, d.B, d.Tp, d.FP, s));
+            FSN_TRY(fsn_launch_offline_den(w.binsum, nullptr, w.den_fb, nullptr, d.B, d.Tp, d.F, d.FP, d.nb, 0, s,
+                                           lengths, d.T));
+        }
+    }
+    // full-band model (model.py:95): 2 LSTM layers + Linear + ReLU
+    const int fb_rt = d.Tp * d.Npad_fb / 16;
+    FsnGemmA a{};
+    FsnGemmC c{};
+    {
+        StageTimer st(ST_FB_GEMM, s);
+        a = FsnGemmA{};
+        c = FsnGemmC{};
+        a.kind = 1;
+        a.p0 = magT;
+        a.den = w.den_fb;
+        a.den_mode = cum ? 1 : 0;
+        a.B = d.B;
+        a.Tp = d.Tp;
+        a.F = d.F;
+        a.FP = d.FP;
+        a.Npad = d.Npad_fb;
+        c.kind = 0;
+        c.p0 = w.gx_fb;
+        c.bias = pk + p.fb_b0;
+        FSN_TRY(fsn_launch_gemm(a, pk + p.fb_wih0, c, fb_rt, 4 * d.Hf / 16, d.FP / 16, s));
+    }
+    {
+        // N = B rows only: a chain of tiny dependent launches, so the two layers advance as a wavefront
+        // (layer 1 at step t next to layer 0 at step t + 1): T' + 1 launches instead of 2 T'
+        StageTimer st(ST_FB_REC, s);
+        if (d.fb_chain) {  // up to 64 utterances, H = 512: the whole chain as one persistent launch
+            FSN_PERSIST_BEGIN(s);
+            FSN_TRY(fsn_launch_fb_chain(w.gx_fb, pk + p.fb_whh0, pk + p.fb_wih1, pk + p.fb_whh1, pk + p.fb_b1,
+                                        w.fb_exchange, w.fb_flags, w.hseq_fb1, d.Tp, d.Npad_fb, d.Hf, s));
+            FSN_TRY(fsn_launch_poison_if(w.fb_flags + fsn_fb_chain_status_word(), w.hseq_fb1,
+                                         (size_t)d.Tp * d.Npad_fb * d.Hf, s));
+        } else {
+            FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_fb, d.Npad_fb / 16, 0, pk + p.fb_whh0, pk + p.fb_wih1,
+                                               pk + p.fb_b1_frag, pk + p.fb_whh1, w.hseq_fb0, w.hseq_fb1, d.Npad_fb, 0,
+                                               w.c_fb, w.c_fb + (size_t)d.Npad_fb * d.Hf, d.Tp, d.Npad_fb / 16, d.Hf, s));
+        }
+    }
+    {
+        StageTimer st(ST_FB_GEMM, s);
+        a = FsnGemmA{};
+        c = FsnGemmC{};
+        a.kind = 0;
+        a.p0 = w.hseq_fb1;
+        a.ld = d.Hf;
+        c.kind = 1;
+        c.p0 = w.fb_out;
+        c.bias = pk + p.fb_fcb;
+        c.B = d.B;
+        c.Tp = d.Tp;
+        c.F = d.F;
+        c.FP = d.FP;
+        c.Npad = d.Npad_fb;
+        FSN_TRY(fsn_launch_gemm(a, pk + p.fb_fc, c, fb_rt, d.FP / 16, d.Hf / 16, s));
+    }
+    if (fullband_only) return FSN_OK;  // fsn_fullsubnet_fullband: w.fb_out is the result
+    // sub-band norm divisor over the (virtual) concatenated sub-band input (model.py:110-111)
+    {
+        StageTimer st(ST_NORM, s);
+        if (cum) {
+            FSN_TRY(fsn_launch_cumulative_den_sb(magT, w.fb_out, w.den_sb, d.B, d.Tp, d.F, d.FP, d.nb, d.den_stride, s));
+        } else {
+            FSN_TRY(fsn_launch_offline_den(w.binsum, w.fb_out, nullptr, w.den_sb, d.B, d.Tp, d.F, d.FP, d.nb, 1, s,
+                                           lengths, d.T));
+        }
+    }
+    if (d.grp_clusters > 0) {
+        // Few rows (6 - 9 utterances): both layers + output layer of the first 64 x clusters rows as ONE persistent launch
+        // (lstm_group_kernels.hip); what does not fill a cluster runs beside it on the auxiliary stream as the two-layer
+        // wavefront of per-step launches (its projection GEMM first, its output layer last).
+        const long grp_rows = (long)d.grp_clusters * 64;
+        const int aux_tiles = d.rec.tiles - d.grp_clusters * 4;
+        FsnSbInput xin{};
+        xin.mag = magT;
+        xin.fb_out = w.fb_out;
+        xin.den = w.den_sb;
+        xin.wih_p = pk + p.sb_wih0;
+        xin.bias = pk + p.sb_b0;
+        xin.den_mode = cum ? 1 : 0;
+        xin.den_stride = d.den_stride;
+        xin.row0 = d.row0;
+        xin.B = d.B;
+        xin.Tp = d.Tp;
+        xin.F = d.F;
+        xin.FP = d.FP;
+        xin.N = d.N < grp_rows ? d.N : (int)grp_rows;
+        xin.nb = d.nb;
+        xin.kin_chunks = p.sb_kin_pad / 16;
+        FsnRecFc gfc{};
+        gfc.w_p = pk + p.sb_fc;
+        gfc.bias = pk + p.sb_fcb;
+        gfc.crm_r = crm_r;
+        gfc.crm_i = crm_i;
+        gfc.N = xin.N;
+        gfc.row0 = d.row0;
+        gfc.F = d.F;
+        gfc.FP = d.FP;
+        gfc.T = d.T;
+        gfc.la = d.la;
+        // The group kernel fills every CU with two 216-register workgroups: what runs beside it must fit in the 80
+        // registers per lane that are left - the two-layer wavefront step kernel (78) and the output-layer GEMM (52) do,
+        // the projection GEMM of the left-over rows does not, so it goes first, on the caller's stream.
+        StreamCtx* cx = nullptr;
+        hipStream_t as = s;
+        if (aux_tiles > 0) {
+            a = FsnGemmA{};
+            c = FsnGemmC{};
+            a.kind = 2;
+            a.p0 = magT;
+            a.p1 = w.fb_out;
+            a.den = w.den_sb;
+            a.den_mode = cum ? 1 : 0;
+            a.den_stride = d.den_stride;
+            a.B = d.B;
+            a.Tp = d.Tp;
+            a.F = d.F;
+            a.FP = d.FP;
+            a.Npad = aux_tiles * 16;
+            a.n_offset = (int)(d.row0 + grp_rows);
+            a.N = (int)(d.row0 + d.N);
+            a.nb = d.nb;
+            c.kind = 0;
+            c.p0 = w.gx_sb;
+            c.bias = pk + p.sb_b0;
+            {
+                StageTimer st(ST_SB_GEMM_L0, s);
+                FSN_TRY(fsn_launch_gemm(a, pk + p.sb_wih0, c, d.Tp * aux_tiles, 4 * d.Hs / 16, p.sb_kin_pad / 16, s));
+            }
+            cx = cur_ctx();
+            FSN_TRY(aux_init(cx));
+            if (hipEventRecord(cx->ev_fork, s) != hipSuccess || hipStreamWaitEvent(cx->aux, cx->ev_fork, 0) != hipSuccess) {
+                fsn_set_error("aux stream fork failed");
+                return FSN_ERR_LAUNCH;
+            }
+            as = cx->aux;
+        }
+        {
+            StageTimer st(ST_SB_REC_L0, s);
+            FSN_PERSIST_BEGIN(s);
+            FSN_TRY(fsn_launch_lstm2_group(&xin, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_whh1, pk + p.sb_b1,
+                                           w.grp_exchange, w.grp_flags, &gfc, d.Tp, d.grp_clusters, d.Hs, s));
+        }
+        if (aux_tiles > 0) {
+            FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_sb, aux_tiles, 0, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_b1_frag,
+                                               pk + p.sb_whh1, w.hseq_sb0, w.hseq_sb1, (long)aux_tiles * 16, 0, w.c_left,
+                                               w.c_left + (size_t)aux_tiles * 16 * d.Hs, d.Tp, aux_tiles, d.Hs, as, nullptr,
+                                               nullptr, 1));
+            a = FsnGemmA{};
+            c = FsnGemmC{};
+            a.kind = 0;
+            a.p0 = w.hseq_sb1;
+            a.ld = d.Hs;
+            c.kind = 2;
+            c.p0 = crm_r;
+            c.p1 = crm_i;
+            c.bias = pk + p.sb_fcb;
+            c.T = d.T;
+            c.F = d.F;
+            c.FP = d.FP;
+            c.Npad = aux_tiles * 16;
+            c.N = (int)(d.row0 + d.N);
+            c.n_off = (int)(d.row0 + grp_rows);
+            c.la = d.la;
+            FSN_TRY(fsn_launch_gemm(a, pk + p.sb_fc, c, d.Tp * aux_tiles, 1, d.Hs / 16, as));
+            if (hipEventRecord(cx->ev_join, cx->aux) != hipSuccess || hipStreamWaitEvent(s, cx->ev_join, 0) != hipSuccess) {
+                fsn_set_error("aux stream join failed");
+                return FSN_ERR_LAUNCH;
+            }
+        }
+        // a spin bound hit inside the group launch (see fsn_launch_poison_if): the mask planes become NaN instead of
+        // garbage - AFTER the join: the left-over rows' output layer on the auxiliary stream writes into the same planes
+        // (poisoned before it, a launch that gave up early left those rows finite: one run of the residency test in many)
+        const unsigned* st_word = w.grp_flags + fsn_lstm2_group_status_word(d.grp_clusters);
+        FSN_TRY(fsn_launch_poison_if(st_word, crm_r, (size_t)d.B * d.T * d.FP, s));
+        FSN_TRY(fsn_launch_poison_if(st_word, crm_i, (size_t)d.B * d.T * d.FP, s));
+        return FSN_OK;
+    }
+    // sub-band model (model.py:121-128): N = B F sequences, 2 LSTM layers + Linear(2)
+    const int sb_rt = (int)((long)d.Tp * d.Npad / 16);
+    // Layer 0: the K = 2nb+2 input projection is fused into the persistent recurrent kernel (no 19 GB
+    // gx round trip); only the few left-over tiles, which run step by step, get a precomputed gx.
+    const long main_rows = (long)d.rec.main_wgs * d.rec.rt * 16;
+    if (d.rec.left_tiles > 0) {
+        StageTimer st(ST_SB_GEMM_L0, s);
+        a = FsnGemmA{};
+        c = FsnGemmC{};
+        a.kind = 2;
+        a.p0 = magT;
+        a.p1 = w.fb_out;
+        a.den = w.den_sb;
+        a.den_mode = cum ? 1 : 0;
+        a.den_stride = d.den_stride;
+        a.B = d.B;
+        a.Tp = d.Tp;
+        a.F = d.F;
+        a.FP = d.FP;
+        a.Npad = d.rec.left_tiles * 16;
+        a.n_offset = (int)(d.row0 + main_rows);  // the provider works on global rows: first row and row limit
+        a.N = (int)(d.row0 + d.N);
+        a.nb = d.nb;
+        c.kind = 0;
+        c.p0 = w.gx_sb;
+        c.bias = pk + p.sb_b0;
+        FSN_TRY(fsn_launch_gemm(a, pk + p.sb_wih0, c, d.Tp * d.rec.left_tiles, 4 * d.Hs / 16, p.sb_kin_pad / 16, s));
+    }
+    // Small batches (no persistent part): both layers as one wavefront of per-step launches on the
+    // projection computed above.
+    const bool sb_wave = d.rec.main_wgs == 0 && d.rec.left_tiles < kWavefrontBelowTiles;
+    if (sb_wave) {
+        StageTimer st(ST_SB_REC_L0, s);
+        FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_sb, d.rec.left_tiles, 0, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_b1_frag,
+                                           pk + p.sb_whh1, w.hseq_sb0, w.hseq_sb1, d.Npad, 0, w.c_left,
+                                           w.c_left + (size_t)d.rec.left_tiles * 16 * d.Hs, d.Tp, d.rec.left_tiles,
+                                           d.Hs, s));
+    } else {
+        StageTimer st(ST_SB_REC_L0, s);
+        FsnSbInput xin{};
+        xin.mag = magT;
+        xin.fb_out = w.fb_out;
+        xin.den = w.den_sb;
+        xin.wih_p = pk + p.sb_wih0;
+        xin.bias = pk + p.sb_b0;
+        xin.den_mode = cum ? 1 : 0;
+        xin.den_stride = d.den_stride;
+        xin.row0 = d.row0;
+        xin.B = d.B;
+        xin.Tp = d.Tp;
+        xin.F = d.F;
+        xin.FP = d.FP;
+        xin.N = d.N;
+        xin.nb = d.nb;
+        xin.kin_chunks = p.sb_kin_pad / 16;
+        const bool f16x3 = cfg->arith == FSN_ARITH_F16X3;  // opt-in experiment, chosen by the caller
+        const bool l0_split = f16x3 && d.Hs == 384 && 2 * d.nb + 2 == 32;
+        FSN_TRY(run_sb_recurrence(nullptr, &xin, w.gx_sb, d.rec.left_tiles, 0, pk + p.sb_whh0, w.hseq_sb0, w.c_left,
+                                  d, s, nullptr, l0_split ? pk + p.sb_whh0_f16x3 : nullptr,
+                                  l0_split ? pk + p.sb_wih0_f16x3 : nullptr, nullptr, nullptr, nullptr,
+                                  d.l1x ? w.hseq_left0 : nullptr));
+    }
+    if (!sb_wave && d.l1x) {
+        // the main rows form this projection inside lstm_rec_x_kernel; only the left-over rows (step kernels) get one
+        if (d.rec.left_tiles > 0) {
+            StageTimer st(ST_SB_GEMM_L1, s);
+            a = FsnGemmA{};
+            c = FsnGemmC{};
+            a.kind = 0;
+            a.p0 = w.hseq_left0;
+            a.ld = d.Hs;
+            c.kind = 0;
+            c.p0 = w.gx_sb;
+            c.bias = pk + p.sb_b1;
+            FSN_TRY(fsn_launch_gemm(a, pk + p.sb_wih1, c, d.Tp * d.rec.left_tiles, 4 * d.Hs / 16, d.Hs / 16, s));
+        }
+    } else if (!sb_wave) {
+        StageTimer st(ST_SB_GEMM_L1, s);
+        a = FsnGemmA{};
+        c = FsnGemmC{};
+        a.kind = 0;
+        a.p0 = w.hseq_sb0;
+        a.ld = d.Hs;
+        c.kind = 0;
+        c.p0 = w.gx_sb;
+        c.bias = pk + p.sb_b1;
+        const bool f16x3 = cfg->arith == FSN_ARITH_F16X3;  // opt-in experiment, chosen by the caller
+        if (f16x3)
+            FSN_TRY(fsn_launch_gemm_f16x3(w.hseq_sb0, d.Hs, pk + p.sb_wih1_f16x3, pk + p.sb_b1, w.gx_sb, sb_rt, 4 * d.Hs,
+                                          d.Hs, s));
+        else
+            FSN_TRY(fsn_launch_gemm(a, pk + p.sb_wih1, c, sb_rt, 4 * d.Hs / 16, d.Hs / 16, s));
+    }
+    // Output layer (model.py:53-61,129-135).  Where the persistent 4-pass kernel runs layer 1 it forms the two
+    // mask values of a row from h_t in LDS and that layer's 4.8 GB hidden sequence is never written or read
+    // back; only rows that went step by step (left-over tiles, small batches) go through the GEMM below.
+    const bool fc_fused = d.fc_fused;
+    FsnRecFc fc{};
+    if (fc_fused) {
+        fc.w_p = pk + p.sb_fc;
+        fc.bias = pk + p.sb_fcb;
+        fc.crm_r = crm_r;
+        fc.crm_i = crm_i;
+        fc.N = d.N;
+        fc.row0 = d.row0;
+        fc.F = d.F;
+        fc.FP = d.FP;
+        fc.T = d.T;
+        fc.la = d.la;
+    }
+    if (!sb_wave && d.l1x) {
+        StageTimer st(ST_SB_REC_L1, s);
+        FSN_TRY(run_sb_recurrence(nullptr, nullptr, w.gx_sb, d.rec.left_tiles, 0, pk + p.sb_whh1, w.hseq_sb1, w.c_left, d,
+                                  s, &fc, nullptr, nullptr, w.hseq_sb0, pk + p.sb_wih1, pk + p.sb_b1));
+    } else if (!sb_wave) {
+        StageTimer st(ST_SB_REC_L1, s);
+        const bool f16x3 = cfg->arith == FSN_ARITH_F16X3;  // opt-in experiment, chosen by the caller
+        FSN_TRY(run_sb_recurrence(w.gx_sb, nullptr, w.gx_sb, d.rec.tiles, main_rows / 16, pk + p.sb_whh1, w.hseq_sb1,
+                                  w.c_left, d, s, fc_fused ? &fc : nullptr,
+                                  f16x3 && fc_fused ? pk + p.sb_whh1_f16x3 : nullptr));
+    }
+    if (!fc_fused || d.rec.left_tiles > 0) {
+        StageTimer st(ST_SB_FC, s);
+        a = FsnGemmA{};
+        c = FsnGemmC{};
+        a.kind = 0;
+        a.p0 = w.hseq_sb1;
+        a.ld = d.Hs;
+        c.kind = 2;
+        c.p0 = crm_r;
+        c.p1 = crm_i;
+        c.bias = pk + p.sb_fcb;
+        c.T = d.T;
+        c.F = d.F;
+        c.FP = d.FP;
+        c.Npad = d.Npad;
+        c.N = (int)(d.row0 + d.N);  // global rows, like the A provider above
+        c.n_off = (int)d.row0;
+        c.la = d.la;
+        int rows_t = sb_rt;
+        if (fc_fused) {  // only the left-over rows: hseq_sb1 is the compact [t][left rows][H] matrix
+            c.Npad = d.rec.left_tiles * 16;
+            c.n_off = (int)(d.row0 + main_rows);
+            rows_t = d.Tp * d.rec.left_tiles;
+        }
+        FSN_TRY(fsn_launch_gemm(a, pk + p.sb_fc, c, rows_t, 1, d.Hs / 16, s));
+    }
+    return FSN_OK;
+}
+
+static int check_bt(int B, int T) {
+    FSN_REQUIRE(B >= 1 && B <= 4096, "batch %d out of range", B);
+    FSN_REQUIRE(T >= 1 && T <= 100000, "frames %d out of range", T);
+    return FSN_OK;
+}
+
+// Batches beyond what ONE round of the persistent kernels holds at 4 row tiles per workgroup (64 utterances of 257 bins
+// on 256 CUs) run as whole chunks of that size plus a remainder, one after the other: the model has no cross-utterance
+// term (both norms are per utterance), and a workgroup walks its RT tiles one after the other every step, so a batch
+// that does not fill rounds x RT x CUs tiles pays for the full round - 104 utterances took 171 ms as two rounds of 4,
+// 64 + 40 take 84 + 63.  Returns the chunk size (B itself: no chunking).
+static int core_chunk(const fsn_fullsubnet_cfg* cfg, int B) {
+    const int cus = plan_cus();
+    const long b0 = ((long)cus * 4 + 16) * 16 / cfg->num_freqs;
+    return b0 >= 1 && B > b0 ? (int)b0 : B;
+}
+// Below one round the same holds between the regimes: 40 utterances take as long as 48 (one round of 3 tiles per
+// workgroup), 24 as long as 32, 10 - 13 run at one tile per CU - where 32 + 8, 16 + 8 and 8 + 2 as separate calls are 12 -
+// 18 % faster.  Time of one core call in microseconds per frame step, from the plan it would take (calibrated on
+// config 2's clips: 1 / 2 / 4 / 8 / 16 / 32 / 48 / 64 utterances = 24 / 37 / 60 / 66 / 122 / 229 / 337 / 441 us per step):
+static double core_cost(const fsn_fullsubnet_cfg* cfg, int b) {
+    const int cus = plan_cus();
+    const CoreDims d = core_dims(cfg, b, 64);
+    double c = 6.0;  // the full-band chain and the fixed launches of a call
+    if (d.rec.main_wgs > 0) {
+        const int rounds = (d.rec.main_wgs + cus - 1) / cus;
+        c += rounds * (d.rec.rt == 1 ? 120.0 : 110.0 * d.rec.rt);  // one tile per CU streams all weights for 16 rows
+    } else if (d.grp_clusters > 0) {
+        c += (d.grp_clusters > cus / 8 ? 2 : 1) * 58.0 + (d.rec.left_tiles - 4 * d.grp_clusters > 0 ? 2.0 : 0.0);
+    } else {
+        c += 7.0 + 0.67 * d.rec.left_tiles;  // two-layer wavefront of per-step launches
+    }
+    return c;
+}
+// the chunk sizes of a batch, largest first: whole rounds of core_chunk(), then the cheapest split of the remainder into
+// {itself, 48, 32, 16, 8}-utterance calls by core_cost
+static int core_chunks_search(const fsn_fullsubnet_cfg* cfg, int B, int* sizes, int max_sizes);
+// The search evaluates core_cost / core_dims ~5 x (remainder) times, each with device-attribute and occupancy lookups:
+// ~10^4 host calls at B = 64, three times per fsn_enhance (workspace query, workspace check, run).  The plan depends
+// only on (configuration, B, device, persistent mode): memoised.
+static int core_chunks(const fsn_fullsubnet_cfg* cfg, int B, int* sizes, int max_sizes) {
+    static std::mutex mu;
+    static std::map<std::string, std::vector<int>> memo;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::string key(reinterpret_cast<const char*>(cfg), sizeof(*cfg));
+    const int tail[4] = {B, dev, fsn_persistent_allowed() ? 1 : 0, max_sizes};
+    key.append(reinterpret_cast<const char*>(tail), sizeof(tail));
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = memo.find(key);
+        if (it != memo.end()) {
+            for (size_t i = 0; i < it->second.size(); ++i) sizes[i] = it->second[i];
+            return (int)it->second.size();
+        }
+    }
+    const int n = core_chunks_search(cfg, B, sizes, max_sizes);
+    std::lock_guard<std::mutex> lk(mu);
+    if (memo.size() > 4096) memo.clear();
+    memo[key] = std::vector<int>(sizes, sizes + n);
+    return n;
+}
+static int core_chunks_search(const fsn_fullsubnet_cfg* cfg, int B, int* sizes, int max_sizes) {
+    int n = 0;
+    const int full = core_chunk(cfg, B);
+    int rem = B;
+    while (rem > full && n < max_sizes - 8) {
+        sizes[n++] = full;
+        rem -= full;
+    }
+    if (rem > 64 || !fsn_persistent_allowed() || cfg->arith != FSN_ARITH_F32) {  // outside the calibrated range: as one call
+        sizes[n++] = rem;
+        return n;
+    }
+    double best[65];
+    int first[65];
+    best[0] = 0.0;
+    first[0] = 0;
+    for (int b = 1; b <= rem; ++b) {
+        best[b] = core_cost(cfg, b);
+        first[b] = b;
+        for (int c : {48, 32, 16, 8}) {
+            if (c >= b) continue;
+            const double v = core_cost(cfg, c) + best[b - c];
+            if (v < 0.97 * best[b]) {  // a split has to be worth it
+                best[b] = v;
+                first[b] = c;
+            }
+        }
+    }
+    for (int b = rem; b > 0 && n < max_sizes; b -= first[b]) sizes[n++] = first[b];
+    return n;
+}
+constexpr int kMaxChunks = 80;  // 4096 utterances (check_bt) in rounds of >= 64, plus the remainder's few calls
+// the core's scratch behind the per-batch planes: sized for the largest chunk's plan (the chunks reuse it)
+static void core_carve_chunks(Carver& cv, const fsn_fullsubnet_cfg* cfg, int B, int T) {
+    int sizes[kMaxChunks];
+    const int n = core_chunks(cfg, B, sizes, kMaxChunks);
+    size_t most = 0;
+    for (int i = 0; i < n; ++i) {
+        if (i > 0 && sizes[i] == sizes[i - 1]) continue;
+        Carver c2(nullptr);
+        core_carve(c2, core_dims(cfg, sizes[i], T), cfg->norm_type);
+        most = c2.off > most ? c2.off : most;
+    }
+    cv.take<char>(most);
+}
+// run_core over the chunks; `scratch` = a region of at least core_carve_chunks' size; lengths: see run_core
+static int run_core_chunks(const fsn_fullsubnet_cfg* cfg, const float* pk, const float* magT, int B, int T, void* scratch,
+                           float* crm_r, float* crm_i, hipStream_t s, const int* lengths = nullptr) {
+    int sizes[kMaxChunks];
+    const int n = core_chunks(cfg, B, sizes, kMaxChunks);
+    int b0 = 0;
+    for (int i = 0; i < n; ++i) {
+        const int b = sizes[i];
+        const CoreDims d = core_dims(cfg, b, T);
+        Carver cv(scratch);
+        const CoreWs w = core_carve(cv, d, cfg->norm_type);
+        FSN_TRY(run_core(cfg, pk, magT + (size_t)b0 * d.Tp * d.FP, d, w, crm_r + (size_t)b0 * d.T * d.FP,
+                         crm_i + (size_t)b0 * d.T * d.FP, s, false, lengths ? lengths + b0 : nullptr));
+        b0 += b;
+    }
+    FSN_REQUIRE(b0 == B, "internal: the chunks cover %d of %d utterances", b0, B);
+    return FSN_OK;
+}
+
+// test hook: the utterance counts of the core calls a batch of B runs as (sum = B); returns their number
+extern "C" int fsn_debug_core_chunks(const fsn_fullsubnet_cfg* cfg, int B, int* sizes, int max_sizes) {
+    if (check_cfg(cfg) != FSN_OK || B < 1 || B > 4096 || !sizes || max_sizes < kMaxChunks) return -1;
+    return core_chunks(cfg, B, sizes, kMaxChunks);
+}
+
+extern "C" int fsn_debug_core_plan(const fsn_fullsubnet_cfg* cfg, int B, int T, int* plan, int n) {
+    if (check_cfg(cfg) != FSN_OK || check_bt(B, T) != FSN_OK || !plan || n < 8) return -1;
+    int sizes[kMaxChunks];
+    const int chunks = core_chunks(cfg, B, sizes, kMaxChunks);
+    const CoreDims d = core_dims(cfg, chunks > 0 ? sizes[0] : B, T);
+    plan[0] = d.N;
+    plan[1] = d.rec.tiles;
+    plan[2] = d.rec.rt;
+    plan[3] = d.rec.main_wgs;
+    plan[4] = d.rec.left_tiles;
+    plan[5] = d.grp_clusters;
+    plan[6] = d.fb_chain ? 1 : 0;
+    plan[7] = chunks;
+    if (n >= 9) {  // rows on the persistent recurrent pair over ALL chunks (whole rounds and a remainder have different plans)
+        long rows = 0;
+        for (int c = 0; c < (chunks > 0 ? chunks : 1); ++c) {
+            const CoreDims dc = core_dims(cfg, chunks > 0 ? sizes[c] : B, T);
+            rows += (long)dc.rec.main_wgs * dc.rec.rt * 16;
+        }
+        plan[8] = (int)rows;
+    }
+    return FSN_OK;
+}
+
+extern "C" size_t fsn_fullsubnet_workspace_bytes(const fsn_fullsubnet_cfg* cfg, int B, int T) {
+    if (check_cfg(cfg) != FSN_OK || check_bt(B, T) != FSN_OK) return 0;
+    const CoreDims d = core_dims(cfg, B, T);
+    Carver cv(nullptr);
+    cv.take<float>((size_t)B * d.Tp * d.FP);     // magT
+    cv.take<float>((size_t)B * d.T * d.FP);      // crm_r
+    cv.take<float>((size_t)B * d.T * d.FP);      // crm_i
+    // the whole batch's plan (what the stage-level entries carve) is never smaller than a chunk's; both are checked
+    Carver whole(nullptr), parts(nullptr);
+    core_carve(whole, d, cfg->norm_type);
+    core_carve_chunks(parts, cfg, B, T);
+    cv.take<char>(whole.off > parts.off ? whole.off : parts.off);
+    return fsn_round_up_sz(cv.off, 256);
+}
+
+extern "C" int fsn_fullsubnet_forward(const fsn_fullsubnet_cfg* cfg, const void* packed, const float* noisy_mag,
+                                      int B, int T, float* crm_out, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_cfg(cfg));
+    FSN_TRY(check_bt(B, T));
+    FSN_REQUIRE(packed && noisy_mag && crm_out && workspace, "NULL pointer argument");
+    const size_t need = fsn_fullsubnet_workspace_bytes(cfg, B, T);
+    if (workspace_bytes < need) {
+        fsn_set_error("workspace too small: %zu < %zu bytes", workspace_bytes, need);
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const CoreDims d = core_dims(cfg, B, T);
+    Carver cv(workspace);
+    float* magT = cv.take<float>((size_t)B * d.Tp * d.FP);
+    float* crm_r = cv.take<float>((size_t)B * d.T * d.FP);
+    float* crm_i = cv.take<float>((size_t)B * d.T * d.FP);
+    void* scratch = cv.take<char>(0);  // the rest: the core's scratch (fsn_fullsubnet_workspace_bytes)
+    prof_reset();
+    // [B,1,F,T] -> frame-major [B][Tp][FP]; look-ahead frames (model.py:85) and padded bins are zeros
+    FSN_TRY(fsn_launch_transpose(noisy_mag, magT, B, d.FP, d.Tp, T, (long)d.F * T, d.FP, (long)d.Tp * d.FP, d.F, T, s));
+    FSN_TRY(run_core_chunks(cfg, static_cast<const float*>(packed), magT, B, T, scratch, crm_r, crm_i, s));
+    // frame-major planes -> [B, 2, F, T] (model.py:129-135)
+    FSN_TRY(fsn_launch_transpose(crm_r, crm_out, B, T, d.F, d.FP, (long)T * d.FP, T, 2L * d.F * T, T, d.F, s));
+    FSN_TRY(fsn_launch_transpose(crm_i, crm_out + (size_t)d.F * T, B, T, d.F, d.FP, (long)T * d.FP, T, 2L * d.F * T,
+                                 T, d.F, s));
+    return FSN_OK;
+}
+
+// ---- the full-band stage alone: model.py:85-95 ---------------------------------------------------
+// look-ahead pad -> norm -> fb_model, i.e. the tensor `fb_output` of model.py:95 in the reference's layout
+// [B, F, T + look_ahead].  Stage-level parity checks read it; a batch-sharded full-band model would too.
+extern "C" int fsn_fullsubnet_fullband(const fsn_fullsubnet_cfg* cfg, const void* packed, const float* noisy_mag,
+                                       int B, int T, float* fb_output, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_cfg(cfg));
+    FSN_TRY(check_bt(B, T));
+    FSN_REQUIRE(packed && noisy_mag && fb_output && workspace, "NULL pointer argument");
+    const size_t need = fsn_fullsubnet_workspace_bytes(cfg, B, T);
+    if (workspace_bytes < need) {
+        fsn_set_error("workspace too small: %zu < %zu bytes", workspace_bytes, need);
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const CoreDims d = core_dims(cfg, B, T);
+    Carver cv(workspace);
+    float* magT = cv.take<float>((size_t)B * d.Tp * d.FP);
+    cv.take<float>((size_t)B * d.T * d.FP);
+    cv.take<float>((size_t)B * d.T * d.FP);
+    const CoreWs w = core_carve(cv, d, cfg->norm_type);
+    prof_reset();
+    FSN_TRY(fsn_launch_transpose(noisy_mag, magT, B, d.FP, d.Tp, T, (long)d.F * T, d.FP, (long)d.Tp * d.FP, d.F, T, s));
+    FSN_TRY(run_core(cfg, static_cast<const float*>(packed), magT, d, w, nullptr, nullptr, s, true));
+    // frame-major [B][T'][FP] -> [B, F, T']
+    FSN_TRY(fsn_launch_transpose(w.fb_out, fb_output, B, d.Tp, d.F, d.FP, (long)d.Tp * d.FP, d.Tp, (long)d.F * d.Tp,
+                                 d.Tp, d.F, s));
+    return FSN_OK;
+}
+
+// ---- row-range form: the sub-band model on a contiguous slice of the flattened (b, f) rows -------------------
+// "rank r owns a contiguous slice of the flattened (b, f) index space".  Only the utterances the
+// slice touches are looked at: their full-band model and norm statistics are computed whole (they couple all
+// bins of an utterance), the sub-band model only on rows [row_begin, row_end).  A slice that is aligned to
+// utterances is exactly fsn_fullsubnet_forward on those utterances.
+struct RowSlice {
+    int b_lo, Bs;
+    long r0, n;
+};
+static int row_slice(const fsn_fullsubnet_cfg* cfg, int B, long row_begin, long row_end, RowSlice* out) {
+    const long F = cfg->num_freqs;
+    FSN_REQUIRE(row_begin >= 0 && row_begin < row_end && row_end <= (long)B * F,
+                "row range [%ld, %ld) is not inside the %ld sub-band rows of the batch", row_begin, row_end, (long)B * F);
+    out->b_lo = (int)(row_begin / F);
+    out->Bs = (int)((row_end - 1) / F) - out->b_lo + 1;
+    out->r0 = row_begin - (long)out->b_lo * F;
+    out->n = row_end - row_begin;
+    return FSN_OK;
+}
+
+extern "C" size_t fsn_fullsubnet_rows_workspace_bytes(const fsn_fullsubnet_cfg* cfg, int B, int T, long row_begin,
+                                                      long row_end) {
+    RowSlice r;
+    if (check_cfg(cfg) != FSN_OK || check_bt(B, T) != FSN_OK || row_slice(cfg, B, row_begin, row_end, &r) != FSN_OK)
+        return 0;
+    const CoreDims d = core_dims(cfg, r.Bs, T, r.r0, r.n);
+    Carver cv(nullptr);
+    cv.take<float>((size_t)r.Bs * d.Tp * d.FP);  // magT
+    cv.take<float>((size_t)r.Bs * d.T * d.FP);   // crm_r
+    cv.take<float>((size_t)r.Bs * d.T * d.FP);   // crm_i
+    core_carve(cv, d, cfg->norm_type);
+    return fsn_round_up_sz(cv.off, 256);
+}
+
+extern "C" int fsn_fullsubnet_forward_rows(const fsn_fullsubnet_cfg* cfg, const void* packed, const float* noisy_mag,
+                                           int B, int T, long row_begin, long row_end, float* crm_rows,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_cfg(cfg));
+    FSN_TRY(check_bt(B, T));
+    RowSlice r;
+    FSN_TRY(row_slice(cfg, B, row_begin, row_end, &r));
+    FSN_REQUIRE(packed && noisy_mag && crm_rows && workspace, "NULL pointer argument");
+    const size_t need = fsn_fullsubnet_rows_workspace_bytes(cfg, B, T, row_begin, row_end);
+    if (workspace_bytes < need) {
+        fsn_set_error("workspace too small: %zu < %zu bytes", workspace_bytes, need);
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const CoreDims d = core_dims(cfg, r.Bs, T, r.r0, r.n);
+    Carver cv(workspace);
+    float* magT = cv.take<float>((size_t)r.Bs * d.Tp * d.FP);
+    float* crm_r = cv.take<float>((size_t)r.Bs * d.T * d.FP);
+    float* crm_i = cv.take<float>((size_t)r.Bs * d.T * d.FP);
+    const CoreWs w = core_carve(cv, d, cfg->norm_type);
+    prof_reset();
+    const float* mag_lo = noisy_mag + (size_t)r.b_lo * d.F * T;  // [B, 1, F, T]: utterances are contiguous
+    FSN_TRY(fsn_launch_transpose(mag_lo, magT, r.Bs, d.FP, d.Tp, T, (long)d.F * T, d.FP, (long)d.Tp * d.FP, d.F, T, s));
+    FSN_TRY(run_core(cfg, static_cast<const float*>(packed), magT, d, w, crm_r, crm_i, s));
+    // this slice's rows of the frame-major planes -> [row][2][T] (what the ranks all-gather)
+    FSN_TRY(fsn_launch_crm_rows(crm_r, crm_i, crm_rows, r.r0, r.n, d.F, d.FP, T, s));
+    return FSN_OK;
+}
+
+
+// ---- streaming: k more frames of the model with carried state -------------------------------------
+// State (caller-owned, zero-filled for a new stream): (h, c) of the four LSTM layers and the running sums
+// of the two cumulative Laplace norms.
+struct StreamState {
+    float *fb_h0, *fb_h1, *fb_c0, *fb_c1, *sb_h0, *sb_h1, *sb_c0, *sb_c1;
+    double *fb_sum, *sb_sum;
+};
+static StreamState stream_carve(Carver& cv, const fsn_fullsubnet_cfg* cfg, int B) {
+    StreamState st;
+    const size_t nfb = (size_t)fsn_round_up(B, 16) * cfg->fb_hidden;
+    const size_t nsb = (size_t)fsn_round_up(B * cfg->num_freqs, 16) * cfg->sb_hidden;
+    st.fb_h0 = cv.take<float>(nfb);
+    st.fb_h1 = cv.take<float>(nfb);
+    st.fb_c0 = cv.take<float>(nfb);
+    st.fb_c1 = cv.take<float>(nfb);
+    st.sb_h0 = cv.take<float>(nsb);
+    st.sb_h1 = cv.take<float>(nsb);
+    st.sb_c0 = cv.take<float>(nsb);
+    st.sb_c1 = cv.take<float>(nsb);
+    st.fb_sum = cv.take<double>((size_t)B);
+    st.sb_sum = cv.take<double>((size_t)B * cfg->num_freqs);
+    return st;
+}
+struct StreamWs {
+    float *magT, *crm_r, *crm_i, *den_fb, *gx_fb, *hseq_fb0, *hseq_fb1, *fb_out, *den_sb, *gx_sb, *hseq_sb0, *hseq_sb1;
+};
+static StreamWs stream_ws_carve(Carver& cv, const fsn_fullsubnet_cfg* cfg, int B, int k) {
+    StreamWs w;
+    const int FP = fsn_fpad(cfg->num_freqs), Npad_fb = fsn_round_up(B, 16), Npad = fsn_round_up(B * cfg->num_freqs, 16);
+    const size_t plane = (size_t)B * k * FP;
+    w.magT = cv.take<float>(plane);
+    w.crm_r = cv.take<float>(plane);
+    w.crm_i = cv.take<float>(plane);
+    w.den_fb = cv.take<float>((size_t)B * k);
+    w.gx_fb = cv.take<float>((size_t)k * Npad_fb * 4 * cfg->fb_hidden);
+    w.hseq_fb0 = cv.take<float>((size_t)k * Npad_fb * cfg->fb_hidden);
+    w.hseq_fb1 = cv.take<float>((size_t)k * Npad_fb * cfg->fb_hidden);
+    w.fb_out = cv.take<float>(plane);
+    w.den_sb = cv.take<float>((size_t)k * Npad);
+    w.gx_sb = cv.take<float>((size_t)k * Npad * 4 * cfg->sb_hidden);
+    w.hseq_sb0 = cv.take<float>((size_t)k * Npad * cfg->sb_hidden);
+    w.hseq_sb1 = cv.take<float>((size_t)k * Npad * cfg->sb_hidden);
+    return w;
+}
+static int check_stream(const fsn_fullsubnet_cfg* cfg, int B, int k) {
+    FSN_TRY(check_cfg(cfg));
+    FSN_REQUIRE(cfg->norm_type == FSN_NORM_CUMULATIVE_LAPLACE, "streaming needs the causal norm (FSN_NORM_CUMULATIVE_LAPLACE)");
+    FSN_REQUIRE(B >= 1 && B <= 4096 && k >= 1 && k <= 4096, "streaming: batch %d / frames %d out of range", B, k);
+    return FSN_OK;
+}
+extern "C" size_t fsn_fullsubnet_stream_state_bytes(const fsn_fullsubnet_cfg* cfg, int B) {
+    if (check_stream(cfg, B, 1) != FSN_OK) return 0;
+    Carver cv(nullptr);
+    stream_carve(cv, cfg, B);
+    return fsn_round_up_sz(cv.off, 256);
+}
+extern "C" size_t fsn_fullsubnet_stream_workspace_bytes(const fsn_fullsubnet_cfg* cfg, int B, int k) {
+    if (check_stream(cfg, B, k) != FSN_OK) return 0;
+    Carver cv(nullptr);
+    stream_ws_carve(cv, cfg, B, k);
+    return fsn_round_up_sz(cv.off, 256);
+}
+
+extern "C" int fsn_fullsubnet_stream_step(const fsn_fullsubnet_cfg* cfg, const void* packed, void* state,
+                                          size_t state_bytes, int steps_done, const float* mag, int B, int k,
+                                          float* crm_out, void* workspace, size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_stream(cfg, B, k));
+    FSN_REQUIRE(packed && state && mag && crm_out && workspace && steps_done >= 0, "NULL pointer argument / negative step count");
+    if (state_bytes < fsn_fullsubnet_stream_state_bytes(cfg, B) ||
+        workspace_bytes < fsn_fullsubnet_stream_workspace_bytes(cfg, B, k)) {
+        fsn_set_error("streaming: state / workspace buffer too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Packed p = packed_layout(cfg);
+    const float* pk = static_cast<const float*>(packed);
+    const int F = cfg->num_freqs, FP = fsn_fpad(F), Hf = cfg->fb_hidden, Hs = cfg->sb_hidden, nb = cfg->sb_num_neighbors;
+    const int Npad_fb = fsn_round_up(B, 16), N = B * F, Npad = fsn_round_up(N, 16);
+    Carver cs(state), cw(workspace);
+    const StreamState st = stream_carve(cs, cfg, B);
+    const StreamWs w = stream_ws_carve(cw, cfg, B, k);
+    // [B, 1, F, k] -> frame-major [B][k][FP]
+    FSN_TRY(fsn_launch_transpose(mag, w.magT, B, FP, k, k, (long)F * k, FP, (long)k * FP, F, k, s));
+    FSN_TRY(fsn_launch_cumulative_den_fb(w.magT, w.den_fb, B, k, F, FP, s, st.fb_sum, steps_done));
+    FsnGemmA a{};
+    FsnGemmC c{};
+    a.kind = 1;
+    a.p0 = w.magT;
+    a.den = w.den_fb;
+    a.den_mode = 1;
+    a.B = B;
+    a.Tp = k;
+    a.F = F;
+    a.FP = FP;
+    a.Npad = Npad_fb;
+    c.kind = 0;
+    c.p0 = w.gx_fb;
+    c.bias = pk + p.fb_b0;
+    const int fb_rt = k * Npad_fb / 16;
+    FSN_TRY(fsn_launch_gemm(a, pk + p.fb_wih0, c, fb_rt, 4 * Hf / 16, FP / 16, s));
+    FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_fb, Npad_fb / 16, 0, pk + p.fb_whh0, pk + p.fb_wih1, pk + p.fb_b1_frag,
+                                       pk + p.fb_whh1, w.hseq_fb0, w.hseq_fb1, Npad_fb, 0, st.fb_c0, st.fb_c1, k,
+                                       Npad_fb / 16, Hf, s, st.fb_h0, st.fb_h1));
+    a = FsnGemmA{};
+    c = FsnGemmC{};
+    a.kind = 0;
+    a.p0 = w.hseq_fb1;
+    a.ld = Hf;
+    c.kind = 1;
+    c.p0 = w.fb_out;
+    c.bias = pk + p.fb_fcb;
+    c.B = B;
+    c.Tp = k;
+    c.F = F;
+    c.FP = FP;
+    c.Npad = Npad_fb;
+    FSN_TRY(fsn_launch_gemm(a, pk + p.fb_fc, c, fb_rt, FP / 16, Hf / 16, s));
+    FSN_TRY(fsn_launch_cumulative_den_sb(w.magT, w.fb_out, w.den_sb, B, k, F, FP, nb, Npad, s, st.sb_sum, steps_done));
+    a = FsnGemmA{};
+    c = FsnGemmC{};
+    a.kind = 2;
+    a.p0 = w.magT;
+    a.p1 = w.fb_out;
+    a.den = w.den_sb;
+    a.den_mode = 1;
+    a.den_stride = Npad;
+    a.B = B;
+    a.Tp = k;
+    a.F = F;
+    a.FP = FP;
+    a.Npad = Npad;
+    a.n_offset = 0;
+    a.N = N;
+    a.nb = nb;
+    c.kind = 0;
+    c.p0 = w.gx_sb;
+    c.bias = pk + p.sb_b0;
+    const int sb_rt = (int)((long)k * Npad / 16);
+    FSN_TRY(fsn_launch_gemm(a, pk + p.sb_wih0, c, sb_rt, 4 * Hs / 16, p.sb_kin_pad / 16, s));
+    FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_sb, Npad / 16, 0, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_b1_frag,
+                                       pk + p.sb_whh1, w.hseq_sb0, w.hseq_sb1, Npad, 0, st.sb_c0, st.sb_c1, k, Npad / 16,
+                                       Hs, s, st.sb_h0, st.sb_h1));
+    a = FsnGemmA{};
+    c = FsnGemmC{};
+    a.kind = 0;
+    a.p0 = w.hseq_sb1;
+    a.ld = Hs;
+    c.kind = 2;
+    c.p0 = w.crm_r;
+    c.p1 = w.crm_i;
+    c.bias = pk + p.sb_fcb;
+    c.T = k;
+    c.F = F;
+    c.FP = FP;
+    c.Npad = Npad;
+    c.N = N;
+    c.la = 0;  // every model step is handed back; the caller matches step s to output frame s - look_ahead
+    FSN_TRY(fsn_launch_gemm(a, pk + p.sb_fc, c, sb_rt, 1, Hs / 16, s));
+    FSN_TRY(fsn_launch_transpose(w.crm_r, crm_out, B, k, F, FP, (long)k * FP, k, 2L * F * k, k, F, s));
+    FSN_TRY(fsn_launch_transpose(w.crm_i, crm_out + (size_t)F * k, B, k, F, FP, (long)k * FP, k, 2L * F * k, k, F, s));
+    return FSN_OK;
+}
+
+// ---- STFT / iSTFT boundary -------------------------------------------------------------------
+static bool fast_fft(int n_fft, int hop) { return n_fft == 512 && hop == 256; }
+
+// fsn_enhance's fused path is built for the FullSubNet recipe's transform only
+static int check_fft(int n_fft, int hop, int win_length) {
+    FSN_REQUIRE(n_fft == 512 && hop == 256 && win_length == 512,
+                "fsn_enhance: only n_fft = win_length = 512, hop = 256 is built (got %d/%d/%d)", n_fft, win_length, hop);
+    return FSN_OK;
+}
+
+// fsn_stft / fsn_istft: 512 / 256 on the radix-8 kernels, any other even size / hop on the direct DFT
+static int check_fft_generic(int n_fft, int hop, int win_length) {
+    FSN_REQUIRE(win_length == n_fft, "win_length %d != n_fft %d is not built", win_length, n_fft);
+    FSN_REQUIRE(n_fft >= 16 && n_fft <= 4096 && n_fft % 2 == 0, "n_fft %d: need an even size in [16, 4096]", n_fft);
+    FSN_REQUIRE(hop >= 1 && hop <= n_fft, "hop %d out of range for n_fft %d", hop, n_fft);
+    return FSN_OK;
+}
+
+extern "C" int fsn_stft(const float* y, int B, int L, int n_fft, int hop, int win_length, const float* window,
+                        float* real, float* imag, float* mag, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_fft_generic(n_fft, hop, win_length));
+    FSN_REQUIRE(y && window, "NULL pointer argument");
+    FSN_REQUIRE(B >= 1 && L > n_fft / 2, "need B >= 1 and L > n_fft/2 (reflect padding), got B=%d L=%d", B, L);
+    const int T = 1 + L / hop, F = n_fft / 2 + 1;
+    FSN_REQUIRE((long)B * T <= 0x7fffffffL, "too many frames");
+    if (!fast_fft(n_fft, hop))
+        return fsn_launch_dft_stft(y, B, L, window, real, imag, mag, T, n_fft, hop, static_cast<hipStream_t>(stream));
+    return fsn_launch_stft(y, B, L, window, real, imag, mag, T, T, F, fsn_fpad(F), false,
+                           static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t fsn_istft_workspace_bytes(int B, int T, int n_fft) {
+    if (B < 1 || T < 1 || n_fft < 16 || n_fft > 4096 || n_fft % 2) return 0;
+    return fsn_round_up_sz((size_t)B * T * n_fft * sizeof(float), 256);
+}
+
+extern "C" int fsn_istft(const float* real, const float* imag, int B, int T, int n_fft, int hop, int win_length,
+                         const float* window, int length, float* y, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_fft_generic(n_fft, hop, win_length));
+    FSN_TRY(check_bt(B, T));
+    FSN_REQUIRE(real && imag && window && y && workspace, "NULL pointer argument");
+    FSN_REQUIRE(length >= 1, "length %d < 1", length);
+    if (workspace_bytes < fsn_istft_workspace_bytes(B, T, n_fft)) {
+        fsn_set_error("workspace too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int F = n_fft / 2 + 1;
+    float* wf = static_cast<float*>(workspace);
+    if (!fast_fft(n_fft, hop)) return fsn_launch_dft_istft(real, imag, window, wf, y, B, T, n_fft, hop, length, s);
+    FSN_TRY(fsn_launch_mask_irfft(real, imag, nullptr, nullptr, B, T, F, fsn_fpad(F), false, window, wf, s));
+    return fsn_launch_ola(wf, window, B, T, length, y, s);
+}
+
+// ragged batches in the reference layout: 512 / 256 only (the radix-8 kernels' lengths path)
+extern "C" int fsn_stft_ragged(const float* y, const int* lengths, int B, int L_max, int n_fft, int hop, int win_length,
+                               const float* window, float* real, float* imag, float* mag, void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(fast_fft(n_fft, hop) && win_length == n_fft,
+                "fsn_stft_ragged: only n_fft = win_length = 512, hop = 256 is built (got %d/%d/%d)", n_fft, win_length, hop);
+    FSN_REQUIRE(y && lengths && window, "NULL pointer argument");
+    FSN_REQUIRE(B >= 1 && L_max > n_fft / 2, "need B >= 1 and L_max > n_fft/2 (reflect padding), got B=%d L_max=%d", B, L_max);
+    const int T = 1 + L_max / hop, F = n_fft / 2 + 1;
+    FSN_REQUIRE((long)B * T <= 0x7fffffffL, "too many frames");
+    return fsn_launch_stft(y, B, L_max, window, real, imag, mag, T, T, F, fsn_fpad(F), false, static_cast<hipStream_t>(stream),
+                           lengths);
+}
+
+extern "C" size_t fsn_mask_istft_workspace_bytes(int B, int T, int n_fft) {
+    if (B < 1 || T < 1 || n_fft != 512) return 0;
+    return fsn_istft_workspace_bytes(B, T, n_fft);
+}
+
+// inferencer.py:134-141 on a model's output: decompress_cIRM + complex mask + iSTFT, the [B][2][F][T] mask read in place
+extern "C" int fsn_mask_istft(const float* crm, const float* real, const float* imag, const int* lengths, int B, int F, int T,
+                              int n_fft, int hop, int win_length, const float* window, int length, float* y, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(fast_fft(n_fft, hop) && win_length == n_fft,
+                "fsn_mask_istft: only n_fft = win_length = 512, hop = 256 is built (got %d/%d/%d)", n_fft, win_length, hop);
+    FSN_TRY(check_bt(B, T));
+    FSN_REQUIRE(F == n_fft / 2 + 1, "fsn_mask_istft: F = %d, need n_fft / 2 + 1 = %d", F, n_fft / 2 + 1);
+    FSN_REQUIRE(crm && real && imag && window && y && workspace, "NULL pointer argument");
+    FSN_REQUIRE(length >= 1, "length %d < 1", length);
+    FSN_REQUIRE(!lengths || (length > n_fft / 2 && T == 1 + length / hop),
+                "fsn_mask_istft: with lengths, need length > n_fft/2 and T = 1 + length / hop (got length %d, T %d)", length, T);
+    if (workspace_bytes < fsn_mask_istft_workspace_bytes(B, T, n_fft)) {
+        fsn_set_error("workspace too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* wf = static_cast<float*>(workspace);
+    FSN_TRY(fsn_launch_mask_irfft(real, imag, crm, crm + (size_t)F * T, B, T, F, fsn_fpad(F), false, window, wf, s, lengths,
+                                  2L * F * T));
+    return fsn_launch_ola(wf, window, B, T, length, y, s, lengths);
+}
+
+// ---- elementwise boundary --------------------------------------------------------------------
+extern "C" int fsn_decompress_cirm(const float* mask, float* out, size_t n, void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(mask && out, "NULL pointer argument");
+    return n ? fsn_launch_decompress(mask, out, n, static_cast<hipStream_t>(stream)) : FSN_OK;
+}
+extern "C" int fsn_compress_cirm(const float* mask, float* out, size_t n, void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(mask && out, "NULL pointer argument");
+    return n ? fsn_launch_compress(mask, out, n, static_cast<hipStream_t>(stream)) : FSN_OK;
+}
+extern "C" int fsn_build_cirm(const float* nr, const float* ni, const float* cr, const float* ci, float* out,
+                              size_t n, void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(nr && ni && cr && ci && out, "NULL pointer argument");
+    return n ? fsn_launch_build_cirm(nr, ni, cr, ci, out, n, static_cast<hipStream_t>(stream)) : FSN_OK;
+}
+
+// ---- the whole path: inferencer.py:130-145 ---------------------------------------------------
+extern "C" size_t fsn_enhance_workspace_bytes(const fsn_fullsubnet_cfg* cfg, int B, int L, int n_fft, int hop) {
+    if (check_cfg(cfg) != FSN_OK || check_fft(n_fft, hop, n_fft) != FSN_OK || B < 1 || L <= n_fft / 2) return 0;
+    const int T = 1 + L / hop;
+    if (check_bt(B, T) != FSN_OK || cfg->num_freqs != n_fft / 2 + 1) return 0;
+    const CoreDims d = core_dims(cfg, B, T);
+    Carver cv(nullptr);
+    cv.take<float>((size_t)B * d.Tp * d.FP);  // magT
+    cv.take<float>((size_t)B * d.T * d.FP);   // re
+    cv.take<float>((size_t)B * d.T * d.FP);   // im
+    cv.take<float>((size_t)B * d.T * d.FP);   // crm_r
+    cv.take<float>((size_t)B * d.T * d.FP);   // crm_i
+    cv.take<float>((size_t)B * d.T * n_fft);  // windowed frames
+    Carver whole(nullptr), parts(nullptr);
+    core_carve(whole, d, cfg->norm_type);
+    core_carve_chunks(parts, cfg, B, T);
+    cv.take<char>(whole.off > parts.off ? whole.off : parts.off);
+    return fsn_round_up_sz(cv.off, 256);
+}
+
+// fsn_enhance and fsn_enhance_ragged: lengths == NULL is the rectangular batch
+static int enhance(const fsn_fullsubnet_cfg* cfg, const void* packed, const float* window, const float* noisy,
+                   const int* lengths, int B, int L, int n_fft, int hop, float* enhanced, float* crm_out, void* workspace,
+                   size_t workspace_bytes, hipStream_t s) {
+    FSN_TRY(check_cfg(cfg));
+    FSN_TRY(check_fft(n_fft, hop, n_fft));
+    FSN_REQUIRE(packed && window && noisy && enhanced && workspace, "NULL pointer argument");
+    FSN_REQUIRE(B >= 1 && L > n_fft / 2, "need B >= 1 and L > n_fft/2, got B=%d L=%d", B, L);
+    FSN_REQUIRE(cfg->num_freqs == n_fft / 2 + 1, "num_freqs %d != n_fft/2+1", cfg->num_freqs);
+    const int T = 1 + L / hop;
+    FSN_TRY(check_bt(B, T));
+    const size_t need = fsn_enhance_workspace_bytes(cfg, B, L, n_fft, hop);
+    if (workspace_bytes < need) {
+        fsn_set_error("workspace too small: %zu < %zu bytes", workspace_bytes, need);
+        return FSN_ERR_WORKSPACE;
+    }
+    const CoreDims d = core_dims(cfg, B, T);
+    Carver cv(workspace);
+    float* magT = cv.take<float>((size_t)B * d.Tp * d.FP);
+    float* re = cv.take<float>((size_t)B * d.T * d.FP);
+    float* im = cv.take<float>((size_t)B * d.T * d.FP);
+    float* crm_r = cv.take<float>((size_t)B * d.T * d.FP);
+    float* crm_i = cv.take<float>((size_t)B * d.T * d.FP);
+    float* wf = cv.take<float>((size_t)B * d.T * n_fft);
+    void* scratch = cv.take<char>(0);  // the rest: the core's scratch (fsn_enhance_workspace_bytes)
+    prof_reset();
+    {
+        StageTimer st(ST_STFT, s);
+        FSN_TRY(fsn_launch_stft(noisy, B, L, window, re, im, magT, d.T, d.Tp, d.F, d.FP, true, s, lengths));
+    }
+    FSN_TRY(run_core_chunks(cfg, static_cast<const float*>(packed), magT, B, T, scratch, crm_r, crm_i, s, lengths));
+    {
+        StageTimer st(ST_MASK_ISTFT, s);
+        FSN_TRY(fsn_launch_mask_irfft(re, im, crm_r, crm_i, B, d.T, d.F, d.FP, true, window, wf, s, lengths));
+        FSN_TRY(fsn_launch_ola(wf, window, B, d.T, L, enhanced, s, lengths));
+    }
+    if (crm_out) {
+        FSN_TRY(fsn_launch_transpose(crm_r, crm_out, B, d.T, d.F, d.FP, (long)d.T * d.FP, d.T, 2L * d.F * d.T, d.T,
+                                     d.F, s, lengths));
+        FSN_TRY(fsn_launch_transpose(crm_i, crm_out + (size_t)d.F * d.T, B, d.T, d.F, d.FP, (long)d.T * d.FP, d.T,
+                                     2L * d.F * d.T, d.T, d.F, s, lengths));
+    }
+    return FSN_OK;
+}
+
+extern "C" int fsn_enhance(const fsn_fullsubnet_cfg* cfg, const void* packed, const float* window,
+                           const float* noisy, int B, int L, int n_fft, int hop, float* enhanced, float* crm_out,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    return enhance(cfg, packed, window, noisy, nullptr, B, L, n_fft, hop, enhanced, crm_out, workspace, workspace_bytes,
+                   static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fsn_enhance_ragged(const fsn_fullsubnet_cfg* cfg, const void* packed, const float* window,
+                                  const float* noisy, const int* lengths, int B, int L_max, int n_fft, int hop,
+                                  float* enhanced, float* crm_out, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(lengths, "NULL pointer argument");
+    return enhance(cfg, packed, window, noisy, lengths, B, L_max, n_fft, hop, enhanced, crm_out, workspace,
+                   workspace_bytes, static_cast<hipStream_t>(stream));
+}

@@ -38,6 +38,15 @@ def test_library_exports_every_declared_symbol():
     assert L.fsn_version() >= 100
     names = _lib.profile_stage_names()
     assert "sb_rec_l1" in names and len(names) == L.fsn_profile_num_stages()
+    # ... and nothing else: launchers, kernel stubs and helpers stay internal (csrc/fsn_exports.map)
+    import subprocess
+    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"  # tools/so_kernel_resources.py's READELF
+    if not os.path.exists(readelf):
+        pytest.skip("llvm-readelf not available")
+    out = subprocess.run([readelf, "--dyn-syms", "--wide", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    defined = sorted({f[7].split("@")[0] for f in (line.split() for line in out.splitlines())
+                      if len(f) >= 8 and f[0].endswith(":") and f[6] != "UND" and f[4] in ("GLOBAL", "WEAK")})
+    assert defined == header_symbols(), sorted(set(defined) ^ set(header_symbols()))[:20]
 
 
 def test_argument_validation_without_a_gpu():

@@ -19,7 +19,7 @@ def main():
     subprocess.run(["/opt/rocm/bin/hipcc"] + b.FLAGS + flags + ["-c", os.path.join(b.CSRC, tu), "-o", obj], check=True)
     objs = [obj if s == tu else b._obj(s) for s in b._sources()]
     so = os.path.join(out, f"{name}.so")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", so], check=True)
+    subprocess.run(["/opt/rocm/bin/hipcc"] + b.LINK_FLAGS + objs + ["-o", so], check=True)
     print(so)
 
 
