@@ -601,8 +601,15 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
     const long r0 = (long)blockIdx.y * rows_per_block;
     long r1 = r0 + rows_per_block;
     r1 = r1 < rows ? r1 : rows;
+    // two levels, chains of 64 rows: one chain of 2048 made the sum of 2^20 rows four times less accurate than a blocked
+    // CPU sum (tests/test_gpu_linear_sweep.py); up to 64 rows per block (every shipped shape) the bits are the same
     float acc = 0.f;
-    for (long r = r0; r < r1; ++r) acc += A[r * lda + c];
+    for (long rc = r0; rc < r1; rc += 64) {
+        const long re = rc + 64 < r1 ? rc + 64 : r1;
+        float a = 0.f;
+        for (long r = rc; r < re; ++r) a += A[r * lda + c];
+        acc += a;
+    }
     part[(long)blockIdx.y * cols + c] = acc;
 }
 
@@ -1099,7 +1106,13 @@ int fsn_launch_gemm_tn16n(const void* A16, long lda, const void* B16, long ldb, 
     const long K32 = K & ~31L;
     const int m_blocks = M / 384;
     long splits = cus / m_blocks > 1 ? cus / m_blocks : 1;
+    // the partials take 32 columns per split whatever Nc is, while the workspace query counts Nc + 1: with a small Nc on a
+    // device of few CUs not even one partial fits
     const long bound = (long)(fsn_gemm_tn_workspace_bytes(M, Nc, K) / ((size_t)M * 32 * sizeof(float)));
+    if (bound < 1) {
+        fsn_set_error("gemm_tn16n: the workspace of a %d x %d product holds no %d x 32 partial", M, Nc, M);
+        return FSN_ERR_WORKSPACE;
+    }
     splits = splits < bound ? splits : bound;
     const long kps = ((K32 + splits - 1) / splits + 31) / 32 * 32;
     splits = (K32 + kps - 1) / kps;

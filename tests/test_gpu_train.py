@@ -294,6 +294,22 @@ def test_linear_forward_backward(fsn, R, I, O, relu):
     assert (yd.detach().cpu() - yo.detach()).abs().max().item() <= 1e-4
     for a, r in ((xd.grad, xo.grad), (wd.grad, wo.grad), (bd.grad, bo.grad)):
         assert (a.cpu() - r).abs().max().item() <= 1e-4 * max(r.abs().max().item(), 1.0)
+    # on top: every element against the fp64 product, with the two bounds of the shape sweep (test_gpu_linear_sweep.py).
+    # The backward saw dy behind the ReLU of the HIP result, so that is the operand of the reference products too.
+    import test_gpu_linear_sweep as S
+    row = S.Row("train", R, I, O)
+    yh = yd.detach().cpu()
+    ops = dict(x=x, w=w, b=b, dy=dy * (yh > 0) if relu else dy)
+    cpu = S.cpu_products(ops)
+    stats = S.new_stats(row, S.tn_splits(fsn._lib.lib(), row))
+    S.check_outputs(stats, ops, dict(dx=xd.grad.cpu(), dw=wd.grad.cpu(), db=bd.grad.cpu()), cpu)
+    y64 = x.double() @ w.double().t() + b.double()
+    stats["y"].add(yh, torch.relu(y64) if relu else y64, x.double().abs() @ w.double().abs().t() + b.double().abs(),
+                   torch.relu(cpu["y"]) if relu else cpu["y"])
+    for s in stats.values():
+        print(f"[linear] {row.id} {s.name}: n {s.n} hard {s.hard:.4f} rms hip {s.rms('hip'):.4f} u cpu {s.rms('cpu'):.4f} u")
+    for s in stats.values():
+        s.assert_rounding()
 
 
 def test_train_step_torch_optimizer_path(fsn, golden_dir):
