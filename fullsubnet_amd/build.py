@@ -11,11 +11,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libfsn_hip.so")
-HEADERS = [os.path.join(CSRC, "fsn_common.h"), os.path.join(CSRC, "fsn_api_internal.h"),
+HEADERS = [os.path.join(CSRC, "fsn_common.h"), os.path.join(CSRC, "fsn_api_internal.h"), os.path.join(CSRC, "lstm_cell.h"),
            os.path.join(HERE, "..", "include", "fsn_hip.h")]
 EXPORTS = os.path.join(CSRC, "fsn_exports.map")  # the library exports the fsn_* entries of fsn_hip.h and nothing else
 SOURCES = ["fft_kernels.hip", "dft_kernels.hip", "elementwise_kernels.hip", "gemm_kernels.hip",
-           "gemm_f16x3_kernels.hip", "lstm_kernels.hip", "lstm_group_kernels.hip",
+           "gemm_f16x3_kernels.hip", "lstm_rec_kernels.hip", "lstm_rec_in_kernels.hip", "lstm_rec_x_kernels.hip",
+           "lstm_step_kernels.hip", "lstm_group_kernels.hip",
            "lstm_group_bptt_kernels.hip", "lstm_group16_kernels.hip", "fb_chain_kernels.hip", "fb_chain_bptt_kernels.hip",
            "lstm_f16x3_kernels.hip", "lstm_train_kernels.hip", "gru_kernels.hip", "optim_kernels.hip",
            "norm_kernels.hip", "section_kernels.hip", "train_glue_kernels.hip", "fast_glue_kernels.hip",

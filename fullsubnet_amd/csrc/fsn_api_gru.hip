@@ -69,7 +69,7 @@ extern "C" size_t fsn_gru_layer_save_bytes(int T, int N, int H) {
 }
 // Many rows in inference (the sub-band model of a GRU FullSubNet: B F rows, audio_zen/model/module/sequence_model.py:59-66
 // under fullsubnet/model.py:121-128): the layer runs on the LSTM's persistent kernels with the GRU written as a four-gate
-// cell (FSN_REC_GRU, lstm_kernels.hip) - lstm_rec_in_kernel for a narrow row-major input (<= 32 columns: the projection is
+// cell (lstm_cell.h) - lstm_rec_in_kernel for a narrow row-major input (<= 32 columns: the projection is
 // formed inside), lstm_rec_x_kernel for the layer above an equally wide one (input = its hidden sequence, no projection
 // GEMM, no gx round trip).  Whole rounds of 2 - 4 row tiles per workgroup; the few left-over tiles advance step by step
 // on the auxiliary stream beside the persistent launch, on compact copies of their rows.

@@ -109,13 +109,6 @@ struct Carver {
     }
 };
 
-// CU count of the current device for the plans; 256 if the query fails or returns < 1.
-inline int plan_cus() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus < 1 ? 256 : cus;
-}
-
 // ---- FullSubNet model (fsn_api_fullsubnet.hip) ----------------------------------------------------------------------
 // below this many sub-band row tiles (batch <= 5) the two layers of the small-batch step path run as a wavefront of
 // per-step launches; from here up to the persistent regime (160 tiles) they run on the group kernel

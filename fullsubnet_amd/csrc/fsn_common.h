@@ -227,6 +227,13 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblk) {
     return base + slot;
 }
 
+// CU count of the current device for the plans; 256 if the query fails or returns < 1.
+inline int plan_cus() {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus < 1 ? 256 : cus;
+}
+
 // ---- kernels' host launchers (one per translation unit) -------------------------------------
 struct FsnStream {
     hipStream_t s;
@@ -419,7 +426,7 @@ int fsn_launch_fb_chain(const float* gx0, const float* whh0_p, const float* wih1
                         float* hseq0 = nullptr, float* save0 = nullptr, float* save1 = nullptr, int cell = 0);
 // gru_kernels.hip: nn.GRU's [3H] gate rows (r, z, n) of one layer as the FOUR-gate cell the chain kernel runs (r | z | nx | nh):
 // w_ih4 [4H][I] = W_ir; W_iz; W_in; 0   w_hh4 [4H][H] = W_hr; W_hz; 0; W_hn   b4 [4H] = b_ir + b_hr; b_iz + b_hz; b_in; b_hn
-// order 1: the gate slots of the many-row persistent kernels (lstm_kernels.hip, FSN_REC_GRU): nh | r | nx | z
+// order 1: the gate slots of the many-row persistent kernels (lstm_cell.h): nh | r | nx | z
 int fsn_launch_gru_expand4(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* w_ih4, float* w_hh4,
                            float* b4, int I, int H, hipStream_t s, int order = 0);
 
@@ -453,7 +460,7 @@ int fsn_launch_gru_bptt_step(const float* dh_out, const float* dgx_next, const f
                              float* carry, const float* save, const float* h_prev, float* dgx, float* dghn,
                              int row_tiles, int H, int last, int first, hipStream_t s);
 
-// lstm_kernels.hip
+// lstm_rec_kernels.hip, lstm_rec_in_kernels.hip, lstm_rec_x_kernels.hip, lstm_step_kernels.hip
 // Sub-band model input (fullsubnet/model.py:98-111) for kernels that build it on the fly:
 // channel c < 2nb+1 of unit n = b F + f at frame t is mag[b][t][reflect(f + c - nb)], channel 2nb+1
 // is fb_out[b][t][f]; everything divided by den (den_mode 0: den[b], 1: den[t * den_stride + n]).

@@ -239,8 +239,7 @@ int fsn_launch_gemm_f16x3(const float* A, long lda, const void* packed, const fl
         }
         attr_set = true;
     }
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = plan_cus();
     const f16x8* whi = static_cast<const f16x8*>(packed);
     const f16x8* wlo = whi + (size_t)n_out * k / 8;
     hipLaunchKernelGGL(gemm_f16x3_lds_kernel, dim3(cus), dim3(512), lds, s, A, lda, whi, wlo, bias, C, row_tiles,

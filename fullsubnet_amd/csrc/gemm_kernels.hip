@@ -325,8 +325,7 @@ int launch(const FsnGemmA& a, const float* wp, const FsnGemmC& c, int row_tiles,
             n = 1;
         occ = n;
     }
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = plan_cus();
     long grid = (long)cus * (wg_per_cu > 0 ? wg_per_cu : occ);
     if (grid > nrb * ncb) grid = nrb * ncb;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WR * WC * 64), lds_reserve, s, a, wp, c, row_tiles,

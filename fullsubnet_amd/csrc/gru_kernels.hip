@@ -2,7 +2,7 @@
 // unidirectional, h0 = 0.  PyTorch's cell (gate rows r, z, n of weight_ih / weight_hh):
 //   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr)        z = sigmoid(W_iz x + b_iz + W_hz h + b_hz)
 //   n = tanh(W_in x + b_in + r * (W_hn h + b_hn))     h' = n + z * (h - n)
-// Same execution shape as the LSTM step kernels (lstm_kernels.hip / lstm_train_kernels.hip): the input
+// Same execution shape as the LSTM step kernels (lstm_step_kernels.hip / lstm_train_kernels.hip): the input
 // projection of all steps is one GEMM (fragment-ordered gx, bias = b_ih + [b_hr, b_hz, 0]); each step is
 // one launch whose workgroups own RTS 16-row tiles x one 16-unit group x the three gates, 4 waves =
 // 4-way split-K reduced through LDS in a fixed order.  Training keeps r, z, n and hn = W_hn h + b_hn.
@@ -97,8 +97,8 @@ __global__ __launch_bounds__(256) void gru_step_kernel(const float* __restrict__
     }
 }
 
-// The same step for the left-over row tiles BESIDE a resident workgroup of the persistent many-row kernels (lstm_kernels.hip,
-// FSN_REC_GRU: 3 x 152 of a SIMD's 512 registers and up to 148 KB of a CU's 160 KB of LDS are taken): one row tile per
+// The same step for the left-over row tiles BESIDE a resident workgroup of the persistent many-row kernels (lstm_rec_in_kernels.hip /
+// lstm_rec_x_kernels.hip, GRU form: 3 x 152 of a SIMD's 512 registers and up to 148 KB of a CU's 160 KB of LDS are taken): one row tile per
 // workgroup, at most 48 registers, 6 KB of LDS - the split-K partial sums travel in two rounds (gates r and z, then the n gate's
 // recurrent part) through one small buffer.  Same operations in the same order as gru_step_kernel<1>: bit-identical results.
 // (gru_step_kernel<1> itself takes 64 registers and 12 KB: its launches waited for the persistent launch to END - measured, a
@@ -299,7 +299,7 @@ int fsn_launch_gru_bptt_step(const float* dh_out, const float* dgx_next, const f
 }
 
 // nn.GRU's gate rows as a four-gate cell (fb_chain_kernel<.., CELL = 1>, fsn_gru2_forward: slots r | z | nx | nh; the many-row
-// persistent kernels, FSN_REC_GRU in lstm_kernels.hip: slots nh | r | nx | z - `order` 1)
+// persistent kernels, the GRU cell of lstm_cell.h: slots nh | r | nx | z - `order` 1)
 namespace {
 __global__ void gru_expand4_kernel(const float* __restrict__ w_ih, const float* __restrict__ w_hh, const float* __restrict__ b_ih,
                                    const float* __restrict__ b_hh, float* __restrict__ w_ih4, float* __restrict__ w_hh4,

@@ -2,7 +2,7 @@
 // both LSTM layers and the output layer as ONE persistent launch in which clusters of workgroups share a group of 64
 // rows (fullsubnet/model.py:121-128: the rows are independent sequences).
 //
-// Why: with ~8 rows per CU the persistent kernels of lstm_kernels.hip cannot be used - a workgroup that owns rows
+// Why: with ~8 rows per CU the persistent kernels of lstm_rec*_kernels.hip cannot be used - a workgroup that owns rows
 // must stream ALL of W_hh (2.4 MB) from L2 every step whatever its row count, which bounds a step at ~31 us - so
 // this regime ran as one launch per step and layer (hidden units x row tiles spread over all CUs, h and c through
 // L2): 29 us per step against 15 us of MFMA work (launch boundary, cold operand fetches, drain), plus a separate

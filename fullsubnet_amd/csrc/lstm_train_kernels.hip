@@ -645,8 +645,7 @@ struct TnPlan {
 // workgroup per CU (or as close below it as the tile count allows).
 TnPlan tn_plan(int M, int Nc, long K, int arith = FSN_ARITH_F32, bool allow_square = true) {
     TnPlan p;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = plan_cus();
     p.narrow = Nc <= 32;
     p.square = 0;
     (void)arith;  // every arithmetic: in fp32 the square plan is worth 0.3 ms of a 42 ms step, under the 16-bit one 1 ms per GEMM
@@ -873,8 +872,7 @@ static long colsum_rows_per_block(int cols, long rows) {
 // workgroup per CU over 256 x 128 tiles, or over 192 x 192 tiles).  fsn_launch_gemm_tn refuses a plan beyond it.
 static long tn_max_splits(int M, int Nc) {
     const bool swap = M <= 32 && Nc > 32;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = plan_cus();
     const int m = swap ? Nc : M, n = swap ? M : Nc;
     const bool narrow = n <= 32;
     const long tiles = narrow ? (long)((m + 511) / 512) * ((n + 31) / 32) : (long)((m + 255) / 256) * ((n + 127) / 128);
@@ -1007,8 +1005,7 @@ static int g_tn16h_wide = 1;  // fsn_tn16h_wide(0): the 192 x 192 tiles also whe
 void fsn_tn16h_wide(int on) { g_tn16h_wide = on; }
 // the 192 x 384 form: Nc a multiple of 384, whole K splits per XCD with one (eight-wave) workgroup per CU
 static bool tn16h_wide_plan(int M, int Nc, long K32, TnPlan* out) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = plan_cus();
     if (!g_tn16h_wide || M % 192 || Nc % 384 || cus % 8) return false;
     const int tiles = (M / 192) * (Nc / 384);
     if ((cus / 8) % tiles) return false;
@@ -1101,8 +1098,7 @@ int fsn_launch_gemm_tn16n(const void* A16, long lda, const void* B16, long ldb, 
         fsn_set_error("gemm_tn16n: 16-bit arithmetic, M a multiple of 384, Nc <= 32 in rows of >= 32 16-bit columns, 16-byte aligned rows");
         return FSN_ERR_ARG;
     }
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = plan_cus();
     const long K32 = K & ~31L;
     const int m_blocks = M / 384;
     long splits = cus / m_blocks > 1 ? cus / m_blocks : 1;
@@ -1155,8 +1151,7 @@ int fsn_launch_gemm_dx16(const void* dg16, long ld16, const float* w, void* wfra
     const int KB = G / 32;
     const size_t lds = (size_t)KB * 2 * 1024;
     unsigned short* wf = static_cast<unsigned short*>(wfrag);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = plan_cus();
     const long tiles = rows / 16;
     const unsigned grid = (unsigned)((tiles + 3) / 4 < cus ? (tiles + 3) / 4 : cus);
     if (arith == FSN_ARITH_F16) {
@@ -1211,7 +1206,7 @@ int fsn_launch_colsum(const float* A, long lda, float* out, int cols, long rows,
     return fsn_check_launch("reduce_splits_kernel");
 }
 
-// The BPTT step in the one-workgroup-per-CU shape of lstm_step_cu_kernel (lstm_kernels.hip), for row counts that
+// The BPTT step in the one-workgroup-per-CU shape of lstm_step_cu_kernel (lstm_step_kernels.hip), for row counts that
 // fill the chip at least once (used from 192 row tiles): a workgroup = four row tiles x CTW
 // column tiles of dh_rec = dgates_{t+1} W_hh, one row tile per wave, the whole K = 4H range per wave (no split-K
 // exchange).  A stage is four K chunks: wave w fetches chunk w's CTW weight fragments for everybody (two-stage LDS

@@ -1,6 +1,6 @@
 """nn.GRU with MANY rows in inference - the sub-band model of a GRU FullSubNet (audio_zen/model/module/sequence_model.py:59-66
 under fullsubnet/model.py:121-128) - on the LSTM's persistent many-row kernels with the GRU written as a four-gate cell
-(FSN_REC_GRU in lstm_kernels.hip, fsn_gru_layer_forward since ABI 117), through the C ABI:
+(the GRU form of lstm_rec_in_kernel / lstm_rec_x_kernel, lstm_cell.h; fsn_gru_layer_forward since ABI 117), through the C ABI:
 
 * against torch's nn.GRU on the CPU (fp32) and against the library's own per-step path, layer forms x row-tile counts, with and
   without left-over row tiles;

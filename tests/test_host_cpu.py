@@ -225,15 +225,17 @@ def test_leftover_step_kernel_fits_next_to_persistent_kernel(tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    out = tmp_path / "lstm.s"
     flags = [f for f in b.FLAGS if f not in ("-shared", "-fPIC")]
-    subprocess.run([hipcc] + flags + ["-S", "--cuda-device-only", os.path.join(b.CSRC, "lstm_kernels.hip"), "-o", str(out)],
-                   check=True, capture_output=True)
     meta = {}
-    for blk in out.read_text().split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
-                      for k in ("vgpr_count", "group_segment_fixed_size", "vgpr_spill_count")}
+    # the files that hold lstm_step1_kernel, lstm_rec_kernel and lstm_rec_x_kernel, each compiled stand-alone
+    for src in ("lstm_step_kernels.hip", "lstm_rec_kernels.hip", "lstm_rec_x_kernels.hip"):
+        out = tmp_path / (src + ".s")
+        subprocess.run([hipcc] + flags + ["-S", "--cuda-device-only", os.path.join(b.CSRC, src), "-o", str(out)],
+                       check=True, capture_output=True)
+        for blk in out.read_text().split("- .agpr_count:")[1:]:
+            name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+            meta[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
+                          for k in ("vgpr_count", "group_segment_fixed_size", "vgpr_spill_count")}
     step = next(v for k, v in meta.items() if "lstm_step1_kernel" in k)
     recs = {k: v for k, v in meta.items() if "lstm_rec_kernelILi384ELi4ELi2E" in k}
     assert len(recs) == 2 and step["vgpr_spill_count"] == 0
@@ -273,12 +275,11 @@ def test_built_library_holds_the_same_budget():
         assert 3 * gran(rec["vgpr_count"]) + gran(step["vgpr_count"]) <= 512, (name, rec, step)
     recx = next(v for k, v in ks.items() if "lstm_rec_x_kernelILi384ELi4ELi2E" in k)
     assert 3 * gran(recx["vgpr_count"]) + gran(step["vgpr_count"]) <= 512 and recx["vgpr_spill_count"] <= 8, recx
-    # the GRU's left-over tiles beside the same kernels run as a four-gate cell (FSN_REC_GRU = 1 << 20 in their OPT / ABL
-    # parameter; gru_step1_kernel): every such instantiation x the step workgroup inside a SIMD's registers and a CU's LDS
+    # the GRU's left-over tiles beside the same kernels run as a four-gate cell (their fourth template parameter, GRU = true;
+    # gru_step1_kernel): every such instantiation x the step workgroup inside a SIMD's registers and a CU's LDS
     gstep = next(v for k, v in ks.items() if "gru_step1_kernel" in k)
     assert gstep["vgpr_spill_count"] == 0 and gstep["group_segment_fixed_size"] <= 8 * 1024, gstep
-    gru = {k: v for k, v in ks.items() if re.search(r"lstm_rec_(in|x)_kernelILi384ELi\dELi2ELi(\d+)E", k)
-           and int(re.search(r"lstm_rec_(?:in|x)_kernelILi384ELi\dELi2ELi(\d+)E", k).group(1)) & (1 << 20)}
+    gru = {k: v for k, v in ks.items() if re.search(r"lstm_rec_(in|x)_kernelILi384ELi\dELi2ELb1E", k)}
     assert len(gru) == 9, sorted(gru)  # rec_in: 2 - 4 row tiles x one / two input chunks; rec_x: 2 - 4 row tiles (hseq out)
     for name, rec in gru.items():
         assert 3 * gran(rec["vgpr_count"]) + gran(gstep["vgpr_count"]) <= 512 and rec["vgpr_spill_count"] <= 8, (name, rec, gstep)

@@ -1,10 +1,9 @@
-// Timing probe for lstm_rec_x_kernel (not part of the library): the shipped kernel and ablations that leave out one
-// ingredient at a time (template parameter ABL, see the kernel) to price it.
-#include <cmath>
+// Timing probe for lstm_rec_x_kernel (not part of the library): the shipped instantiations stand-alone at config 2's shape
+// (PROBE_RT row tiles per workgroup on 256 workgroups).  The ablations that priced the kernel's ingredients one at a time
+// are on record in profiles/r05_rec_probes.md.
 #include <cstdio>
 #include <cstdlib>
-#include <vector>
-#include "../fullsubnet_amd/csrc/lstm_kernels.hip"
+#include "../fullsubnet_amd/csrc/lstm_rec_x_kernels.hip"
 void fsn_set_error(const char*, ...) {}
 int fsn_check_launch(const char*) { return hipGetLastError() == hipSuccess ? 0 : -3; }
 FsnCallScope::FsnCallScope(void*) : prev(-1), switched(false) {}
@@ -19,11 +18,11 @@ __global__ void fill_kernel(float* p, size_t n, unsigned seed, float scale) {
 #define PROBE_RT 4
 #define PROBE_UG 2
 #endif
-template <int ABL>
+template <bool GRU, bool HSEQ>
 float run(const float* xseq, const float* w, const float* bias, int Tp, int Npad, const FsnRecFc& fc) {
     constexpr int H = 384, RT = PROBE_RT, UG = PROBE_UG, NW = H / (16 * UG);
     const size_t lds = ((size_t)RT * 16 * (H + 4) + 2 * H + (size_t)2 * RT * 6 * 256) * sizeof(float);
-    auto kern = lstm_rec_x_kernel<H, RT, UG, ABL>;
+    auto kern = lstm_rec_x_kernel<H, RT, UG, GRU, HSEQ>;
     hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     float best = 1e30f;
@@ -35,23 +34,12 @@ float run(const float* xseq, const float* w, const float* bias, int Tp, int Npad
     }
     return best;
 }
-static std::vector<float> g_ref;
-static float* g_out = nullptr;
-static size_t g_n = 0;
-// max |difference| of the output plane against the shipped kernel's (first call: remember it)
-static double check() {
-    std::vector<float> h(g_n);
-    hipMemcpy(h.data(), g_out, g_n * 4, hipMemcpyDeviceToHost);
-    if (g_ref.empty()) { g_ref = h; return 0.0; }
-    double m = 0.0;
-    for (size_t i = 0; i < g_n; ++i) { const double d = std::fabs((double)h[i] - (double)g_ref[i]); if (!(d <= m)) m = d; }
-    return m;
-}
 int main(int argc, char** argv) {
     const int Tp = argc > 1 ? atoi(argv[1]) : 190;
     const int H = 384, tiles = 1028, Npad = tiles * 16, F = 257, T = Tp - 2;
-    float *xseq, *w, *bias, *fcw, *fcb, *cr, *ci;
+    float *xseq, *w, *bias, *fcw, *fcb, *cr, *ci, *hseq;
     hipMalloc(&xseq, (size_t)Tp * Npad * H * 4);
+    hipMalloc(&hseq, (size_t)Tp * Npad * H * 4);
     hipMalloc(&w, (size_t)8 * H * H * 4);
     hipMalloc(&bias, 4 * H * 4);
     hipMalloc(&fcw, 16 * H * 4);
@@ -66,23 +54,16 @@ int main(int argc, char** argv) {
     hipDeviceSynchronize();
     FsnRecFc fc{};
     fc.w_p = fcw; fc.bias = fcb; fc.crm_r = cr; fc.crm_i = ci; fc.N = 64 * F; fc.F = F; fc.FP = 272; fc.T = T; fc.la = 2; fc.row0 = 0;
+    FsnRecFc out{};  // the hidden-sequence forms: the destination travels in crm_r
+    out.crm_r = hseq;
     const double flops = 2.0 * 256 * 64 * 768.0 * 1536 * Tp;
-    g_out = cr; g_n = (size_t)64 * T * 272;
-    hipMemset(cr, 0, g_n * 4);
-    const float t0 = run<0>(xseq, w, bias, Tp, Npad, fc);
-    check();
-    printf("lstm_rec_x_kernel<384,%d,%d> x %d workgroups: %.3f ms = %.1f TFLOP/s (ideal at 157.3: %.3f ms)\n", PROBE_RT, PROBE_UG, 256 * 4 / PROBE_RT, t0, flops / t0 / 1e9, flops / 157.3e9);
-#define VARIANT(NAME, BITS)                                                            \
-    {                                                                                  \
-        const float ms = run<BITS>(xseq, w, bias, Tp, Npad, fc);                       \
-        printf("  %-58s: %.3f ms   max |d| vs shipped %.3e\n", NAME, ms, check());     \
-    }
-    VARIANT("64 + 256 (round 5's first form)", 320)
-    VARIANT("+ 131072: ring fills behind the first row tile of a slice", 320 + 131072)
-    VARIANT("+ 524288: their addresses from scalar registers", 320 + 131072 + 524288)
-    VARIANT("+ 262144: output layer's tail without the 64-bit division", 320 + 131072 + 524288 + 262144)
-    VARIANT("+ 4096 (the library's form)", FSN_REC_X_OPT)
-    VARIANT("the library's form without ring fills (8)", FSN_REC_X_OPT + 8)
-    VARIANT("the library's form", FSN_REC_X_OPT)
+    printf("lstm_rec_x_kernel<384,%d,%d,..> x %d workgroups, %d steps (ideal at 157.3 TFLOP/s: %.3f ms)\n", PROBE_RT, PROBE_UG,
+           256 * 4 / PROBE_RT, Tp, flops / 157.3e9);
+    const float t_fc = run<false, false>(xseq, w, bias, Tp, Npad, fc);
+    printf("  %-44s: %.3f ms = %.1f TFLOP/s\n", "LSTM, fused output layer", t_fc, flops / t_fc / 1e9);
+    const float t_hs = run<false, true>(xseq, w, bias, Tp, Npad, out);
+    printf("  %-44s: %.3f ms = %.1f TFLOP/s\n", "LSTM, hidden sequence out", t_hs, flops / t_hs / 1e9);
+    const float t_gru = run<true, true>(xseq, w, bias, Tp, Npad, out);  // 3/4 of the LSTM's matrix work
+    printf("  %-44s: %.3f ms = %.1f TFLOP/s\n", "GRU (four-gate cell), hidden sequence out", t_gru, 0.75 * flops / t_gru / 1e9);
     return 0;
 }
