@@ -558,13 +558,13 @@ __global__ void tn16h_reduce_kernel(const float* __restrict__ part, float* __res
 
 // column sums riding on gemm_tn: sum of the split partials (fixed order) + the K % 16 tail rows
 __global__ void tn_colsum_reduce_kernel(const float* __restrict__ asum_part, float* __restrict__ out, int M, int splits,
-                                        const float* __restrict__ A, long lda, long k_tail0, long K) {
+                                        const float* __restrict__ A, long lda, long k_tail0, long K, int accumulate) {
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= M) return;
     float acc = 0.f;
     for (int s = 0; s < splits; ++s) acc += asum_part[(long)s * M + m];
     for (long k = k_tail0; k < K; ++k) acc += A[k * lda + m];
-    out[m] = acc;
+    out[m] = accumulate ? out[m] + acc : acc;  // a later K segment: onto the sum of the earlier ones
 }
 
 // out[i] = sum_s part[s][i] in a fixed order
@@ -581,7 +581,7 @@ __global__ void reduce_splits_kernel(const float* __restrict__ part, float* __re
 // does not cover; `transposed`: the partials hold C^T ([Nc][M], operands were swapped).
 __global__ void tn_reduce_kernel(const float* __restrict__ part, float* __restrict__ C, long ldc, int M, int Nc,
                                  int splits, int transposed, const float* __restrict__ A, long lda,
-                                 const float* __restrict__ B, long ldb, long k_tail0, long K) {
+                                 const float* __restrict__ B, long ldb, long k_tail0, long K, int accumulate) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)M * Nc) return;
     const int m = (int)(i / Nc), n = (int)(i % Nc);
@@ -589,7 +589,7 @@ __global__ void tn_reduce_kernel(const float* __restrict__ part, float* __restri
     float acc = 0.f;
     for (int s = 0; s < splits; ++s) acc += part[(long)s * M * Nc + pi];
     for (long k = k_tail0; k < K; ++k) acc += A[k * lda + m] * B[k * ldb + n];
-    C[(long)m * ldc + n] = acc;
+    C[(long)m * ldc + n] = accumulate ? C[(long)m * ldc + n] + acc : acc;  // a later K segment (fsn_launch_gemm_tn)
 }
 
 // partial column sums over blocks of rows: part[rb][c] = sum_{r in block rb} A[r][c]
@@ -887,8 +887,8 @@ static long tn_max_splits(int M, int Nc) {
     }
     return splits;
 }
-// test hook (fsn_debug_tn_plan): the K splits fsn_launch_gemm_tn would take for this product and the bound its scratch is
-// sized by
+// test hook (fsn_debug_tn_plan): the K splits of the product's plan and the bound its scratch is sized by.  A product that
+// fsn_launch_gemm_tn forms in K segments (kTnLongChain) launches each segment with its own plan of at most that bound
 void fsn_tn_plan_splits(int M, int Nc, long K, int arith, int* splits, long* bound) {
     const bool swap = M <= 32 && Nc > 32;
     const long K16 = K & ~15L;
@@ -901,25 +901,13 @@ size_t fsn_gemm_tn_workspace_bytes(int M, int Nc, long K) {
     return (size_t)tn_max_splits(M, Nc) * M * (Nc + 1) * sizeof(float);  // + one column-sum row per split
 }
 
-// colsum_out (may be NULL): also out[m] = sum_k A[k][m], from the same pass over A (not with a narrow M)
-int fsn_launch_gemm_tn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int Nc, long K,
-                       void* workspace, hipStream_t s, float* colsum_out, int arith) {
-    if (arith != FSN_ARITH_F32 && arith != FSN_ARITH_F16 && arith != FSN_ARITH_BF16) {
-        fsn_set_error("gemm_tn: arithmetic %d unknown", arith);
-        return FSN_ERR_ARG;
-    }
-    if (K <= 0 || lda * 16 > 0x7fffffffL || ldb * 16 > 0x7fffffffL) {
-        fsn_set_error("gemm_tn: bad K = %ld or leading dimension", K);
-        return FSN_ERR_ARG;
-    }
-    // a narrow M (the 2-row dW of the sub-band output layer) goes on the narrow side of the tile
-    const bool swap = M <= 32 && Nc > 32;
-    if (swap && colsum_out) {
-        fsn_set_error("gemm_tn: fused column sums are not available for M <= 32");
-        return FSN_ERR_ARG;
-    }
-    const long K16 = K & ~15L;
-    float* part = static_cast<float*>(workspace);
+constexpr long kTnLongChain = 4096;  // rows per K split from which fsn_launch_gemm_tn forms the product in K segments ...
+constexpr long kTnSegChain = 2048;   // ... of this many rows per split
+// One K segment of fsn_launch_gemm_tn: rows [0, K16) of A / B (K16 a multiple of 16, may be 0) through the MFMA kernel, the split
+// partials summed into C (`accumulate`: onto an earlier segment's sum) together with rows [k_tail0, K_all) of A_all / B_all.
+static int gemm_tn_segment(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int Nc, long K16,
+                           float* part, hipStream_t s, float* colsum_out, int arith, bool swap, bool accumulate,
+                           const float* A_all, const float* B_all, long k_tail0, long K_all) {
     float* asum_part = nullptr;
     int splits = 0;
     if (K16 > 0) {
@@ -988,12 +976,61 @@ int fsn_launch_gemm_tn(const float* A, long lda, const float* B, long ldb, float
     }
     const long n = (long)M * Nc;
     hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, C, ldc, M, Nc, splits,
-                       swap ? 1 : 0, A, lda, B, ldb, K16, K);
+                       swap ? 1 : 0, A_all, lda, B_all, ldb, k_tail0, K_all, accumulate ? 1 : 0);
     FSN_TRY_LAUNCH("tn_reduce_kernel");
     if (colsum_out) {
         hipLaunchKernelGGL(tn_colsum_reduce_kernel, dim3((M + 255) / 256), dim3(256), 0, s, asum_part, colsum_out, M,
-                           splits, A, lda, K16, K);
+                           splits, A_all, lda, k_tail0, K_all, accumulate ? 1 : 0);
         return fsn_check_launch("tn_colsum_reduce_kernel");
+    }
+    return FSN_OK;
+}
+
+
+// colsum_out (may be NULL): also out[m] = sum_k A[k][m], from the same pass over A (not with a narrow M)
+int fsn_launch_gemm_tn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int Nc, long K,
+                       void* workspace, hipStream_t s, float* colsum_out, int arith) {
+    if (arith != FSN_ARITH_F32 && arith != FSN_ARITH_F16 && arith != FSN_ARITH_BF16) {
+        fsn_set_error("gemm_tn: arithmetic %d unknown", arith);
+        return FSN_ERR_ARG;
+    }
+    if (K <= 0 || lda * 16 > 0x7fffffffL || ldb * 16 > 0x7fffffffL) {
+        fsn_set_error("gemm_tn: bad K = %ld or leading dimension", K);
+        return FSN_ERR_ARG;
+    }
+    // a narrow M (the 2-row dW of the sub-band output layer) goes on the narrow side of the tile
+    const bool swap = M <= 32 && Nc > 32;
+    if (swap && colsum_out) {
+        fsn_set_error("gemm_tn: fused column sums are not available for M <= 32");
+        return FSN_ERR_ARG;
+    }
+    const long K16 = K & ~15L;
+    float* part = static_cast<float*>(workspace);
+    // K in SEGMENTS when one split's chain would be long.  A split is one fp32 accumulation chain; one workgroup per CU fixes
+    // the split count, so the chain grows with K: 18 240 rows per split at K = 190 x 1536 (dW_hh of the sub-band pair) put the
+    // product at 2.3e-6 of fp64 in relative Frobenius norm, 5 - 6 x torch's blocked fp32 sum
+    // (tests/test_gpu_recurrent_sweep.py).  From kTnLongChain rows per split on, the product is formed in segments of
+    // splits x kTnSegChain rows, each summed over its splits and added to C in a fixed order: three levels instead of two.
+    // Cost: nseg launches of the product and of the reduction instead of one (9 at that K) and splits x M x Nc partials read
+    // per segment (38 MB each there, against the 2.2 GB the product reads anyway); the training step's time with it has not been
+    // measured.  fp32 only: the 16-bit arithmetics (this entry and gemm_tn16h / gemm_tn16n) keep one chain per split - their
+    // operands are rounded to 8 - 11 bits, against which the chain's fp32 rounding does not show (tests/test_gpu_amp.py).
+    long seg = K16 > 0 ? K16 : 0;
+    int nseg = 1;
+    if (K16 > 0) {
+        const TnPlan p0 = swap ? tn_plan(Nc, M, K16, arith, false) : tn_plan(M, Nc, K16, arith);
+        if (arith == FSN_ARITH_F32 && p0.k_per_split > kTnLongChain) {
+            nseg = (int)((K16 + (long)p0.splits * kTnSegChain - 1) / ((long)p0.splits * kTnSegChain));
+            seg = ((K16 + nseg - 1) / nseg + 15) / 16 * 16;
+            nseg = (int)((K16 + seg - 1) / seg);
+        }
+    }
+    for (int sg = 0; sg < nseg; ++sg) {
+        const long k0 = (long)sg * seg, Kc = K16 - k0 < seg ? K16 - k0 : seg;
+        const bool last_seg = sg == nseg - 1;
+        const int rc = gemm_tn_segment(A + k0 * lda, lda, B + k0 * ldb, ldb, C, ldc, M, Nc, Kc, part, s, colsum_out, arith, swap,
+                                       sg > 0, A, B, last_seg ? K16 : K, K);
+        if (rc != FSN_OK) return rc;
     }
     return FSN_OK;
 }
