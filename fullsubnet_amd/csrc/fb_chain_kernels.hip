@@ -73,10 +73,8 @@ __device__ __forceinline__ bool chain_wait(const unsigned* flags, int nflags, un
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // 16-byte write-through store (sc1): whole 16-byte groups, never single dwords - a step of the chain publishes ~0.8 MB,
 // and as dword stores that was 200 k partial-line write transactions per step (measured: 2 us of a 9.6 us step)
-__device__ __forceinline__ void chain_store16(const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff, f32x4 v,
-                                              bool plain) {
-    if (plain) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 0);
-    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 16);  // aux 16 = sc1
+__device__ __forceinline__ void chain_store16(const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff, f32x4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 16);  // aux 16 = sc1
 }
 // value of quad lane Q (lanes 4 k .. 4 k + 3 form a quad) in every lane of the quad
 template <int Q>
@@ -85,9 +83,6 @@ __device__ __forceinline__ float quad_bcast(float v) {
 }
 
 // KS = K split over the waves: 1 (up to 4 row tiles), 2 (up to 2), 4 (one row tile)
-// ABL: experiment knob of tools/probe_chain.hip (0 in the library; any bit set gives WRONG results): 1 no flag polling,
-// 2 no h / projection stores, 4 A fragments not loaded, 8 plain instead of write-through stores, 16 no drain before
-// the flag store, 32 no flag stores, 64 no layer-1 projection in L0 (L1 does not wait for it)
 // SAVE: the training form - every step also keeps the activated gates, the cell state and layer 0's hidden sequence
 // (fsn_lstm_layer_backward's inputs, the layouts of fsn_lstm_layer_forward)
 // CELL: 0 = LSTM (gate tile i | f | g | o); 1 = GRU (audio_zen/model/module/sequence_model.py:59-66) written as a FOUR-gate cell
@@ -95,7 +90,7 @@ __device__ __forceinline__ float quad_bcast(float v) {
 //   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr), z likewise, nx = W_in x + b_in (no recurrent part), nh = W_hn h + b_hn (no
 //   input part), n = tanh(nx + r nh), h' = n + z (h - n)
 // - the caller expands nn.GRU's [3H] gate rows to [4H] with zero blocks (fsn_gru2_forward); the cell state registers hold h.
-template <int CH, int KS, int ABL = 0, bool SAVE = false, int CELL = 0>
+template <int CH, int KS, bool SAVE = false, int CELL = 0>
 __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
     static_assert(!(SAVE && CELL != 0), "the training form is built for the LSTM cell");
     constexpr int CKC = CH / 16;   // K chunks of an H-wide operand (and column tiles per gate)
@@ -135,10 +130,8 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
     auto load_a = [&](f32x4 (&ar)[CW], const __amdgpu_buffer_rsrc_t& r, int ts) {
         const unsigned base = (unsigned)((((size_t)ts * RT + rt) * CKC + kp * CW) * 1024);
 #pragma unroll
-        for (int q = 0; q < CW; ++q) {
-            if (ABL & 4) ar[q] = f32x4{0.5f, 0.25f, -0.125f, 0.0625f};
-            else ar[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, lane16, base + q * 1024u, 16));
-        }
+        for (int q = 0; q < CW; ++q)
+            ar[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, lane16, base + q * 1024u, 16));
         __builtin_amdgcn_sched_barrier(0);  // every request leaves before the first MFMA waits for one of them
     };
     auto mac = [&](f32x4 acc, const f32x4 (&ar)[CW], const f32x4 (&w)[CW]) -> f32x4 {
@@ -165,13 +158,10 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
     };
     // every wave drains its stores, then one flag store per copy
     auto publish = [&](unsigned* flags, unsigned epoch) {
-        if (!(ABL & 16)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if ((int)threadIdx.x < CREP && !(ABL & 32))
+        if ((int)threadIdx.x < CREP)
             __hip_atomic_store(flags + (size_t)threadIdx.x * CFS + j, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    auto hstore = [&](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff, f32x4 v) {
-        if (!(ABL & 2)) chain_store16(r, voff, soff, v, (ABL & 8) != 0);
     };
     // lane (u', lq) of a quad holds v[i] = x[row 4 lq + i][unit u']: 4 x 4 transpose inside the quad ->
     // x[row 4 lq + ul][units 0..3], one 16-byte group of a row-major (or A-fragment) buffer per lane
@@ -251,7 +241,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
             f32x4 acc = gxn;
             if (owner && t + 1 < Tp) gxn = *reinterpret_cast<const f32x4*>(gx0p + (size_t)(t + 1) * gx0_step);
             if (t > 0) {
-                if (wave == 0 && !(ABL & 1)) (void)chain_wait(fl0 + rep * CFS, CNW, (unsigned)t, nullptr, 0, a.status, a.spin_ticks);
+                if (wave == 0) (void)chain_wait(fl0 + rep * CFS, CNW, (unsigned)t, nullptr, 0, a.status, a.spin_ticks);
                 __syncthreads();
                 if (active) load_a(ar, r0, t - 1);
             }
@@ -262,7 +252,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
                     const f32x4 hv = cell(acc, c, SAVE ? a.gates0 + (size_t)t * a.Npad * 4 * CH : nullptr,
                                           SAVE ? a.cseq0 + (size_t)t * a.Npad * CH : nullptr);
                     if (g == 0) {
-                        hstore(r0, hvoff, hsoff(t), hv);
+                        chain_store16(r0, hvoff, hsoff(t), hv);
                         if (SAVE) *reinterpret_cast<f32x4*>(a.hseq0 + ((size_t)t * a.Npad + rt * 16 + hrow) * CH + 4 * j) = hv;
                     }
                 }
@@ -272,18 +262,13 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
             // cost their full 1.7 us at 64 rows - a write-through store is acknowledged faster than that).  The tile's
             // store is awaited by the next drain: tile s is complete once this workgroup has published s + 3.  Inline
             // asm: a store the compiler sees makes every later wait for a load a wait for ALL memory operations.
-            const bool proj = t > 0 && active && !(ABL & 64);
+            const bool proj = t > 0 && active;
             const float b = kp == 0 ? bias1 : 0.f;
             if (t < Tp) publish(fl0, (unsigned)t + 1);
             if (proj) {
                 const f32x4 accx = mac(f32x4{b, b, b, b}, ar, wih);
                 const unsigned so = (unsigned)(t - 1) * gx1_step + gx1_wave;
-                if (ABL & 2) {
-                } else if (ABL & 8) {
-                    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" ::"v"(accx), "v"(lane16), "s"(rx), "s"(so) : "memory");
-                } else {
-                    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen sc1" ::"v"(accx), "v"(lane16), "s"(rx), "s"(so) : "memory");
-                }
+                asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen sc1" ::"v"(accx), "v"(lane16), "s"(rx), "s"(so) : "memory");
             }
             if (t == Tp) publish(fl0, (unsigned)Tp + 2);
         }
@@ -295,9 +280,8 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
     load_w(a.whh1_p, whh);
     for (int s = 0; s < Tp; ++s) {
         // h1_{s-1} of all workgroups, and the projection tile of step s from L0 workgroup j (complete at flag s + 3)
-        if (wave == 0 && !(ABL & 1))
-            (void)chain_wait(fl1 + rep * CFS, CNW, (unsigned)s, (ABL & 64) ? nullptr : fl0 + rep * CFS + j, (unsigned)s + 3,
-                             a.status, a.spin_ticks);
+        if (wave == 0)
+            (void)chain_wait(fl1 + rep * CFS, CNW, (unsigned)s, fl0 + rep * CFS + j, (unsigned)s + 3, a.status, a.spin_ticks);
         __syncthreads();
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
         if (active) {
@@ -312,7 +296,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
             const f32x4 hv = cell(acc, c, SAVE ? a.gates1 + (size_t)s * a.Npad * 4 * CH : nullptr,
                                   SAVE ? a.cseq1 + (size_t)s * a.Npad * CH : nullptr);
             if (g == 0) {
-                hstore(r1, hvoff, hsoff(s), hv);
+                chain_store16(r1, hvoff, hsoff(s), hv);
                 *reinterpret_cast<f32x4*>(a.hseq1 + ((size_t)s * a.Npad + rt * 16 + hrow) * CH + 4 * j) = hv;
             }
         }
@@ -329,12 +313,12 @@ template <int CH>
 bool chain_grid_fits(int RT) {
     const unsigned grid = 2 * (CH / 4);
     const void *k, *ks;
-    if (RT == 1) k = (const void*)fb_chain_kernel<CH, 4, 0, false>, ks = (const void*)fb_chain_kernel<CH, 4, 0, true>;
-    else if (RT == 2) k = (const void*)fb_chain_kernel<CH, 2, 0, false>, ks = (const void*)fb_chain_kernel<CH, 2, 0, true>;
-    else k = (const void*)fb_chain_kernel<CH, 1, 0, false>, ks = (const void*)fb_chain_kernel<CH, 1, 0, true>;
-    const void* kg = RT == 1   ? (const void*)fb_chain_kernel<CH, 4, 0, false, 1>
-                     : RT == 2 ? (const void*)fb_chain_kernel<CH, 2, 0, false, 1>
-                               : (const void*)fb_chain_kernel<CH, 1, 0, false, 1>;
+    if (RT == 1) k = (const void*)fb_chain_kernel<CH, 4, false>, ks = (const void*)fb_chain_kernel<CH, 4, true>;
+    else if (RT == 2) k = (const void*)fb_chain_kernel<CH, 2, false>, ks = (const void*)fb_chain_kernel<CH, 2, true>;
+    else k = (const void*)fb_chain_kernel<CH, 1, false>, ks = (const void*)fb_chain_kernel<CH, 1, true>;
+    const void* kg = RT == 1   ? (const void*)fb_chain_kernel<CH, 4, false, 1>
+                     : RT == 2 ? (const void*)fb_chain_kernel<CH, 2, false, 1>
+                               : (const void*)fb_chain_kernel<CH, 1, false, 1>;
     return fsn_grid_fits(k, 256, grid) && fsn_grid_fits(ks, 256, grid) && fsn_grid_fits(kg, 256, grid);
 }
 }  // namespace
@@ -356,9 +340,9 @@ namespace {
 template <int CH, bool SAVE, int CELL = 0>
 void chain_launch(const ChainArgs& a, hipStream_t s) {
     const dim3 grid(2 * (CH / 4)), block(256);
-    if (a.RT == 1) FSN_PERSIST_LAUNCH((fb_chain_kernel<CH, 4, 0, SAVE, CELL>), grid, block, s, a);
-    else if (a.RT == 2) FSN_PERSIST_LAUNCH((fb_chain_kernel<CH, 2, 0, SAVE, CELL>), grid, block, s, a);
-    else FSN_PERSIST_LAUNCH((fb_chain_kernel<CH, 1, 0, SAVE, CELL>), grid, block, s, a);
+    if (a.RT == 1) FSN_PERSIST_LAUNCH((fb_chain_kernel<CH, 4, SAVE, CELL>), grid, block, s, a);
+    else if (a.RT == 2) FSN_PERSIST_LAUNCH((fb_chain_kernel<CH, 2, SAVE, CELL>), grid, block, s, a);
+    else FSN_PERSIST_LAUNCH((fb_chain_kernel<CH, 1, SAVE, CELL>), grid, block, s, a);
 }
 }  // namespace
 

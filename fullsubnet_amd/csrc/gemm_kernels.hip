@@ -18,10 +18,6 @@
 // (base_model.py:31-44, fullsubnet/model.py:110-111) are never materialised.
 #include "fsn_common.h"
 
-#ifndef FSN_GEMM_ABLATE
-#define FSN_GEMM_ABLATE 0  // probe-only: 1 = no operand loads in the K loop, 2 = no MFMAs
-#endif
-
 namespace {
 
 __device__ __forceinline__ int reflect_idx(int j, int F) {
@@ -229,7 +225,6 @@ __global__ __launch_bounds__(WR* WC * 64) void gemm_kernel(FsnGemmA a, const flo
     for (int kc0 = 0; kc0 < k_main; kc0 += PF) {
 #pragma unroll
         for (int p = 0; p < PF; ++p) {
-#if FSN_GEMM_ABLATE != 2
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -237,13 +232,6 @@ __global__ __launch_bounds__(WR* WC * 64) void gemm_kernel(FsnGemmA a, const flo
 #pragma unroll
                     for (int ct = 0; ct < CTW; ++ct)
                         acc[rt][ct] = mfma16(abuf[p][rt][j], bbuf[p][ct][j], acc[rt][ct]);
-#else
-#pragma unroll
-            for (int rt = 0; rt < RTW; ++rt) asm volatile("" ::"v"(abuf[p][rt]));
-#pragma unroll
-            for (int ct = 0; ct < CTW; ++ct) asm volatile("" ::"v"(bbuf[p][ct]));
-#endif
-#if FSN_GEMM_ABLATE != 1
             // pin the refill of slot p right here: hipcc otherwise sinks these loads down to their
             // first use (one ring turn later), which turns the ring into load -> wait -> use
             __builtin_amdgcn_sched_barrier(0);
@@ -254,7 +242,6 @@ __global__ __launch_bounds__(WR* WC * 64) void gemm_kernel(FsnGemmA a, const flo
 #pragma unroll
             for (int ct = 0; ct < CTW; ++ct) bbuf[p][ct] = *reinterpret_cast<const f32x4*>(bptr[ct] + (long)kn * 256);
             __builtin_amdgcn_sched_barrier(0);
-#endif
         }
     }
     // remainder chunks (k_chunks % PF of them) are already sitting in the ring, in order

@@ -12,9 +12,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 #ifndef FSN_F16X3_UG
 #define FSN_F16X3_UG 2  // hidden-unit groups of 16 per wave: 2 -> 12 waves, 3 -> 8 waves
 #endif
-#ifndef FSN_PROBE_ABLATE  // tools/probe_rec_f16x3.hip only: 1 no W refills, 2 no LDS operand reads, 3 no cell math
-#define FSN_PROBE_ABLATE 0
-#endif
 
 namespace {
 
@@ -145,16 +142,14 @@ __global__ __launch_bounds__((H / (16 * UG)) * 64) void lstm_rec_f16x3_kernel(co
                     // pinned: without the fences the compiler sinks these loads to the top of the NEXT iteration,
                     // right in front of the MFMAs that wait for them (an L2 round trip exposed per chunk)
                     __builtin_amdgcn_sched_barrier(0);
-                    if (FSN_PROBE_ABLATE != 1) {
 #pragma unroll
-                        for (int u = 0; u < UG; ++u) {
-                            bhn[u] = whi[bo[u] + (long)kcur * 64];
-                            bln[u] = wlo[bo[u] + (long)kcur * 64];
-                        }
+                    for (int u = 0; u < UG; ++u) {
+                        bhn[u] = whi[bo[u] + (long)kcur * 64];
+                        bln[u] = wlo[bo[u] + (long)kcur * 64];
                     }
                     __builtin_amdgcn_sched_barrier(0);
-                    const _Float16* ap = hh + lr * HSH + (FSN_PROBE_ABLATE == 2 ? 0 : kc * 32) + 8 * lq;
-                    const _Float16* lp = hlo + lr * HSH + (FSN_PROBE_ABLATE == 2 ? 0 : kc * 32) + 8 * lq;
+                    const _Float16* ap = hh + lr * HSH + kc * 32 + 8 * lq;
+                    const _Float16* lp = hlo + lr * HSH + kc * 32 + 8 * lq;
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt) {
                         const f16x8 ah = *reinterpret_cast<const f16x8*>(ap + rt * 16 * HSH);
@@ -176,8 +171,7 @@ __global__ __launch_bounds__((H / (16 * UG)) * 64) void lstm_rec_f16x3_kernel(co
         const float x = acc[rt][u][i] * (1.0f / kS);                  \
         STMT;                                                         \
     }
-            if (FSN_PROBE_ABLATE == 3) { FSN_CELL(tmp[rt][u][i] = x + cst[rt][u][i]) }
-            else if (pass == 0) { FSN_CELL(cst[rt][u][i] = sigmoid_fast(x) * cst[rt][u][i]) }
+            if (pass == 0) { FSN_CELL(cst[rt][u][i] = sigmoid_fast(x) * cst[rt][u][i]) }
             else if (pass == 1) { FSN_CELL(tmp[rt][u][i] = sigmoid_fast(x)) }
             else if (pass == 2) { FSN_CELL(cst[rt][u][i] = cst[rt][u][i] + tmp[rt][u][i] * tanh_fast(x)) }
             else { FSN_CELL(tmp[rt][u][i] = sigmoid_fast(x) * tanh_fast(cst[rt][u][i])) }

@@ -222,11 +222,8 @@ struct G16FwdArgs {
     int Tp, Nrows;
 };
 
-// ABL: experiment knob of tools/probe_g16.hip (0 in the library; any bit set gives WRONG results): 1 no flag waits, 2 the
-// partners' tiles not loaded (constants staged), 4 no weight loads (constant fragments), 8 no saves, 16 no h stores
-template <int LAYER, int AR, int ABL, int XS, int SV>
+template <int LAYER, int AR, int XS, int SV>
 __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, int member, unsigned char* act, unsigned char* xsm) {
-    float live = 0.f;  // keeps ablated values alive
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lq = lane >> 4;
     const int Tp = a.Tp;
@@ -238,9 +235,8 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
     auto wbase = [&](unsigned o, int kbn) { return o + (unsigned)((member * 4 + wave) * kbn) * 3072u; };
     const unsigned w_rec = wbase(LAYER ? a.o_hh1 : a.o_hh0, 12), w_in = LAYER ? wbase(a.o_ih1, 12) : wbase(a.o_ih0, 1);
     auto wload = [&](unsigned base, int kb, int j) {
-        if constexpr ((ABL & 4) != 0) return q_u32x4{0x3c003c00u + (unsigned)kb, 0x38003800u, 0x34003400u + (unsigned)j, 0x30003000u};
-        else return __builtin_bit_cast(q_u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (unsigned)lane * 16u,
-                                                                                      base + (unsigned)kb * 3072u + (unsigned)j * 1024u, 0));
+        return __builtin_bit_cast(q_u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (unsigned)lane * 16u,
+                                                                                 base + (unsigned)kb * 3072u + (unsigned)j * 1024u, 0));
     };
     // the cluster's [64][H] tile of step t of a hidden sequence / cell sequence, its [64][4H] tile of a gate buffer
     auto tileh = [&](float* p, int t) { return q_rsrc(p + ((size_t)t * N + (size_t)cluster * QROWS) * QH, QROWS * QH * 4); };
@@ -262,13 +258,8 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
             for (int i = 0; i < 6; ++i) {
                 const int q = tid + 256 * (half * 6 + i), row = q / 48, k8 = q % 48;
                 const unsigned go = (unsigned)((row * QH + k8 * 8) * 4);
-                if constexpr ((ABL & 2) != 0) {
-                    v[2 * i] = f32x4{0.01f * (float)row, 0.02f, -0.01f, 0.03f};
-                    v[2 * i + 1] = f32x4{0.02f, -0.03f, 0.01f * (float)k8, 0.f};
-                } else {
-                    v[2 * i] = q_load_sc1<XS>(src, go, 0);
-                    v[2 * i + 1] = q_load_sc1<XS>(src, go, 16);
-                }
+                v[2 * i] = q_load_sc1<XS>(src, go, 0);
+                v[2 * i + 1] = q_load_sc1<XS>(src, go, 16);
             }
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
@@ -287,8 +278,7 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
             const int q = tid + 256 * i, row = q / 48, k8 = q % 48;
-            if constexpr ((ABL & 2) != 0) v[i] = q_u32x4{0x2c002c00u + (unsigned)row, 0x28002800u, 0x24002400u + (unsigned)k8, 0x20002000u};
-            else v[i] = __builtin_bit_cast(q_u32x4, __builtin_amdgcn_raw_buffer_load_b128(src, (unsigned)(row * QG * 4 + Q_H16_OFF + k8 * 16), 0, XS));
+            v[i] = __builtin_bit_cast(q_u32x4, __builtin_amdgcn_raw_buffer_load_b128(src, (unsigned)(row * QG * 4 + Q_H16_OFF + k8 * 16), 0, XS));
         }
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
@@ -359,8 +349,7 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
                 *reinterpret_cast<q_u32x4*>(xsm + row * X_STRIDE + k8 * 16) = q_u32x4{lo[0], lo[1], hi[0], hi[1]};
             }
             if (t > 0) {
-                if constexpr ((ABL & 1) != 0) __syncthreads();
-                else q_wait(fl0, (unsigned)t, a.status, a.spin_ticks);  // h0_{t-1} of all members
+                q_wait(fl0, (unsigned)t, a.status, a.spin_ticks);  // h0_{t-1} of all members
                 if constexpr (SV != 0) stage16(a.gates0, t - 1);
                 else stage(tileh(a.hseq0, t - 1));
             }
@@ -378,16 +367,14 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
         } else {
             // x_t W_ih1^T first: it needs h0_t, which layer 0 published long ago; then h1_{t-1} W_hh1^T
             ring_start(ring, w_in);
-            if constexpr ((ABL & 1) != 0) __syncthreads();
-            else q_wait(fl0, (unsigned)t + 1, a.status, a.spin_ticks);
+            q_wait(fl0, (unsigned)t + 1, a.status, a.spin_ticks);
             if constexpr (SV != 0) stage16(a.gates0, t);
             else stage(tileh(a.hseq0, t));
             __syncthreads();
             kloop12(acc, ring, w_in);
             if (t > 0) {
                 ring_start(ring, w_rec);
-                if constexpr ((ABL & 1) != 0) __syncthreads();
-                else q_wait(fl1, (unsigned)t, a.status, a.spin_ticks);  // h1_{t-1} of all members; also: everyone has left `act`
+                q_wait(fl1, (unsigned)t, a.status, a.spin_ticks);  // h1_{t-1} of all members; also: everyone has left `act`
                 if constexpr (SV != 0) stage16(a.gates1, t - 1);
                 else stage(tileh(a.hseq1, t - 1));
                 __syncthreads();
@@ -418,8 +405,7 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
                 hv[i] = og * tanh_fast(cn);
                 sg[e][0][i] = ig, sg[e][1][i] = fg, sg[e][2][i] = gg, sg[e][3][i] = og;
             }
-            if constexpr ((ABL & 16) != 0) live += hv[0] + hv[1] + hv[2] + hv[3];
-            else if constexpr (SV != 0)
+            if constexpr (SV != 0)
                 __builtin_amdgcn_raw_buffer_store_b64(q_round4<AR>(hv), rg, (unsigned)(row * QG * 4 + Q_H16_OFF + (QU * member + quad * 4) * 2), 0, XS);
             else q_store_sc1<XS>(rh, (unsigned)((row * QH + QU * member + quad * 4) * 4), 0, hv);
         }
@@ -430,35 +416,29 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
         for (int e = 0; e < 3; ++e) {
             const int q = tid + 256 * e, row = q / 12, quad = q % 12;
             const unsigned go = (unsigned)((row * QG + QU * member + quad * 4) * 4);
-            if constexpr ((ABL & 8) != 0) {
+            if constexpr (SV != 0) {
+                const unsigned so = (unsigned)(row * QG * 4 + (12 * member + quad) * 32);
+                const fsn_u32x2 pi = q_round4<AR>(sg[e][0]), pf = q_round4<AR>(sg[e][1]);
+                const fsn_u32x2 pg = q_round4<AR>(sg[e][2]), po = q_round4<AR>(sg[e][3]);
+                __builtin_amdgcn_raw_buffer_store_b128(q_u32x4{pi[0], pi[1], pf[0], pf[1]}, rg, so, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(q_u32x4{pg[0], pg[1], po[0], po[1]}, rg, so, 16, 0);
+                // (h_t in 16 bits sits behind them, second half of the row's slot, [H] values: the hand-off above - and the B
+                // operand of two weight-gradient products, which need no conversion pass over the hidden sequence.)  The
+                // fp32 hidden sequence, off the hand-off path: recomputed from o and c, the very value that was rounded
+                f32x4 hv;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) live += sg[e][g][0] + sg[e][g][3];
+                for (int i = 0; i < 4; ++i) hv[i] = sg[e][3][i] * tanh_fast(c[e][i]);
+                q_store(rh, (unsigned)((row * QH + QU * member + quad * 4) * 4), 0, hv);
             } else {
-                if constexpr (SV != 0) {
-                    const unsigned so = (unsigned)(row * QG * 4 + (12 * member + quad) * 32);
-                    const fsn_u32x2 pi = q_round4<AR>(sg[e][0]), pf = q_round4<AR>(sg[e][1]);
-                    const fsn_u32x2 pg = q_round4<AR>(sg[e][2]), po = q_round4<AR>(sg[e][3]);
-                    __builtin_amdgcn_raw_buffer_store_b128(q_u32x4{pi[0], pi[1], pf[0], pf[1]}, rg, so, 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b128(q_u32x4{pg[0], pg[1], po[0], po[1]}, rg, so, 16, 0);
-                    // (h_t in 16 bits sits behind them, second half of the row's slot, [H] values: the hand-off above - and the B
-                    // operand of two weight-gradient products, which need no conversion pass over the hidden sequence.)  The
-                    // fp32 hidden sequence, off the hand-off path: recomputed from o and c, the very value that was rounded
-                    f32x4 hv;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) hv[i] = sg[e][3][i] * tanh_fast(c[e][i]);
-                    q_store(rh, (unsigned)((row * QH + QU * member + quad * 4) * 4), 0, hv);
-                } else {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) q_store(rg, go, (unsigned)(g * QH * 4), sg[e][g]);
-                }
-                q_store(rc, (unsigned)((row * QH + QU * member + quad * 4) * 4), 0, c[e]);
+                for (int g = 0; g < 4; ++g) q_store(rg, go, (unsigned)(g * QH * 4), sg[e][g]);
             }
+            q_store(rc, (unsigned)((row * QH + QU * member + quad * 4) * 4), 0, c[e]);
         }
     }
-    if (ABL != 0 && live == 123.456f) a.status[1] = 1u;  // never true: the ablated values stay computed
 }
 
-template <int AR, int ABL = 0, int SV = 0>
+template <int AR, int SV = 0>
 __global__ __launch_bounds__(256, 2) void lstm2_g16_fwd_kernel(const G16FwdArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char act[FWD_LDS];
     __shared__ __attribute__((aligned(16))) unsigned char xsm[QROWS * X_STRIDE];
@@ -470,10 +450,7 @@ __global__ __launch_bounds__(256, 2) void lstm2_g16_fwd_kernel(const G16FwdArgs 
     const int bid = (int)blockIdx.x - layer * half;
     const int nclusters = half / QM;
     int cluster, member;
-    if ((ABL & 128) != 0 && nclusters % 8 == 0) {  // experiment: MEMBERS (not clusters) share an XCD - its L2 holds 1/8 of the weights
-        member = bid & 7;
-        cluster = bid >> 3;
-    } else if (nclusters % 8 == 0) {
+    if (nclusters % 8 == 0) {
         const int xcd = bid & 7, j = bid >> 3;
         cluster = xcd * (nclusters / 8) + j / QM;
         member = j % QM;
@@ -484,7 +461,7 @@ __global__ __launch_bounds__(256, 2) void lstm2_g16_fwd_kernel(const G16FwdArgs 
     // Placement check: every workgroup reports the XCD it runs on (HW_REG_XCC_ID) and reads its cluster's sixteen reports;
     // only when all agree is the payload exchanged at XCD scope (XS = 1: 9 % of the launch, the partners' tiles come from
     // the shared L2 instead of through the fabric).  Any other placement - or a timeout - takes the device-scope path:
-    // results never depend on where the workgroups run.  (ABL & 64: the probe's device-scope run.)
+    // results never depend on where the workgroups run.
     bool same_xcd = false;
     {
         unsigned xcc;
@@ -510,15 +487,15 @@ __global__ __launch_bounds__(256, 2) void lstm2_g16_fwd_kernel(const G16FwdArgs 
             if (lane == 0) *agree = ok ? 1u : 0u;
         }
         __syncthreads();
-        same_xcd = *agree != 0u && (ABL & 64) == 0;
+        same_xcd = *agree != 0u;
         __syncthreads();  // (xsm is the layer-0 input tile afterwards)
     }
     if (same_xcd) {
-        if (layer == 0) g16_fwd_body<0, AR, ABL, 1, SV>(a, cluster, member, act, xsm);
-        else g16_fwd_body<1, AR, ABL, 1, SV>(a, cluster, member, act, xsm);
+        if (layer == 0) g16_fwd_body<0, AR, 1, SV>(a, cluster, member, act, xsm);
+        else g16_fwd_body<1, AR, 1, SV>(a, cluster, member, act, xsm);
     } else {
-        if (layer == 0) g16_fwd_body<0, AR, ABL, 16, SV>(a, cluster, member, act, xsm);
-        else g16_fwd_body<1, AR, ABL, 16, SV>(a, cluster, member, act, xsm);
+        if (layer == 0) g16_fwd_body<0, AR, 16, SV>(a, cluster, member, act, xsm);
+        else g16_fwd_body<1, AR, 16, SV>(a, cluster, member, act, xsm);
     }
 }
 
@@ -561,12 +538,9 @@ struct G16BwdArgs {
     int Tp, Nrows;
 };
 
-// ABL (tools/probe_g16.hip; 0 in the library, any bit set gives WRONG results): 1 no flag waits, 2 saved activations not
-// loaded, 4 no weight loads, 8 no gate-gradient stores, 16 no exchange stores, 32 exchanged operand not loaded
-template <int LAYER, int AR, int ABL, int SV>
+template <int LAYER, int AR, int SV>
 __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, int member, unsigned char* red, unsigned char* dsh,
                                              float (*dbs)[4 * QU]) {
-    float live = 0.f;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lq = lane >> 4;
     const int Tp = a.Tp;
@@ -578,18 +552,10 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
     constexpr int NBW = q_nbw<AR>(), NBM = q_nbm<AR>(), XSLOT = q_xslot<AR>();
     auto wbase = [&](unsigned o) { return o + (unsigned)((member * 4 + wave) * NBW) * 3072u; };
     auto wload = [&](unsigned base, int kbl, int j) {
-        if constexpr ((ABL & 4) != 0) return q_u32x4{0x3c003c00u + (unsigned)kbl, 0x38003800u, 0x34003400u + (unsigned)j, 0x30003000u};
-        else return __builtin_bit_cast(q_u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (unsigned)lane * 16u,
-                                                                                      base + (unsigned)kbl * 3072u + (unsigned)j * 1024u, 0));
+        return __builtin_bit_cast(q_u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (unsigned)lane * 16u,
+                                                                                 base + (unsigned)kbl * 3072u + (unsigned)j * 1024u, 0));
     };
-    auto wait = [&](unsigned* f8, unsigned epoch) {
-        if constexpr ((ABL & 1) != 0) __syncthreads();
-        else q_wait(f8, epoch, a.status, a.spin_ticks);
-    };
-    auto sload = [&](const __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-        if constexpr ((ABL & 2) != 0) return f32x4{0.4f, 0.3f, 0.2f + 1e-6f * (float)soff, 0.1f};
-        else return q_load(r, voff, soff);
-    };
+    auto wait = [&](unsigned* f8, unsigned epoch) { q_wait(f8, epoch, a.status, a.spin_ticks); };
     auto tileh = [&](const float* p, int t) { return q_rsrc(p + ((size_t)t * N + (size_t)cluster * QROWS) * QH, QROWS * QH * 4); };
     auto tileg = [&](const float* p, int t) { return q_rsrc(p + ((size_t)t * N + (size_t)cluster * QROWS) * QG, QROWS * QG * 4); };
     const __amdgpu_buffer_rsrc_t rx1 = q_rsrc(reinterpret_cast<const unsigned char*>(a.x1) + (size_t)cluster * QDX * XSLOT, (unsigned)QDX * XSLOT);
@@ -605,9 +571,8 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
     // starts here, after it.
     auto kloop = [&](f32x4 (&acc)[3][4], q_u32x4 (&wring)[QWD][3], unsigned wb, const __amdgpu_buffer_rsrc_t rx, unsigned xo) {
         auto xload = [&](int kbl, int r) {
-            if constexpr ((ABL & 32) != 0) return q_u32x4{0x2c002c00u + (unsigned)kbl, 0x28002800u, 0x24002400u + (unsigned)r, 0x20002000u};
-            else return __builtin_bit_cast(q_u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                        rx, (unsigned)lane * 16u, xo + (unsigned)(((wave * NBW + kbl) * 4 + r) * 1024), 16));
+            return __builtin_bit_cast(q_u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                   rx, (unsigned)lane * 16u, xo + (unsigned)(((wave * NBW + kbl) * 4 + r) * 1024), 16));
         };
         q_u32x4 aring[QAD][4];
 #pragma unroll
@@ -660,7 +625,7 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
     {
         const __amdgpu_buffer_rsrc_t rc = tileh(cseq, Tp - 1);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) c_t[j] = sload(rc, eo_h, (unsigned)(j * 64));
+        for (int j = 0; j < 3; ++j) c_t[j] = q_load(rc, eo_h, (unsigned)(j * 64));
     }
 
     for (int t = Tp - 1; t >= 0; --t) {
@@ -677,7 +642,7 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
         f32x4 sg[3][4], c_p[3], dh[3];
         {
             const float* gp = gates + ((size_t)t * N + (size_t)cluster * QROWS + wave * 16 + lr) * QG + QU * member + 4 * lq;
-            if constexpr ((ABL & 2) == 0 && SV != 0) {  // 16-bit saves: a lane's (row, unit quad) item = 32 bytes = two pieces
+            if constexpr (SV != 0) {  // 16-bit saves: a lane's (row, unit quad) item = 32 bytes = two pieces
                 const unsigned char* gp16 = reinterpret_cast<const unsigned char*>(gates) +
                                             ((size_t)t * N + (size_t)cluster * QROWS + wave * 16 + lr) * (QG * 4) + (12 * member + lq) * 32;
 #pragma unroll
@@ -685,7 +650,7 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
 #pragma unroll
                     for (int p = 0; p < 2; ++p)
                         q_lds_dma(reinterpret_cast<const float*>(gp16 + j * 128 + p * 16), red_w + (unsigned)((j * 2 + p) * 1024));
-            } else if constexpr ((ABL & 2) == 0) {
+            } else {
 #pragma unroll
                 for (int j = 0; j < 3; ++j)
 #pragma unroll
@@ -694,8 +659,8 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
             const __amdgpu_buffer_rsrc_t rp = tileh(cseq, t > 0 ? t - 1 : 0), rd = tileh(LAYER ? a.dh1 : cseq, t);
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                c_p[j] = t > 0 ? sload(rp, eo_h, (unsigned)(j * 64)) : f32x4{0.f, 0.f, 0.f, 0.f};
-                dh[j] = LAYER ? sload(rd, eo_h, (unsigned)(j * 64)) : f32x4{0.f, 0.f, 0.f, 0.f};
+                c_p[j] = t > 0 ? q_load(rp, eo_h, (unsigned)(j * 64)) : f32x4{0.f, 0.f, 0.f, 0.f};
+                dh[j] = LAYER ? q_load(rd, eo_h, (unsigned)(j * 64)) : f32x4{0.f, 0.f, 0.f, 0.f};
             }
         }
         q_u32x4 wring[QWD][3];
@@ -711,7 +676,7 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
         }
         // the gates have landed long ago (the DMA is older than every load the K loops consumed); say so, read them back
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr ((ABL & 2) == 0 && SV != 0) {
+        if constexpr (SV != 0) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 const q_u32x4 v0 = q_lds128(red + (wave * 12 + j * 2) * 1024 + lane * 16);
@@ -723,10 +688,7 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
 #pragma unroll
             for (int j = 0; j < 3; ++j)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    if constexpr ((ABL & 2) != 0) sg[j][g] = f32x4{0.4f, 0.3f, 0.2f + 1e-3f * (float)(j + g), 0.1f};
-                    else sg[j][g] = *reinterpret_cast<const f32x4*>(red + (wave * 12 + j * 4 + g) * 1024 + lane * 16);
-                }
+                for (int g = 0; g < 4; ++g) sg[j][g] = *reinterpret_cast<const f32x4*>(red + (wave * 12 + j * 4 + g) * 1024 + lane * 16);
         }
         // the four waves' K quarters meet: wave w' takes row tile w', sums the sources in a fixed order
 #pragma unroll
@@ -771,53 +733,49 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
 #pragma unroll
         for (int kbl = 0; kbl < NBM; ++kbl) {
             const q_u32x4 v = q_lds128(dsh + (wave * 16 + lr) * DSH_STRIDE + kbl * 64 + lq * 16);
-            if constexpr ((ABL & 16) != 0) live += __builtin_bit_cast(float, v[0]);
-            else __builtin_amdgcn_raw_buffer_store_b128(v, rxo, (unsigned)lane * 16u,
-                                                        (unsigned)((t % QDX) * XSLOT + ((NBM * member + kbl) * 4 + wave) * 1024), 16);
+            __builtin_amdgcn_raw_buffer_store_b128(v, rxo, (unsigned)lane * 16u,
+                                                   (unsigned)((t % QDX) * XSLOT + ((NBM * member + kbl) * 4 + wave) * 1024), 16);
         }
         q_publish(myfl + member, done + 1);  // its barrier also closes this step's use of `red` and `dsh`
         // AFTER the hand-off (only the fragment-order tile belongs to it): the gate gradients for the products that follow
         // the launch - 16-bit row-major copies [t][row][4H] (the weight-gradient products' operand: rounding here or at their
         // matrix input is the same number), fp32 for layer 0 (its input gradient is an fp32 product) - and their column sums
         // (the bias gradients, from the fp32 values): the 16 rows of a wave summed by DPP, one lane per unit quad adds to LDS
-        if constexpr ((ABL & 8) == 0) {
-            const __amdgpu_buffer_rsrc_t r16 = q_rsrc(dg16 + ((size_t)t * N + (size_t)cluster * QROWS) * QG, QROWS * QG * 2);
-            const unsigned eo_16 = (unsigned)((((wave * 16 + lr) * QG) + QU * member + 4 * lq) * 2);
+        const __amdgpu_buffer_rsrc_t r16 = q_rsrc(dg16 + ((size_t)t * N + (size_t)cluster * QROWS) * QG, QROWS * QG * 2);
+        const unsigned eo_16 = (unsigned)((((wave * 16 + lr) * QG) + QU * member + 4 * lq) * 2);
 #pragma unroll
-            for (int j = 0; j < 3; ++j)
+        for (int j = 0; j < 3; ++j)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    if (LAYER ? a.dg1_f32 : a.dg0_f32) q_store(ro, eo_g, (unsigned)(g * QH * 4 + j * 64), sg[j][g]);
-                    __builtin_amdgcn_raw_buffer_store_b64(q_round4<AR>(sg[j][g]), r16, eo_16, (unsigned)((g * QH + j * 16) * 2), 0);
-                    fsn_hold_store_data(sg[j][g]);  // the sums below may be formed in the store's data registers
-                    f32x4 v = sg[j][g];
+            for (int g = 0; g < 4; ++g) {
+                if (LAYER ? a.dg1_f32 : a.dg0_f32) q_store(ro, eo_g, (unsigned)(g * QH * 4 + j * 64), sg[j][g]);
+                __builtin_amdgcn_raw_buffer_store_b64(q_round4<AR>(sg[j][g]), r16, eo_16, (unsigned)((g * QH + j * 16) * 2), 0);
+                fsn_hold_store_data(sg[j][g]);  // the sums below may be formed in the store's data registers
+                f32x4 v = sg[j][g];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {  // sum over the 16 lanes lr of this lane's group: quad xor 1, xor 2, half mirror, mirror
-                        float x = v[i];
-                        x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
-                        x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));
-                        x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));
-                        x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));
-                        v[i] = x;
-                    }
-                    if (lr == 0) {
-                        f32x4* d = reinterpret_cast<f32x4*>(&dbs[wave][g * QU + 16 * j + 4 * lq]);
-                        *d += v;
-                    }
+                for (int i = 0; i < 4; ++i) {  // sum over the 16 lanes lr of this lane's group: quad xor 1, xor 2, half mirror, mirror
+                    float x = v[i];
+                    x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
+                    x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));
+                    x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));
+                    x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));
+                    v[i] = x;
                 }
-        }
+                if (lr == 0) {
+                    f32x4* d = reinterpret_cast<f32x4*>(&dbs[wave][g * QU + 16 * j + 4 * lq]);
+                    *d += v;
+                }
+            }
     }
     // the member's bias-gradient sums: the four waves' (row tiles') accumulators in a fixed order
     __syncthreads();
-    if (threadIdx.x < 4 * QU && (ABL & 8) == 0) {
+    if (threadIdx.x < 4 * QU) {
         const int k = threadIdx.x;
         const float v = ((dbs[0][k] + dbs[1][k]) + dbs[2][k]) + dbs[3][k];
         a.dbp[((size_t)LAYER * (gridDim.x / (2 * QM)) + cluster) * QG + (k / QU) * QH + QU * member + k % QU] = v;
     }
-    if (ABL != 0 && live == 123.456f) a.status[1] = 1u;  // never true: the ablated values stay computed
 }
 
-template <int AR, int ABL = 0, int SV = 0>
+template <int AR, int SV = 0>
 __global__ __launch_bounds__(256, 2) void lstm2_g16_bwd_kernel(const G16BwdArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char red[4 * 12 * 1024];
     __shared__ __attribute__((aligned(16))) unsigned char dsh[QROWS * DSH_STRIDE];
@@ -829,10 +787,7 @@ __global__ __launch_bounds__(256, 2) void lstm2_g16_bwd_kernel(const G16BwdArgs 
     const int bid = (int)blockIdx.x - second * half;
     const int nclusters = half / QM;
     int cluster, member;
-    if ((ABL & 128) != 0 && nclusters % 8 == 0) {  // experiment: MEMBERS (not clusters) share an XCD - its L2 holds 1/8 of the weights
-        member = bid & 7;
-        cluster = bid >> 3;
-    } else if (nclusters % 8 == 0) {
+    if (nclusters % 8 == 0) {
         const int xcd = bid & 7, j = bid >> 3;
         cluster = xcd * (nclusters / 8) + j / QM;
         member = j % QM;
@@ -840,8 +795,8 @@ __global__ __launch_bounds__(256, 2) void lstm2_g16_bwd_kernel(const G16BwdArgs 
         cluster = bid / QM;
         member = bid % QM;
     }
-    if (!second) g16_bwd_body<1, AR, ABL, SV>(a, cluster, member, red, dsh, dbs);
-    else g16_bwd_body<0, AR, ABL, SV>(a, cluster, member, red, dsh, dbs);
+    if (!second) g16_bwd_body<1, AR, SV>(a, cluster, member, red, dsh, dbs);
+    else g16_bwd_body<0, AR, SV>(a, cluster, member, red, dsh, dbs);
 }
 
 // After the launch: the rows that did not fill a cluster (computed step by step beside it, fp32) need their 16-bit copies ...
@@ -877,8 +832,8 @@ int fsn_lstm2_g16_clusters(int tiles) {
         return 0;
     for (const void* k : {(const void*)lstm2_g16_fwd_kernel<FSN_ARITH_F16>, (const void*)lstm2_g16_fwd_kernel<FSN_ARITH_BF16>,
                           (const void*)lstm2_g16_bwd_kernel<FSN_ARITH_F16>, (const void*)lstm2_g16_bwd_kernel<FSN_ARITH_BF16>,
-                          (const void*)lstm2_g16_fwd_kernel<FSN_ARITH_F16, 0, 1>, (const void*)lstm2_g16_fwd_kernel<FSN_ARITH_BF16, 0, 1>,
-                          (const void*)lstm2_g16_bwd_kernel<FSN_ARITH_F16, 0, 1>, (const void*)lstm2_g16_bwd_kernel<FSN_ARITH_BF16, 0, 1>})
+                          (const void*)lstm2_g16_fwd_kernel<FSN_ARITH_F16, 1>, (const void*)lstm2_g16_fwd_kernel<FSN_ARITH_BF16, 1>,
+                          (const void*)lstm2_g16_bwd_kernel<FSN_ARITH_F16, 1>, (const void*)lstm2_g16_bwd_kernel<FSN_ARITH_BF16, 1>})
         if (!fsn_grid_fits(k, 256, 2u * (unsigned)cus)) return 0;
     const int cap = cus / QM, c = tiles / 4;
     return c < cap ? c : cap;
@@ -917,7 +872,7 @@ static int g16_launch_bptt(G16BwdArgs a, const float* w_hh1, const float* w_ih1,
     a.x1 = exchange;
     a.x0 = reinterpret_cast<unsigned char*>(exchange) + (size_t)clusters * QDX * q_xslot<AR>();
     const dim3 grid((unsigned)clusters * QM * 2), block(256);
-    if (saves16) FSN_PERSIST_LAUNCH((lstm2_g16_bwd_kernel<AR, 0, 1>), grid, block, s, a);
+    if (saves16) FSN_PERSIST_LAUNCH((lstm2_g16_bwd_kernel<AR, 1>), grid, block, s, a);
     else FSN_PERSIST_LAUNCH(lstm2_g16_bwd_kernel<AR>, grid, block, s, a);
     return fsn_check_launch("lstm2_g16_bwd_kernel");
 }
@@ -972,8 +927,8 @@ int fsn_launch_lstm2_g16_train(const float* x, int I, int Nrows, const float* w_
     a.Nrows = Nrows;
     const dim3 grid((unsigned)clusters * QM * 2), block(256);
     if (saves16) {
-        if (arith == FSN_ARITH_F16) FSN_PERSIST_LAUNCH((lstm2_g16_fwd_kernel<FSN_ARITH_F16, 0, 1>), grid, block, s, a);
-        else FSN_PERSIST_LAUNCH((lstm2_g16_fwd_kernel<FSN_ARITH_BF16, 0, 1>), grid, block, s, a);
+        if (arith == FSN_ARITH_F16) FSN_PERSIST_LAUNCH((lstm2_g16_fwd_kernel<FSN_ARITH_F16, 1>), grid, block, s, a);
+        else FSN_PERSIST_LAUNCH((lstm2_g16_fwd_kernel<FSN_ARITH_BF16, 1>), grid, block, s, a);
     } else {
         if (arith == FSN_ARITH_F16) FSN_PERSIST_LAUNCH(lstm2_g16_fwd_kernel<FSN_ARITH_F16>, grid, block, s, a);
         else FSN_PERSIST_LAUNCH(lstm2_g16_fwd_kernel<FSN_ARITH_BF16>, grid, block, s, a);

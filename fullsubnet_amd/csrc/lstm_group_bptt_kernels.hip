@@ -20,17 +20,14 @@
 //   - flags / bounded spins / status exactly as in lstm_group_kernels.hip.
 #include "fsn_common.h"
 
-#ifndef FSN_BPTT_A_AUX
-// 16: sc1 loads of the A operand (never cached: 0.3 GB per step through the fabric); 0: ordinary loads after an
-// agent-scope acquire (buffer_inv sc1), shared through the XCD's L2 - measured slower (48.5 against 47.1 ms per training
-// step: the invalidates of 64 workgroups per XCD and step take the weights out of the L2 as well)
-#define FSN_BPTT_A_AUX 16
-#ifndef FSN_BPTT_TURN
-#define FSN_BPTT_TURN 2  // x 4 chunks = A fragments in flight (must divide 24 stages); measured: 2 -> 12.5 ms, 3 -> 12.9, 4 -> 13.2
-#endif
-#endif
-
 namespace {
+
+// sc1 loads of the A operand (never cached: 0.3 GB per step through the fabric).  Ordinary loads after an agent-scope
+// acquire (buffer_inv sc1), shared through the XCD's L2, measured slower (48.5 against 47.1 ms per training step: the
+// invalidates of 64 workgroups per XCD and step take the weights out of the L2 as well)
+constexpr int BPTT_A_AUX = 16;
+constexpr int BPTT_TURN = 2;    // x 4 chunks = A fragments in flight (must divide 24 stages); measured: 2 -> 12.5 ms, 3 -> 12.9, 4 -> 13.2
+constexpr int BPTT_TURN16 = 2;  // the same under the 16-bit arithmetic (the K loop is 8x shorter: the A operand's latency shows)
 
 constexpr int BH = 384;           // hidden units (both layers)
 constexpr int BG = 4 * BH;        // gate columns = K of every product
@@ -38,13 +35,7 @@ constexpr int BKC = BG / 16;      // K chunks (96)
 constexpr int BM = 8;             // members per cluster and layer
 constexpr int BU = BH / 16 / BM;  // 16-unit groups per member (3)
 constexpr int BROWS = 64;         // rows per cluster
-#ifndef FSN_BPTT_TURN16
-#define FSN_BPTT_TURN16 2  // the same under the 16-bit arithmetic (the K loop is 8x shorter: the A operand's latency shows)
-#endif
-#ifndef FSN_BPTT_BCH
-#define FSN_BPTT_BCH 4  // probe: 4 -> 12.8 ms, 6 -> 13.0
-#endif
-constexpr int BCH = FSN_BPTT_BCH;  // K chunks per LDS stage
+constexpr int BCH = 4;            // K chunks per LDS stage (probe: 4 -> 12.8 ms, 6 -> 13.0)
 constexpr int BFS = 32;           // words between flag groups (one cache line each)
 
 struct BpttArgs {
@@ -76,11 +67,8 @@ __device__ __forceinline__ bool bptt_poll(unsigned* flags8, unsigned epoch, unsi
     }
 }
 
-// ABL: experiment knob of tools/probe_bptt.hip (0 in the library; any bit set gives WRONG results): 1 no flag polling,
-// 2 no gate-gradient / dx stores, 4 A fragments not loaded, 8 saved activations not loaded, 16 plain instead of
-// write-through stores, 32 no tanhf in the cell derivative
 // AR: arithmetic of the products (fsn_mma_k16); everything stored stays fp32
-template <int LAYER, int ABL, int AR>
+template <int LAYER, int AR>
 __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int member,
                                           typename FsnWFrag<AR>::type (*bsh)[BCH * 2 * BU][64]) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -123,15 +111,14 @@ __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int me
     // a 69 us step), while behind sixteen chunks of buffered MFMA work the same wait is covered.
     auto kloop = [&](auto& acc, const __amdgpu_buffer_rsrc_t xr, unsigned b, unsigned b2, int n, auto&& mid) {
         constexpr int NT = (int)(sizeof(acc) / sizeof(f32x4));
-        constexpr int TURN = AR == FSN_ARITH_F32 ? FSN_BPTT_TURN : FSN_BPTT_TURN16;  // stages per turn of the A ring
+        constexpr int TURN = AR == FSN_ARITH_F32 ? BPTT_TURN : BPTT_TURN16;  // stages per turn of the A ring
         constexpr int AD = TURN * BCH;       // A fragments in flight (write-through data of other CUs: first touch is far)
         constexpr int NB = BU;       // B fragments a wave holds in registers at a time (NT = 6: fetched in two halves)
         f32x4 ar[AD];
         typename FsnWFrag<AR>::type bn[NB];
         auto fetch_a = [&](int k) -> f32x4 {
             const int kc = k < n ? k : n - 1;
-            if (ABL & 4) return f32x4{0.5f, 0.25f, -0.125f, 0.0625f};
-            return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, a_off, (unsigned)kc * 64u, FSN_BPTT_A_AUX));
+            return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, a_off, (unsigned)kc * 64u, BPTT_A_AUX));
         };
         // Stage s holds chunks BCH s .. BCH s + BCH - 1, fragment (c, u) at index c NT + u.  The BCH NT fragments of a
         // stage are fetched in batches of NB (the registers a wave spends on them): batch id = fragments NB id ..;
@@ -205,13 +192,8 @@ __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int me
         return v;
     };
     auto wait_peeked = [&](unsigned v, unsigned* flags8, unsigned epoch) {
-        if (wave == 0 && !(ABL & 1) && !__all((int)(v >= epoch))) (void)bptt_poll(flags8, epoch, a.status, a.spin_ticks);
+        if (wave == 0 && !__all((int)(v >= epoch))) (void)bptt_poll(flags8, epoch, a.status, a.spin_ticks);
         __syncthreads();
-#if FSN_BPTT_A_AUX == 0
-        // agent-scope acquire (buffer_inv sc1): the A operand is then read with ordinary loads, which the 16 workgroups
-        // of a cluster - on one XCD when the grid allows it - share through that XCD's L2
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
     };
     auto publish = [&](unsigned* flag, unsigned epoch) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -220,9 +202,7 @@ __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int me
     };
 
     auto gstore = [&](const __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float v) {
-        if (ABL & 2) return;
-        if (ABL & 16) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
-        else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 16);  // sc1: write-through
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 16);  // sc1: write-through
     };
     const float* gates = LAYER ? a.gates1 : a.gates0;
     const float* cseq = LAYER ? a.cseq1 : a.cseq0;
@@ -253,11 +233,11 @@ __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int me
                 for (int i = 0; i < 4; ++i) {
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
-                        e_g[u][i][g] = (ABL & 8) ? 0.4f : ldf(rg, voff_g, (unsigned)((i * BG + g * BH + u * 16) * 4));
+                        e_g[u][i][g] = ldf(rg, voff_g, (unsigned)((i * BG + g * BH + u * 16) * 4));
                     const unsigned so = (unsigned)((i * BH + u * 16) * 4);
-                    e_ct[u][i] = (ABL & 8) ? 0.3f : ldf(rc, voff_h, so);
-                    e_cp[u][i] = (ABL & 8) ? 0.2f : (t > 0 ? ldf(rp, voff_h, so) : 0.f);
-                    e_dh[u][i] = (ABL & 8) ? 0.1f : (LAYER ? ldf(rd, voff_h, so) : 0.f);
+                    e_ct[u][i] = ldf(rc, voff_h, so);
+                    e_cp[u][i] = t > 0 ? ldf(rp, voff_h, so) : 0.f;
+                    e_dh[u][i] = LAYER ? ldf(rd, voff_h, so) : 0.f;
                 }
         };
         f32x4 acc[BU];
@@ -310,7 +290,7 @@ __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int me
                 for (int i = 0; i < 4; ++i) {
                     const float ig = e_g[u][i][0], fg = e_g[u][i][1], gg = e_g[u][i][2], og = e_g[u][i][3];
                     const float dh = e_dh[u][i] + acc[u][i];
-                    const float tc = (ABL & 32) ? e_ct[u][i] : tanhf(e_ct[u][i]);
+                    const float tc = tanhf(e_ct[u][i]);
                     const float d_o = dh * tc;
                     const float dct = dc[u][i] + dh * og * (1.f - tc * tc);
                     const unsigned so = (unsigned)((i * BG + u * 16) * 4);
@@ -325,7 +305,7 @@ __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int me
     }
 }
 
-template <int ABL, int AR = FSN_ARITH_F32>
+template <int AR>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(116))) void lstm2_group_bptt_kernel(const BpttArgs a) {
     __shared__ typename FsnWFrag<AR>::type bsh[2][BCH * 2 * BU][64];  // two stages x (4 chunks x up to 6 column tiles) x 1 KB (512 B in 16 bits)
     // first half of the grid: layer 1 (the leading chain), second half: layer 0; cluster members on one XCD when the
@@ -345,9 +325,9 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(116))) void 
     }
     if (!second) {
         __builtin_amdgcn_s_setprio(2);  // layer 1 is the longer chain (six tiles per A fragment against three)
-        bptt_body<1, ABL, AR>(a, cluster, member, bsh);
+        bptt_body<1, AR>(a, cluster, member, bsh);
     } else {
-        bptt_body<0, ABL, AR>(a, cluster, member, bsh);
+        bptt_body<0, AR>(a, cluster, member, bsh);
     }
 }
 
@@ -360,8 +340,8 @@ int fsn_lstm2_group_bptt_clusters(int tiles) {
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
         return 0;
     // residency contract: two workgroups per CU, by the compiled kernel's occupancy
-    for (const void* k : {(const void*)lstm2_group_bptt_kernel<0>, (const void*)lstm2_group_bptt_kernel<0, FSN_ARITH_F16>,
-                          (const void*)lstm2_group_bptt_kernel<0, FSN_ARITH_BF16>})
+    for (const void* k : {(const void*)lstm2_group_bptt_kernel<FSN_ARITH_F32>, (const void*)lstm2_group_bptt_kernel<FSN_ARITH_F16>,
+                          (const void*)lstm2_group_bptt_kernel<FSN_ARITH_BF16>})
         if (!fsn_grid_fits(k, 256, 2u * (unsigned)cus)) return 0;
     const int cap = cus / BM, c = tiles / 4;
     return c < cap ? c : cap;
@@ -410,9 +390,9 @@ int fsn_launch_lstm2_group_bptt(const float* dh1, const float* whh1T_p, const fl
     a.Tp = Tp;
     a.Nrows = Nrows;
     const dim3 grid((unsigned)clusters * BM * 2), block(256);
-    if (arith == FSN_ARITH_F16) FSN_PERSIST_LAUNCH((lstm2_group_bptt_kernel<0, FSN_ARITH_F16>), grid, block, s, a);
-    else if (arith == FSN_ARITH_BF16) FSN_PERSIST_LAUNCH((lstm2_group_bptt_kernel<0, FSN_ARITH_BF16>), grid, block, s, a);
-    else if (arith == FSN_ARITH_F32) FSN_PERSIST_LAUNCH(lstm2_group_bptt_kernel<0>, grid, block, s, a);
+    if (arith == FSN_ARITH_F16) FSN_PERSIST_LAUNCH(lstm2_group_bptt_kernel<FSN_ARITH_F16>, grid, block, s, a);
+    else if (arith == FSN_ARITH_BF16) FSN_PERSIST_LAUNCH(lstm2_group_bptt_kernel<FSN_ARITH_BF16>, grid, block, s, a);
+    else if (arith == FSN_ARITH_F32) FSN_PERSIST_LAUNCH(lstm2_group_bptt_kernel<FSN_ARITH_F32>, grid, block, s, a);
     else {
         fsn_set_error("lstm2_group_bptt: arithmetic %d unknown", arith);
         return FSN_ERR_ARG;

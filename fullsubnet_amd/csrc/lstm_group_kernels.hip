@@ -27,47 +27,25 @@
 // wave per SIMD hides none of its own latencies.  profiles/r06_duo_probe.md.)
 #include "fsn_common.h"
 
-#ifndef FSN_GRP_AD
-#define FSN_GRP_AD 6        // A fragments in flight (probe, 32 clusters: 4 -> 11.34 ms, 6 -> 11.2, 8 -> 11.4 with spills)
-#endif
-#ifndef FSN_GRP_CPS
-#define FSN_GRP_CPS 2       // K chunks per LDS stage of the weight fragments = per workgroup barrier (probe: 1 -> 11.09 ms, 2 -> 10.88)
-#endif
-#ifndef FSN_GRP_CPS16
-#define FSN_GRP_CPS16 4     // the same under the 16-bit arithmetic: fragments are half as large and a chunk is 8x fewer MFMA cycles
-#endif
-#ifndef FSN_GRP_AD16
-#define FSN_GRP_AD16 8      // a multiple of FSN_GRP_CPS16
-#endif
-#ifndef FSN_GRP_VGPR
-#define FSN_GRP_VGPR 108    // register cap of the two-workgroups-per-CU forms
-#endif
-#ifndef FSN_GRP_BOOST
-#define FSN_GRP_BOOST 12    // experiment (ABL 8192): first chunk of layer 0's K loop at the raised priority
-#endif
-#ifndef FSN_GRP_LEAD
-#define FSN_GRP_LEAD 2      // experiment (ABL 2048)
-#endif
-#ifndef FSN_GRP_D0
-#define FSN_GRP_D0 4
-#endif
-#ifndef FSN_GRP_BIAS_LDS
-#define FSN_GRP_BIAS_LDS 1  // biases in LDS also with one cluster per workgroup set (frees 12 registers for the ring)
-#endif
-
 namespace {
 
+constexpr int GRP_AD = 6;      // A fragments in flight (probe, 32 clusters: 4 -> 11.34 ms, 6 -> 11.2, 8 -> 11.4 with spills)
+constexpr int GRP_CPS = 2;     // K chunks per LDS stage of the weight fragments = per workgroup barrier (probe: 1 -> 11.09 ms, 2 -> 10.88)
+constexpr int GRP_CPS16 = 4;   // the same under the 16-bit arithmetic: fragments are half as large and a chunk is 8x fewer MFMA cycles
+constexpr int GRP_AD16 = 8;    // a multiple of GRP_CPS16
+constexpr int GRP_VGPR = 108;  // register cap of the two-workgroups-per-CU forms
+
 template <int AR>
-constexpr int grp_cps() { return AR == FSN_ARITH_F32 ? FSN_GRP_CPS : FSN_GRP_CPS16; }
+constexpr int grp_cps() { return AR == FSN_ARITH_F32 ? GRP_CPS : GRP_CPS16; }
 template <int AR>
-constexpr int grp_ad() { return AR == FSN_ARITH_F32 ? FSN_GRP_AD : FSN_GRP_AD16; }
+constexpr int grp_ad() { return AR == FSN_ARITH_F32 ? GRP_AD : GRP_AD16; }
 
 constexpr int GH = 384;          // hidden units (both layers)
 constexpr int GKC = GH / 16;     // K chunks of an H-wide operand
 constexpr int GM = 8;            // members per cluster and layer
 constexpr int GU = GH / 16 / GM; // unit groups per member (3)
 constexpr int GROWS = 64;        // rows per cluster
-constexpr int GD0 = FSN_GRP_D0;           // depth of layer 0's exchange buffer: layer 0 may run GD0 - 2 steps ahead of layer 1
+constexpr int GD0 = 4;          // depth of layer 0's exchange buffer: layer 0 may run GD0 - 2 steps ahead of layer 1
 constexpr int GFS = 32;          // words between the flag groups of (cluster, layer): one 128-byte line each
 
 struct GrpArgs {
@@ -95,7 +73,6 @@ struct GrpArgs {
     // cluster's missing 16-row tiles load a valid tile's rows and store nothing)
     const float* gx;
     int gx_tiles;
-    unsigned long long* dbg;  // tools/probe_group.hip's timeline (ABL 4096): [layer][member][Tp + 1][8] clock stamps of cluster 0
 };
 
 // Several weight sets in one launch (GX form): the sections of improved_fullsubnet/model.py:402-449 are independent
@@ -134,10 +111,6 @@ __device__ __forceinline__ bool grp_poll(unsigned* flags8, unsigned epoch, unsig
     }
 }
 
-// ABL: experiment knob of tools/probe_group.hip (0 in the library; any bit set gives WRONG results): 1 no acquire
-// fence, 2 no flag polling, 4 plain instead of write-through stores, 8 no gate non-linearities, 16 no output layer,
-// 32 A fragments not loaded (a constant instead), 128 weight fragments not loaded, 256 no LDS stage of the weight fragments
-// (operands from registers, no K-loop barriers), 512 members (not clusters) share an XCD.
 // What a workgroup keeps per cluster.  A workgroup serves one cluster, or TWO alternately (batches of 9 - 16 utterances:
 // more clusters than the chip holds at once): step t of cluster A, step t of cluster B, step t + 1 of A ... - while it
 // works on one cluster the partners' flags and write-through data of the other are on their way.
@@ -159,22 +132,13 @@ struct GrpCl {
 // SAVE (with TRAIN): also keep the activated gates and cell states (the training forward)
 // AR: arithmetic of the products (fsn_mma_k16: FSN_ARITH_F32, or 16-bit operands with fp32 accumulation for autocast
 // training); data movement and everything stored are the same in every mode
-template <int LAYER, int ABL, bool TRAIN, int NCL, bool SAVE, int AR, bool GX = false>
+template <int LAYER, bool TRAIN, int NCL, bool SAVE, int AR, bool GX = false>
 __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int cluster_b, int member,
                                            typename FsnWFrag<AR>::type (*bsh)[GU * 4 * grp_cps<AR>()][64], float (*bias_sh)[16]) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lr = lane & 15, lq = lane >> 4;
     const int Tp = a.Tp;
     const FsnSbInput& x = a.xin;
-    auto stamp = [&](int cl, int t, int e) {
-        if constexpr ((ABL & 4096) != 0) {
-            if (cl == 0 && threadIdx.x == 0) {
-                __builtin_amdgcn_sched_barrier(0);
-                a.dbg[(((size_t)LAYER * GM + member) * (Tp + 1) + t) * 8 + e] = (unsigned long long)wall_clock64();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
     // byte offset of the tile that holds h0_t / h1_t inside hx0 / hx1
     const unsigned step_bytes = TRAIN ? (unsigned)a.Nrows * GH * 4u : 0u;
     auto slot0 = [&](int t) { return TRAIN ? (unsigned)t * step_bytes : (unsigned)((t % GD0) * GROWS * GH * 4); };
@@ -209,23 +173,16 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 16));  // aux 16 = sc1
     };
 
-    // biases of this member's 12 column tiles: registers, or LDS when the workgroup keeps two clusters' state (12
-    // registers decide between fitting and spilling there; with one cluster the registers are faster)
-    constexpr bool kBiasLds = NCL > 1 || FSN_GRP_BIAS_LDS;
-    float bias[GU][4];
+    // biases of this member's 12 column tiles: in LDS (12 registers decide between fitting and spilling when the
+    // workgroup keeps two clusters' state, and with one cluster they are better spent on the A ring)
     if (GX && LAYER == 0) {
         // the projection tiles carry layer 0's bias
-    } else if (kBiasLds) {
+    } else {
         if (threadIdx.x < GU * 4 * 16) {
             const int f = threadIdx.x >> 4, u = f >> 2, g = f & 3, l = threadIdx.x & 15;
             bias_sh[f][l] = (LAYER ? a.bias1 : a.xin.bias)[(g * GKC + member * GU + u) * 16 + l];
         }
         __syncthreads();
-    } else {
-#pragma unroll
-        for (int u = 0; u < GU; ++u)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) bias[u][g] = (LAYER ? a.bias1 : a.xin.bias)[(g * GKC + member * GU + u) * 16 + lr];
     }
 
     // ---- K loop: acc += A(16 rows x 16 n) B(16 n x [3 unit groups x 4 gates x 16]) over two operand segments -------
@@ -250,15 +207,6 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
         typename FsnWFrag<AR>::type bn[GU];
         auto fetch_a = [&](int k) -> f32x4 {
             const int kc = k < n ? k : n - 1;
-            if (ABL & 32) return f32x4{0.5f, 0.25f, 0.125f, 0.0625f};
-            if constexpr ((ABL & 16384) != 0) {  // experiment (wrong data): a wave's fragment as ONE contiguous 1 KB block of the tile
-                const unsigned fo = (unsigned)lane * 16u, blk = (unsigned)wave * 1024u;
-                if (kc < n1) {
-                    if (xa) return kc == 0 ? xa[0] : xa[1];
-                    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r1, fo, at1 + (unsigned)kc * 4096u + blk, 16));
-                }
-                return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r2, fo, at2 + (unsigned)(kc - n1) * 4096u + blk, 16));
-            }
             if (kc < n1) {
                 if (xa) return kc == 0 ? xa[0] : xa[1];
                 return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r1, a_off, at1 + (unsigned)kc * 64u, 16));
@@ -274,8 +222,7 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
             for (int j = 0; j < GU; ++j) {
                 const int f = wave * GU + j, u = f >> 2, g = f & 3;
                 const unsigned ofs = bb + ((unsigned)(g * GKC + member * GU + u) * cs + (unsigned)kk) * 256u;
-                if constexpr ((ABL & 128) != 0 && AR == FSN_ARITH_F32) bn[j] = f32x4{0.01f, 0.02f, -0.01f, 0.005f};
-                else bn[j] = fsn_load_wfrag<AR>(wrsrc, (unsigned)lane, ofs);
+                bn[j] = fsn_load_wfrag<AR>(wrsrc, (unsigned)lane, ofs);
             }
         };
 #pragma unroll
@@ -286,14 +233,10 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
         for (int c = 0; c < CPS; ++c) {
             fetch_b(c);
 #pragma unroll
-            for (int j = 0; j < GU; ++j)
-                if (!(ABL & 256)) bsh[0][c * GU * 4 + wave * GU + j][lane] = bn[j];
+            for (int j = 0; j < GU; ++j) bsh[0][c * GU * 4 + wave * GU + j][lane] = bn[j];
         }
-        if (!(ABL & 256)) __syncthreads();
+        __syncthreads();
         for (int k0 = 0; k0 < n; k0 += AD) {
-            if constexpr ((ABL & 8192) != 0 && LAYER == 0) {  // experiment: layer 0 issues first in the tail of its K loop
-                if (k0 == FSN_GRP_BOOST) __builtin_amdgcn_s_setprio(3);
-            }
 #pragma unroll
             for (int d = 0; d < AD; ++d) {
                 const int k = k0 + d;
@@ -301,24 +244,15 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
                     const int c = d % CPS, buf = (k / CPS) & 1;
                     __builtin_amdgcn_sched_barrier(0);  // requests first, pinned under this chunk's MFMAs
                     const f32x4 av = ar[d];
-                    if constexpr ((ABL & 32768) != 0) {  // experiment: the A request first (the wait for the weight fragments then covers it)
-                        ar[d] = fetch_a(k + AD);
-                        __builtin_amdgcn_sched_barrier(0);
-                        fetch_b(k + CPS);
-                    } else {
-                        fetch_b(k + CPS);                   // the same chunk of the next stage
-                        ar[d] = fetch_a(k + AD);
-                    }
+                    fetch_b(k + CPS);  // the same chunk of the next stage
+                    ar[d] = fetch_a(k + AD);
                     __builtin_amdgcn_sched_barrier(0);
                     if constexpr (AR == FSN_ARITH_F32) {
 #pragma unroll
                         for (int u = 0; u < GU; ++u) {
                             f32x4 b[4];
 #pragma unroll
-                            for (int g = 0; g < 4; ++g) {
-                                if constexpr ((ABL & 256) != 0) b[g] = bn[(u + g) % GU];
-                                else b[g] = bsh[buf][c * GU * 4 + u * 4 + g][lane];
-                            }
+                            for (int g = 0; g < 4; ++g) b[g] = bsh[buf][c * GU * 4 + u * 4 + g][lane];
 #pragma unroll
                             for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -333,13 +267,12 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
                                 acc[u][g] = fsn_mma_k16<AR>(ao, fsn_wfrag_operand<AR>(bsh[buf][c * GU * 4 + u * 4 + g][lane]), acc[u][g]);
                     }
 #pragma unroll
-                    for (int j = 0; j < GU; ++j)
-                        if (!(ABL & 256)) bsh[buf ^ 1][c * GU * 4 + wave * GU + j][lane] = bn[j];
-                    if (c == CPS - 1 && !(ABL & 256)) __syncthreads();
+                    for (int j = 0; j < GU; ++j) bsh[buf ^ 1][c * GU * 4 + wave * GU + j][lane] = bn[j];
+                    if (c == CPS - 1) __syncthreads();
                 }
             }
         }
-        if (n % CPS && !(ABL & 256)) __syncthreads();  // a last, partial stage (layer 0's 2 + 24 chunks at four per stage): close it as well
+        if (n % CPS) __syncthreads();  // a last, partial stage (layer 0's 2 + 24 chunks at four per stage): close it as well
     };
 
     // Flags are looked at EARLY (before a K loop) and checked after it: in the steady state the early look already
@@ -351,7 +284,7 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
         return v;
     };
     auto wait_peeked = [&](unsigned v, unsigned* flags8, unsigned epoch) {
-        if (wave == 0 && !(ABL & 2) && !__all((int)(v >= epoch))) (void)grp_poll(flags8, epoch, a.status, a.spin_ticks);
+        if (wave == 0 && !__all((int)(v >= epoch))) (void)grp_poll(flags8, epoch, a.status, a.spin_ticks);
         __syncthreads();  // one wave looked for all four
     };
     // h slice of this step is in flight (write-through): every wave drains, then one lane bumps the flag
@@ -366,20 +299,14 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
         for (int u = 0; u < GU; ++u)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                float ig, fg, gg, og;
-                if (ABL & 8) {
-                    ig = acc[u][0][i], fg = acc[u][1][i], gg = acc[u][2][i], og = acc[u][3][i];
-                } else {
-                    ig = sigmoid_fast(acc[u][0][i]), fg = sigmoid_fast(acc[u][1][i]);
-                    gg = tanh_fast(acc[u][2][i]), og = sigmoid_fast(acc[u][3][i]);
-                }
+                const float ig = sigmoid_fast(acc[u][0][i]), fg = sigmoid_fast(acc[u][1][i]);
+                const float gg = tanh_fast(acc[u][2][i]), og = sigmoid_fast(acc[u][3][i]);
                 const float cn = fg * k.c[u][i] + ig * gg;
                 k.c[u][i] = cn;
                 float* hp = hdst + (size_t)(wave * 16 + 4 * lq + i) * GH + (member * GU + u) * 16 + lr;
-                const float hv = (ABL & 8) ? og * cn : og * tanh_fast(cn);
+                const float hv = og * tanh_fast(cn);
                 if (GX && !k.tile_ok) continue;
-                if (ABL & 4) *hp = hv;
-                else store_sc1(hp, hv);
+                store_sc1(hp, hv);
                 if (TRAIN && SAVE) {  // kept in place of the pre-activations for save_cell (after the hand-off)
                     acc[u][0][i] = ig, acc[u][1][i] = fg, acc[u][2][i] = gg, acc[u][3][i] = og;
                 }
@@ -410,7 +337,6 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
             // requested now, divided after the wait below
             float raw[8];
             f32x4 acc[GU][4];
-            stamp(k.cluster, t, 0);
             const float den = (k.row_ok && !TRAIN) ? x.den[x.den_mode ? (long)t * x.den_stride + k.ng : (long)k.xb] : 1.f;
             if (GX) {  // the projection tiles of this wave's rows at frame t (bias included): requested before the wait
                 const int tile = k.cluster * (GROWS / 16) + (k.tile_ok ? wave : 0);
@@ -440,7 +366,6 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
                 }
             }
             if (t > 0) wait_peeked(peek(k.fl0), k.fl0, (unsigned)t);  // h0_{t-1} of all members (just published: polls)
-            stamp(k.cluster, t, 1);
             f32x4 xa[2];
             if (!GX) {
 #pragma unroll
@@ -453,33 +378,19 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
                 for (int u = 0; u < GU; ++u)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const float b = kBiasLds ? bias_sh[u * 4 + g][lr] : bias[u][g];
+                        const float b = bias_sh[u * 4 + g][lr];
                         acc[u][g] = f32x4{b, b, b, b};
                     }
             }
             const unsigned ring = t >= GD0 ? peek(k.fl1) : 0xffffffffu;
-            if constexpr ((ABL & 2048) != 0) {  // experiment: layer 0 issues first while it is less than two steps ahead
-                unsigned v = lane < GM ? __hip_atomic_load(k.fl1 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
-                v = min(v, (unsigned)__shfl_xor((int)v, 1, 64));
-                v = min(v, (unsigned)__shfl_xor((int)v, 2, 64));
-                v = min(v, (unsigned)__shfl_xor((int)v, 4, 64));
-                const int done1 = __builtin_amdgcn_readfirstlane((int)v);  // steps layer 1 has published
-                if (t - done1 < FSN_GRP_LEAD) __builtin_amdgcn_s_setprio(2);
-                else __builtin_amdgcn_s_setprio(0);
-            }
             if (!GX) kloop(acc, xa, k.xrsrc0, 0, a.o_wih0, 2, 2, k.xrsrc0, t > 0 ? slot0(t - 1) : 0u, a.o_whh0, GKC, t > 0 ? GKC : 0);
             else if (t > 0) kloop(acc, nullptr, k.xrsrc0, 0, 0, 0, 0, k.xrsrc0, slot0(t - 1), a.o_whh0, GKC, GKC);
             // slot t % GD0 still holds h0_{t-GD0}: layer 1 must have finished its step t - GD0 (it reads that slot
             // there) - all eight layer-1 members, i.e. they have published step t - GD0 + 1
-            stamp(k.cluster, t, 2);
             if (t >= GD0) wait_peeked(ring, k.fl1, (unsigned)(t - GD0 + 1));
-            stamp(k.cluster, t, 3);
             cell(k, acc, reinterpret_cast<float*>(reinterpret_cast<char*>(k.hx0) + slot0(t)),
                  TRAIN ? a.gates0 + (size_t)t * a.Nrows * 4 * GH : nullptr, TRAIN ? a.cseq0 + (size_t)t * a.Nrows * GH : nullptr);
-            stamp(k.cluster, t, 4);
             publish(k.fl0 + member, (unsigned)t + 1);
-            if constexpr ((ABL & 8192) != 0) __builtin_amdgcn_s_setprio(0);
-            stamp(k.cluster, t, 5);
             if (TRAIN && SAVE) save_cell(k, acc, a.gates0 + (size_t)t * a.Nrows * 4 * GH, a.cseq0 + (size_t)t * a.Nrows * GH);
         };
         GrpCl ka, kb;
@@ -500,30 +411,26 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
             // iteration s = Tp only computes the output layer of the last step.
             f32x4 acc[GU][4];
             unsigned seen1 = 0xffffffffu;
-            stamp(k.cluster, s, 0);
             if (s < Tp) {
                 wait_peeked(k.seen0, k.fl0, (unsigned)s + 1);
-                stamp(k.cluster, s, 1);
                 seen1 = peek(k.fl1);
 #pragma unroll
                 for (int u = 0; u < GU; ++u)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const float b = kBiasLds ? bias_sh[u * 4 + g][lr] : bias[u][g];
+                        const float b = bias_sh[u * 4 + g][lr];
                         acc[u][g] = f32x4{b, b, b, b};
                     }
                 kloop(acc, nullptr, k.xrsrc0, slot0(s), a.o_wih1, GKC, GKC, k.xrsrc0, 0, 0, 0, 0);
             } else {
                 seen1 = peek(k.fl1);
             }
-            stamp(k.cluster, s, 2);
             if (s > 0) {
                 wait_peeked(seen1, k.fl1, (unsigned)s);  // h1_{s-1} of all members
-                stamp(k.cluster, s, 3);
                 // Output layer (nn.Linear(384, 2)) of step s - 1 for rows 8 m .. 8 m + 7 of the cluster, from h1_{s-1} as
                 // it has just been gathered: 16 dot products x 16 threads (~1 us, covered by the layer-0 workgroup
                 // that shares the CU)
-                if (!(ABL & 16) && !TRAIN) {
+                if (!TRAIN) {
                     const unsigned hoff = (unsigned)((((s - 1) & 1) * GROWS * GH + frow * GH + p * 24) * 4);
                     f32x4 hv[6], fw[6];
 #pragma unroll
@@ -551,17 +458,13 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
                 }
             }
             k.seen0 = peek(k.fl0);  // for the next step: layer 0 is ahead, this usually shows s + 2 already
-            stamp(k.cluster, s, 4);
             if (s > 0 && s < Tp)
                 kloop(acc, nullptr, k.xrsrc1, slot1(s - 1), a.o_whh1, GKC, GKC, k.xrsrc1, 0, 0, 0, 0);
-            stamp(k.cluster, s, 5);
             if (s < Tp) {
                 // slot s & 1 held h1_{s-2}: read by every member in step s - 1, which they have left (flag1 >= s above)
                 cell(k, acc, reinterpret_cast<float*>(reinterpret_cast<char*>(k.hx1) + slot1(s)),
                      TRAIN ? a.gates1 + (size_t)s * a.Nrows * 4 * GH : nullptr, TRAIN ? a.cseq1 + (size_t)s * a.Nrows * GH : nullptr);
-                stamp(k.cluster, s, 6);
                 publish(k.fl1 + member, (unsigned)s + 1);
-                stamp(k.cluster, s, 7);
                 if (TRAIN && SAVE) save_cell(k, acc, a.gates1 + (size_t)s * a.Nrows * 4 * GH, a.cseq1 + (size_t)s * a.Nrows * GH);
             }
         };
@@ -579,8 +482,8 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
     }
 }
 
-template <int ABL, bool TRAIN = false, int NCL = 1, bool SAVE = TRAIN, int AR = FSN_ARITH_F32>
-__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(FSN_GRP_VGPR))) void lstm2_group_kernel(const GrpArgs a) {
+template <bool TRAIN = false, int NCL = 1, bool SAVE = TRAIN, int AR = FSN_ARITH_F32>
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(GRP_VGPR))) void lstm2_group_kernel(const GrpArgs a) {
     // weight fragments of one K chunk, shared by the four waves: two stages x 12 fragments x 1 KB
     __shared__ typename FsnWFrag<AR>::type bsh[2][GU * 4 * grp_cps<AR>()][64];
     __shared__ float bias_sh[GU * 4][16];
@@ -595,10 +498,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(FSN_GRP_VGPR
     const int bid = (int)blockIdx.x - layer * half;
     const int slots = half / GM;
     int slot, member;
-    if ((ABL & 512) && slots % 8 == 0) {
-        member = bid & 7;
-        slot = bid >> 3;
-    } else if (slots % 8 == 0) {
+    if (slots % 8 == 0) {
         const int xcd = bid & 7, j = bid >> 3;  // j-th block of that XCD
         slot = xcd * (slots / 8) + j / GM;
         member = j % GM;
@@ -609,19 +509,16 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(FSN_GRP_VGPR
     const int cluster = slot, cluster_b = slot + slots < a.nclusters ? slot + slots : -1;
     // Layer 1 is the longer dependent chain (K = 768 per step against 416) and layer 0 is throttled to stay within
     // GD0 - 2 steps of it: layer 1's waves issue first, layer 0's fill the gaps.
-    if ((ABL & 1024) && layer == 0) __builtin_amdgcn_s_setprio(2);
-    else if ((ABL & 2048) && layer == 1) __builtin_amdgcn_s_setprio(1);
-    else if (!(ABL & (1024 | 2048)) && layer == 1 && !(ABL & 64)) __builtin_amdgcn_s_setprio(2);
-    if (layer == 0) group_body<0, ABL, TRAIN, NCL, SAVE, AR>(a, cluster, cluster_b, member, bsh, bias_sh);
-    else group_body<1, ABL, TRAIN, NCL, SAVE, AR>(a, cluster, cluster_b, member, bsh, bias_sh);
+    if (layer == 1) __builtin_amdgcn_s_setprio(2);
+    if (layer == 0) group_body<0, TRAIN, NCL, SAVE, AR>(a, cluster, cluster_b, member, bsh, bias_sh);
+    else group_body<1, TRAIN, NCL, SAVE, AR>(a, cluster, cluster_b, member, bsh, bias_sh);
 }
 
 // Several independent two-layer stacks (weight sets) in one launch, GX form: workgroup set `slot` serves cluster `slot`
 // of the launch, which belongs to the set whose cluster range contains it.
-template <int ABL>
-__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(FSN_GRP_VGPR))) void lstm2_group_multi_kernel(const GrpArgs a0,
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(GRP_VGPR))) void lstm2_group_multi_kernel(const GrpArgs a0,
                                                                                                           const GrpSets sets) {
-    __shared__ typename FsnWFrag<FSN_ARITH_F32>::type bsh[2][GU * 4 * FSN_GRP_CPS][64];
+    __shared__ typename FsnWFrag<FSN_ARITH_F32>::type bsh[2][GU * 4 * GRP_CPS][64];
     __shared__ float bias_sh[GU * 4][16];
     const int half = gridDim.x >> 1;
     const int layer = (int)blockIdx.x >= half ? 1 : 0;
@@ -652,9 +549,9 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(FSN_GRP_VGPR
     a.Nrows = q.N;
     a.flags = a0.flags + (size_t)q.cluster0 * 2 * GFS;
     const int cluster = slot - q.cluster0;  // within the set
-    if (layer == 1 && !(ABL & 64)) __builtin_amdgcn_s_setprio(2);
-    if (layer == 0) group_body<0, ABL, true, 1, false, FSN_ARITH_F32, true>(a, cluster, -1, member, bsh, bias_sh);
-    else group_body<1, ABL, true, 1, false, FSN_ARITH_F32, true>(a, cluster, -1, member, bsh, bias_sh);
+    if (layer == 1) __builtin_amdgcn_s_setprio(2);
+    if (layer == 0) group_body<0, true, 1, false, FSN_ARITH_F32, true>(a, cluster, -1, member, bsh, bias_sh);
+    else group_body<1, true, 1, false, FSN_ARITH_F32, true>(a, cluster, -1, member, bsh, bias_sh);
 }
 
 }  // namespace
@@ -672,14 +569,14 @@ static int grp_slots_cap() {
         return 0;
     // residency contract: two workgroups per CU of EVERY form of the kernel (compiled occupancy, not an assumption)
     const unsigned grid = 2u * (unsigned)cus;
-    const void* forms[] = {(const void*)lstm2_group_kernel<0, false, 1>,      (const void*)lstm2_group_kernel<0, false, 2>,
-                           (const void*)lstm2_group_kernel<0, true, 1, true>, (const void*)lstm2_group_kernel<0, true, 2, true>,
-                           (const void*)lstm2_group_kernel<0, true, 1, false>, (const void*)lstm2_group_kernel<0, true, 2, false>,
-                           (const void*)lstm2_group_kernel<0, true, 1, true, FSN_ARITH_F16>,
-                           (const void*)lstm2_group_kernel<0, true, 2, true, FSN_ARITH_F16>,
-                           (const void*)lstm2_group_kernel<0, true, 1, true, FSN_ARITH_BF16>,
-                           (const void*)lstm2_group_kernel<0, true, 2, true, FSN_ARITH_BF16>,
-                           (const void*)lstm2_group_multi_kernel<0>};
+    const void* forms[] = {(const void*)lstm2_group_kernel<false, 1>,      (const void*)lstm2_group_kernel<false, 2>,
+                           (const void*)lstm2_group_kernel<true, 1, true>, (const void*)lstm2_group_kernel<true, 2, true>,
+                           (const void*)lstm2_group_kernel<true, 1, false>, (const void*)lstm2_group_kernel<true, 2, false>,
+                           (const void*)lstm2_group_kernel<true, 1, true, FSN_ARITH_F16>,
+                           (const void*)lstm2_group_kernel<true, 2, true, FSN_ARITH_F16>,
+                           (const void*)lstm2_group_kernel<true, 1, true, FSN_ARITH_BF16>,
+                           (const void*)lstm2_group_kernel<true, 2, true, FSN_ARITH_BF16>,
+                           (const void*)lstm2_group_multi_kernel};
     for (const void* k : forms)
         if (!fsn_grid_fits(k, 256, grid)) return 0;
     return cus / GM;
@@ -733,8 +630,8 @@ int fsn_launch_lstm2_group(const FsnSbInput* xin, const float* whh0_p, const flo
         fsn_set_error("lstm2_group: %d clusters cannot be co-resident on this device (persistent kernels off, or occupancy)", clusters);
         return FSN_ERR_ARG;
     }
-    if (clusters > slots) FSN_PERSIST_LAUNCH((lstm2_group_kernel<0, false, 2>), dim3((unsigned)slots * GM * 2), dim3(256), s, a);
-    else FSN_PERSIST_LAUNCH((lstm2_group_kernel<0, false, 1>), dim3((unsigned)slots * GM * 2), dim3(256), s, a);
+    if (clusters > slots) FSN_PERSIST_LAUNCH((lstm2_group_kernel<false, 2>), dim3((unsigned)slots * GM * 2), dim3(256), s, a);
+    else FSN_PERSIST_LAUNCH((lstm2_group_kernel<false, 1>), dim3((unsigned)slots * GM * 2), dim3(256), s, a);
     return fsn_check_launch("lstm2_group_kernel");
 }
 
@@ -799,17 +696,17 @@ int fsn_launch_lstm2_group_train(const float* x, long x_ld, int x_cols, int Nrow
     }
     const dim3 grid((unsigned)slots * GM * 2), block(256);
     if (save && arith == FSN_ARITH_F16) {
-        if (clusters > slots) FSN_PERSIST_LAUNCH((lstm2_group_kernel<0, true, 2, true, FSN_ARITH_F16>), grid, block, s, a);
-        else FSN_PERSIST_LAUNCH((lstm2_group_kernel<0, true, 1, true, FSN_ARITH_F16>), grid, block, s, a);
+        if (clusters > slots) FSN_PERSIST_LAUNCH((lstm2_group_kernel<true, 2, true, FSN_ARITH_F16>), grid, block, s, a);
+        else FSN_PERSIST_LAUNCH((lstm2_group_kernel<true, 1, true, FSN_ARITH_F16>), grid, block, s, a);
     } else if (save && arith == FSN_ARITH_BF16) {
-        if (clusters > slots) FSN_PERSIST_LAUNCH((lstm2_group_kernel<0, true, 2, true, FSN_ARITH_BF16>), grid, block, s, a);
-        else FSN_PERSIST_LAUNCH((lstm2_group_kernel<0, true, 1, true, FSN_ARITH_BF16>), grid, block, s, a);
+        if (clusters > slots) FSN_PERSIST_LAUNCH((lstm2_group_kernel<true, 2, true, FSN_ARITH_BF16>), grid, block, s, a);
+        else FSN_PERSIST_LAUNCH((lstm2_group_kernel<true, 1, true, FSN_ARITH_BF16>), grid, block, s, a);
     } else if (save) {
-        if (clusters > slots) FSN_PERSIST_LAUNCH((lstm2_group_kernel<0, true, 2, true>), grid, block, s, a);
-        else FSN_PERSIST_LAUNCH((lstm2_group_kernel<0, true, 1, true>), grid, block, s, a);
+        if (clusters > slots) FSN_PERSIST_LAUNCH((lstm2_group_kernel<true, 2, true>), grid, block, s, a);
+        else FSN_PERSIST_LAUNCH((lstm2_group_kernel<true, 1, true>), grid, block, s, a);
     } else {
-        if (clusters > slots) FSN_PERSIST_LAUNCH((lstm2_group_kernel<0, true, 2, false>), grid, block, s, a);
-        else FSN_PERSIST_LAUNCH((lstm2_group_kernel<0, true, 1, false>), grid, block, s, a);
+        if (clusters > slots) FSN_PERSIST_LAUNCH((lstm2_group_kernel<true, 2, false>), grid, block, s, a);
+        else FSN_PERSIST_LAUNCH((lstm2_group_kernel<true, 1, false>), grid, block, s, a);
     }
     return fsn_check_launch("lstm2_group_kernel (training)");
 }
@@ -866,6 +763,6 @@ int fsn_launch_lstm2_group_multi(int n, const FsnGroupStack* st, unsigned* flags
     a.spin_ticks = fsn_spin_ticks();
     a.Tp = Tp;
     a.nclusters = clusters;
-    FSN_PERSIST_LAUNCH((lstm2_group_multi_kernel<0>), dim3((unsigned)clusters * GM * 2), dim3(256), s, a, sets);
+    FSN_PERSIST_LAUNCH((lstm2_group_multi_kernel), dim3((unsigned)clusters * GM * 2), dim3(256), s, a, sets);
     return fsn_check_launch("lstm2_group_multi_kernel");
 }

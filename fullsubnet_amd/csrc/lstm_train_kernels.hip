@@ -159,8 +159,7 @@ __global__ __launch_bounds__(NW * 64) void bptt_step_kernel(const float* __restr
 // chunk: 16 lanes read 64 contiguous bytes of one k row, the row base is wave-uniform (SGPR) and
 // the lane part a fixed 32-bit offset.  Out-of-range columns are clamped on load and never stored.
 // AR: arithmetic of the products (fsn_mma_k16): the lane's four k of a chunk ARE the 16-bit instruction's operand.
-// ABL: experiment knob of tools/probe_tn.hip (0 in the library; a set bit gives WRONG results): 1 operands not loaded
-template <int RTW, int CTW, int WM, int WN, int AR = FSN_ARITH_F32, int PF = 2, int ABL = 0>
+template <int RTW, int CTW, int WM, int WN, int AR = FSN_ARITH_F32, int PF = 2>
 __global__ __launch_bounds__(256) void gemm_tn_kernel(const float* __restrict__ A, long lda,
                                                       const float* __restrict__ B, long ldb,
                                                       float* __restrict__ part, int M, int Nc, long K, long k_per_split,
@@ -217,9 +216,9 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const float* __restrict__ 
             const float* ar = a0 + ((long)kc * 16 + j) * lda;  // wave-uniform row bases
             const float* br = b0 + ((long)kc * 16 + j) * ldb;
 #pragma unroll
-            for (int i = 0; i < RTW; ++i) abuf[p][i][j] = (ABL & 1) ? 0.25f * (float)kc : ar[aoff[i]];
+            for (int i = 0; i < RTW; ++i) abuf[p][i][j] = ar[aoff[i]];
 #pragma unroll
-            for (int i = 0; i < CTW; ++i) bbuf[p][i][j] = (ABL & 1) ? 0.5f : br[boff[i]];
+            for (int i = 0; i < CTW; ++i) bbuf[p][i][j] = br[boff[i]];
         }
     };
     auto consume = [&](int p) {
@@ -673,14 +672,12 @@ TnPlan tn_plan(int M, int Nc, long K, int arith = FSN_ARITH_F32, bool allow_squa
     p.splits = (int)((K + p.k_per_split - 1) / p.k_per_split);
     return p;
 }
-#ifndef FSN_TN_PF32
-#define FSN_TN_PF32 2  // operand chunks in flight of the fp32 192 x 192 form (measured r04: 2 -> 3.76 ms, 3 -> 3.72: not latency-bound)
+constexpr int TN_PF32 = 2;  // operand chunks in flight of the fp32 192 x 192 form (measured r04: 2 -> 3.76 ms, 3 -> 3.72: not latency-bound)
 // (r04, tools/probe_tn.hip, profiles/r04_tn_probe.txt: without its operand loads this kernel's matrix stream runs at 0.98 of
 // the fp32 peak, 3.03 ms, with them at 0.80, 3.67.  Three LDS-staged forms of the same product - 16-byte row pieces through
 // registers with one / two chunks in flight, and by LDS-DMA with software-pipelined ds_read_b32 operands - measured 4.6 /
 // 4.2 / 3.67 ms: the staged form only reaches the register ring's time (its DMA costs 0.3 ms, its LDS reads 0.2, its
 // barrier 0.15), so the ring stays.)
-#endif
 
 // ---- layer 0's INPUT-side products from the 16-bit gate gradients (round 6) -------------------------------------------------
 // With these two the BPTT launch of the 16-bit arithmetic stores no fp32 gate gradients at all (2.45 GB less written per
@@ -953,7 +950,7 @@ static int gemm_tn_segment(const float* A, long lda, const float* B, long ldb, f
         } else if (p.square) {
             auto square = arith == FSN_ARITH_F16    ? gemm_tn_kernel<6, 6, 2, 2, FSN_ARITH_F16>
                           : arith == FSN_ARITH_BF16 ? gemm_tn_kernel<6, 6, 2, 2, FSN_ARITH_BF16>
-                                                    : gemm_tn_kernel<6, 6, 2, 2, FSN_ARITH_F32, FSN_TN_PF32>;
+                                                    : gemm_tn_kernel<6, 6, 2, 2, FSN_ARITH_F32, TN_PF32>;
             static bool sq_set[4] = {false, false, false, false};
             if (!sq_set[arith]) {
                 if (hipFuncSetAttribute(reinterpret_cast<const void*>(square), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1345,9 +1342,7 @@ __global__ __launch_bounds__(256) void bptt_step_cu_kernel(const float* __restri
         }
 }
 
-#ifndef FSN_BPTT_SPLIT16_TILES
-#define FSN_BPTT_SPLIT16_TILES 8  // measured (round 6, 5 tiles x 512 units, Fast FullSubNet's decoder at batch 72): see DESIGN 7.4
-#endif
+constexpr int BPTT_SPLIT16_TILES = 8;  // measured (round 6, 5 tiles x 512 units, Fast FullSubNet's decoder at batch 72): see DESIGN 7.4
 int fsn_launch_bptt_step(const float* dh_out, const float* dgates_next, const float* whhT_p, float* dc,
                          const float* gates, const float* c_t, const float* c_prev, float* dgates, int row_tiles, int H,
                          int last, int first, hipStream_t s) {
@@ -1366,7 +1361,7 @@ int fsn_launch_bptt_step(const float* dh_out, const float* dgates_next, const fl
     hipLaunchKernelGGL((bptt_step_kernel<R, C>), dim3(H / 16 / C, (row_tiles + R - 1) / R), dim3(256), 0, s, dh_out, \
                        dgates_next, whhT_p, dc, gates, c_t, c_prev, dgates, row_tiles, H, last, first)
     if (cfg == 22) FSN_BPTT_CASE(2, 2);
-    else if (row_tiles <= FSN_BPTT_SPLIT16_TILES && (4 * H / 16) % 16 == 0)  // a handful of rows (full-band model, the sibling models' blocks): 16-way split-K
+    else if (row_tiles <= BPTT_SPLIT16_TILES && (4 * H / 16) % 16 == 0)  // a handful of rows (full-band model, the sibling models' blocks): 16-way split-K
         hipLaunchKernelGGL((bptt_step_kernel<1, 1, 16>), dim3(H / 16, row_tiles), dim3(1024), 0, s, dh_out, dgates_next,
                            whhT_p, dc, gates, c_t, c_prev, dgates, row_tiles, H, last, first);
     else FSN_BPTT_CASE(1, 1);

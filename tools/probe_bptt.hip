@@ -1,5 +1,7 @@
-// Timing probe for lstm2_group_bptt_kernel (not part of the library): the shipped kernel and ablations (template
-// parameter ABL, see the kernel) on random operands at config 3's per-rank shape (2064 rows = 32 clusters + 16 rows).
+// Timing probe for lstm2_group_bptt_kernel (not part of the library): the shipped kernel stand-alone on random operands
+// at config 3's per-rank shape (2064 rows = 32 clusters + 16 rows).  The ablations that priced the kernel's ingredients
+// one at a time are on record in profiles/r02_bptt_probe.md and profiles/r03_bptt_probe_f16.md; the ablated variants
+// are in git history before the commit that retired the kernel's experiment switches.
 #include <cstdio>
 #include <cstdlib>
 #include "../fullsubnet_amd/csrc/lstm_group_bptt_kernels.hip"
@@ -20,14 +22,13 @@ __global__ void fill_kernel(float* p, size_t n, unsigned seed, float scale, floa
 #ifndef PROBE_AR
 #define PROBE_AR 0  // -DPROBE_AR=2 / 3: fp16 / bf16 matrix-core operands
 #endif
-template <int ABL>
 float run(BpttArgs a, int clusters) {
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     float best = 1e30f;
     for (int it = 0; it < 3; ++it) {
         hipMemsetAsync(a.flags, 0, fsn_lstm2_group_bptt_flag_words(clusters) * 4, 0);
         hipEventRecord(e0, 0);
-        hipLaunchKernelGGL((lstm2_group_bptt_kernel<ABL, PROBE_AR>), dim3(clusters * BM * 2), dim3(256), 0, 0, a);
+        hipLaunchKernelGGL((lstm2_group_bptt_kernel<PROBE_AR>), dim3(clusters * BM * 2), dim3(256), 0, 0, a);
         hipEventRecord(e1, 0); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1); if (it > 0 && ms < best) best = ms;
     }
@@ -49,20 +50,9 @@ int main(int argc, char** argv) {
     a.gates0 = sv0; a.cseq0 = sv0 + TN * BG; a.gates1 = sv1; a.cseq1 = sv1 + TN * BG; a.dg1 = dg; a.dg0 = dg + TN * BG; a.dx = dx;
     a.flags = flags; a.status = flags + (size_t)clusters * 2 * BFS; a.spin_ticks = 1ull << 31; a.Tp = Tp; a.Nrows = N;
     const double mfma_us = 2.0 * 64 * 48 * (3.0 * BG) / (64.0 * 4 * 2.4e3);  // per step and CU (one member of each layer) at 2.4 GHz
-    const float t0 = run<0>(a, clusters);
+    const float t0 = run(a, clusters);
     unsigned st = 0; hipMemcpy(&st, a.status, 4, hipMemcpyDeviceToHost);
     printf("arithmetic %d: ", PROBE_AR);
     printf("lstm2_group_bptt_kernel, %d clusters, %d steps: %.3f ms = %.1f us per step (MFMA alone %.1f us), status %u\n", clusters, Tp, t0, 1e3 * t0 / Tp, mfma_us, st);
-#define V(abl, what) { const float t = run<abl>(a, clusters); printf("  %-52s: %.3f ms = %.1f us per step\n", what, t, 1e3 * t / Tp); }
-    V(16, "plain instead of write-through stores");
-    V(2, "no gate-gradient / dx stores");
-    V(8, "saved activations not loaded");
-    V(32, "no tanhf");
-    V(4, "A fragments not loaded");
-    V(1, "no flag polling");
-    V(2 + 8, "no stores, no saved activations");
-    V(2 + 8 + 4, "... and no A loads");
-    V(1 + 2 + 8 + 4 + 32, "... no flags, no tanhf (K loops, barriers, B through LDS)");
-    V(0, "shipped again");
     return 0;
 }

@@ -1,5 +1,7 @@
-// Timing probe for fb_chain_kernel (not part of the library): the shipped kernel and ablations (template parameter
-// ABL, see the kernel) on random operands: where does a step of the full-band chain spend its time?
+// Timing probe for fb_chain_kernel (not part of the library): the shipped kernel stand-alone on random operands.  Where a
+// step of the full-band chain spends its time - the ablations that priced its ingredients one at a time - is on record in
+// profiles/r02_chain_probe.md; the ablated variants are in git history before the commit that retired the kernel's
+// experiment switches.
 #include <cstdio>
 #include <cstdlib>
 #include "../fullsubnet_amd/csrc/fb_chain_kernels.hip"
@@ -17,37 +19,24 @@ __global__ void fill_kernel(float* p, size_t n, unsigned seed, float scale, floa
         p[i] = ((x & 0xffff) / 32768.0f - 1.0f) * scale + offset;
     }
 }
-template <int KS, int ABL>
+template <int KS>
 float run(ChainArgs a) {
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     float best = 1e30f;
     for (int it = 0; it < 4; ++it) {
         hipMemsetAsync(a.flags, 0, fsn_fb_chain_flag_words() * 4, 0);
         hipEventRecord(e0, 0);
-        hipLaunchKernelGGL((fb_chain_kernel<512, KS, ABL>), dim3(2 * 128), dim3(256), 0, 0, a);
+        hipLaunchKernelGGL((fb_chain_kernel<512, KS>), dim3(2 * 128), dim3(256), 0, 0, a);
         hipEventRecord(e1, 0); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1); if (it > 0 && ms < best) best = ms;
     }
     return best;
 }
 template <int KS>
-void sweep(ChainArgs a, int Tp) {
-    const float t0 = run<KS, 0>(a);
+void report(ChainArgs a, int Tp) {
+    const float t0 = run<KS>(a);
     unsigned st = 0; hipMemcpy(&st, a.status, 4, hipMemcpyDeviceToHost);
     printf("fb_chain_kernel<KS=%d>, %d row tiles, %d steps: %.3f ms = %.2f us per step, status %u\n", KS, a.RT, Tp, t0, 1e3 * t0 / Tp, st);
-#define V(abl, what) { const float t = run<KS, abl>(a); printf("  %-46s: %.3f ms = %.2f us per step\n", what, t, 1e3 * t / Tp); }
-    V(16, "no drain before the flag store");
-    V(8, "plain instead of write-through stores");
-    V(2, "no h / gx1 stores");
-    V(64, "no layer-1 projection in L0");
-    V(1, "no flag polling");
-    V(1 + 32, "no flag polling, no flag stores");
-    V(1 + 32 + 16, "... and no drain");
-    V(1 + 32 + 16 + 2, "... and no h stores");
-    V(1 + 32 + 16 + 2 + 4, "... and no A loads (MFMA, cell, barriers)");
-    V(1 + 32 + 16 + 4, "no sync, no A loads, but h stores");
-    V(4, "no A loads only");
-#undef V
 }
 int main(int argc, char** argv) {
     const int Tp = argc > 1 ? atoi(argv[1]) : 190, Npad = argc > 2 ? atoi(argv[2]) : 64;
@@ -64,8 +53,8 @@ int main(int argc, char** argv) {
     a.gx0 = gx0; a.whh0_p = w; a.wih1_p = w + (size_t)4 * H * H; a.whh1_p = w + (size_t)8 * H * H; a.b1 = b1;
     a.hx0 = ex; a.hx1 = ex + (size_t)Tp * Npad * H; a.gx1 = ex + (size_t)2 * Tp * Npad * H; a.hseq1 = hseq;
     a.flags = flags; a.status = flags + fsn_fb_chain_status_word(); a.spin_ticks = 1ull << 31; a.Tp = Tp; a.RT = Npad / 16; a.Npad = Npad;
-    if (a.RT == 1) sweep<4>(a, Tp);
-    else if (a.RT == 2) sweep<2>(a, Tp);
-    else sweep<1>(a, Tp);
+    if (a.RT == 1) report<4>(a, Tp);
+    else if (a.RT == 2) report<2>(a, Tp);
+    else report<1>(a, Tp);
     return 0;
 }

@@ -1,6 +1,9 @@
 // Timing probe for the 16-bit arithmetic's group kernels (lstm_group16_kernels.hip; not part of the library): the shipped
-// kernels and ablations (template parameter ABL, see the kernels) on random operands at config 3's per-rank shape
-// (32 clusters of 64 rows, 195 / 193 steps).   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/probe_g16.hip -o tools/bin/probe_g16
+// kernels stand-alone on random operands at config 3's per-rank shape (32 clusters of 64 rows, 195 / 193 steps).  The
+// ablations that priced the kernels' ingredients one at a time are on record in profiles/r04_g16_probe_v1.txt,
+// profiles/r04_g16_probe_fwd_v2.txt, profiles/r04_g16_probe_bptt_v2.txt and profiles/r06_g16_placement_probe.md; the
+// ablated variants are in git history before the commit that retired the kernels' experiment switches.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/probe_g16.hip -o tools/bin/probe_g16
 #include <cstdio>
 #include <cstdlib>
 #include "../fullsubnet_amd/csrc/lstm_group16_kernels.hip"
@@ -25,27 +28,25 @@ __global__ void fill_kernel(float* p, size_t n, unsigned seed, float scale, floa
 #define PROBE_SV 0  // 1: the gates saved / the hand-off in 16 bits (FSN_ARITH_SAVES16, the default under AMP since round 6)
 #endif
 static unsigned* g_flags; static int g_clusters;
-template <int ABL>
 float run_fwd(G16FwdArgs a) {
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     float best = 1e30f;
     for (int it = 0; it < 3; ++it) {
         hipMemsetAsync(g_flags, 0, fsn_lstm2_g16_flag_words(g_clusters) * 4, 0);
         hipEventRecord(e0, 0);
-        hipLaunchKernelGGL((lstm2_g16_fwd_kernel<PROBE_AR, ABL, PROBE_SV>), dim3(g_clusters * QM * 2), dim3(256), 0, 0, a);
+        hipLaunchKernelGGL((lstm2_g16_fwd_kernel<PROBE_AR, PROBE_SV>), dim3(g_clusters * QM * 2), dim3(256), 0, 0, a);
         hipEventRecord(e1, 0); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1); if (it > 0 && ms < best) best = ms;
     }
     return best;
 }
-template <int ABL>
 float run_bwd(G16BwdArgs a) {
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     float best = 1e30f;
     for (int it = 0; it < 3; ++it) {
         hipMemsetAsync(g_flags, 0, fsn_lstm2_g16_flag_words(g_clusters) * 4, 0);
         hipEventRecord(e0, 0);
-        hipLaunchKernelGGL((lstm2_g16_bwd_kernel<PROBE_AR, ABL, PROBE_SV>), dim3(g_clusters * QM * 2), dim3(256), 0, 0, a);
+        hipLaunchKernelGGL((lstm2_g16_bwd_kernel<PROBE_AR, PROBE_SV>), dim3(g_clusters * QM * 2), dim3(256), 0, 0, a);
         hipEventRecord(e1, 0); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1); if (it > 0 && ms < best) best = ms;
     }
@@ -79,22 +80,9 @@ int main(int argc, char** argv) {
         a.o_hh1 = (unsigned)((p_d - p_a) * 2); a.bias0 = bias; a.bias1 = bias + QG; a.hseq0 = h0; a.hseq1 = h1;
         a.gates0 = sv0; a.cseq0 = sv0 + TN * QG; a.gates1 = sv1; a.cseq1 = sv1 + TN * QG; a.flags = flags;
         a.status = flags + fsn_lstm2_g16_status_word(clusters); a.spin_ticks = 1ull << 31; a.Tp = Tp; a.Nrows = N;
-        const float t0 = run_fwd<0>(a);
+        const float t0 = run_fwd(a);
         unsigned st = 0; hipMemcpy(&st, a.status, 4, hipMemcpyDeviceToHost);
         printf("arithmetic %d: lstm2_g16_fwd_kernel, %d clusters, %d steps: %.3f ms = %.1f us per step, status %u\n", PROBE_AR, clusters, Tp, t0, 1e3 * t0 / Tp, st);
-#define VF(abl, what) { const float t = run_fwd<abl>(a); printf("  %-60s: %.3f ms = %.1f us per step\n", what, t, 1e3 * t / Tp); }
-        VF(64, "payload at device scope (what any other placement takes)");
-        VF(128, "members (not clusters) share an XCD");
-        VF(128 + 8, "... no saves");
-        VF(8, "no saves");
-        VF(4, "no weight loads");
-        VF(2, "partners' tiles not loaded (constants staged)");
-        VF(1, "no flag waits");
-        VF(8 + 4, "no saves, no weight loads");
-        VF(8 + 4 + 2, "... and no tile loads");
-        VF(8 + 4 + 2 + 1, "... and no flag waits");
-        VF(8 + 4 + 2 + 1 + 16, "... and no h stores (K loops, LDS traffic, barriers, cell)");
-        VF(0, "shipped again");
     }
 #endif
     if (which & 2) {
@@ -111,22 +99,9 @@ int main(int argc, char** argv) {
         unsigned short* dg16; float* dbp; hipMalloc(&dg16, 2 * TN * QG * 2); hipMalloc(&dbp, (size_t)2 * clusters * QG * 4);
         b.dg16_0 = dg16; b.dg16_1 = dg16 + TN * QG; b.dbp = dbp; b.dg1_f32 = 0;
         b.flags = flags; b.status = flags + fsn_lstm2_g16_status_word(clusters); b.spin_ticks = 1ull << 31; b.Tp = Tp; b.Nrows = N;
-        const float t0 = run_bwd<0>(b);
+        const float t0 = run_bwd(b);
         unsigned st = 0; hipMemcpy(&st, b.status, 4, hipMemcpyDeviceToHost);
         printf("arithmetic %d: lstm2_g16_bwd_kernel, %d clusters, %d steps: %.3f ms = %.1f us per step, status %u\n", PROBE_AR, clusters, Tp, t0, 1e3 * t0 / Tp, st);
-#define VB(abl, what) { const float t = run_bwd<abl>(b); printf("  %-60s: %.3f ms = %.1f us per step\n", what, t, 1e3 * t / Tp); }
-        VB(128, "members (not clusters) share an XCD");
-        VB(8, "no gate-gradient stores");
-        VB(2, "saved activations not loaded");
-        VB(4, "no weight loads");
-        VB(16, "no exchange stores");
-        VB(32, "exchanged operand not loaded");
-        VB(1, "no flag waits");
-        VB(8 + 2, "no saved loads, no gate-gradient stores");
-        VB(8 + 2 + 16 + 32, "... and no exchange traffic");
-        VB(8 + 2 + 16 + 32 + 4, "... and no weight loads");
-        VB(8 + 2 + 16 + 32 + 4 + 1, "... and no flag waits (K loops, LDS, barriers, cell derivative)");
-        VB(0, "shipped again");
     }
     return 0;
 }

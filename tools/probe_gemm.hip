@@ -1,4 +1,6 @@
-// Stand-alone timing probe for the fp32 MFMA GEMM family (not part of the library).
+// Stand-alone timing probe for the fp32 MFMA GEMM family (not part of the library): tile shapes and ring depths the template
+// offers, the shipped one first.  The runs without operand loads / without MFMAs are on record in profiles/r01_gemm_probe.md;
+// those variants are in git history before the commit that retired the kernel's experiment switch.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off tools/probe_gemm.hip -o gpurun_out/probe_gemm
 #include <cstdio>
 #include <cstdlib>

@@ -14,8 +14,8 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef ABL
-#define ABL 0  // probe-only ablations: 1 = no C store, 2 = A fragments loaded once per tile (no A traffic in the K loop)
+#ifndef PROBE_SKIP
+#define PROBE_SKIP 0  // probe-only ablations: 1 = no C store, 2 = A fragments loaded once per tile (no A traffic in the K loop)
 #endif
 constexpr int K = 384, N = 1536, KC = K / 32;  // 12 chunks of 32
 constexpr float SA = 64.f, SW = 256.f;          // power-of-two pre-scales keep the low halves out of fp16 subnormals
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void gemm_f16x3_kernel(const float* __restrict
         auto fetch_a = [&](int slot, int kc) {
 #pragma unroll
             for (int rt = 0; rt < RTW; ++rt) {
-                if (ABL == 2 && kc >= APF) continue;
+                if (PROBE_SKIP == 2 && kc >= APF) continue;
                 araw[slot][rt][0] = *reinterpret_cast<const f32x4*>(arow[rt] + kc * 32);
                 araw[slot][rt][1] = *reinterpret_cast<const f32x4*>(arow[rt] + kc * 32 + 4);
             }
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void gemm_f16x3_kernel(const float* __restrict
         for (int rt = 0; rt < RTW; ++rt)
 #pragma unroll
             for (int ct = 0; ct < CTW; ++ct)
-                if (rtile0 + rt < row_tiles && (ABL != 1 || acc[rt][ct][0] == 12345.678f)) {
+                if (rtile0 + rt < row_tiles && (PROBE_SKIP != 1 || acc[rt][ct][0] == 12345.678f)) {
                     const f32x4 a = acc[rt][ct];
                     *reinterpret_cast<f32x4*>(C + (((rtile0 + rt) * (N / 16) + ctile0 + ct) * 64 + lane) * 4) =
                         f32x4{a[0] * unscale, a[1] * unscale, a[2] * unscale, a[3] * unscale};

@@ -1,5 +1,8 @@
-// Timing probe for the split-precision recurrent kernel (not part of the library): where does a step go?
-//   hipcc -O3 --offload-arch=gfx950 -std=c++17 -DFSN_PROBE_ABLATE=k tools/probe_rec_f16x3.hip -o probe   (k = 0..3)
+// Timing probe for the split-precision recurrent kernel (not part of the library): the shipped kernel stand-alone at
+// config 2's shape.  Where a step goes - the runs without weight refills, LDS operand reads and cell math - is on record in
+// profiles/r01_gemm_probe.md; those variants are in git history before the commit that retired the kernel's
+// experiment switch.
+//   hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/probe_rec_f16x3.hip -o probe
 #include <cstdio>
 #include <cstdlib>
 #include "../fullsubnet_amd/csrc/lstm_f16x3_kernels.hip"
@@ -44,7 +47,6 @@ int main(int argc, char** argv) {
         float ms; hipEventElapsedTime(&ms, e0, e1); if (it > 0 && ms < best) best = ms;
     }
     const double flops = 3 * 2.0 * 255 * 64 * 384.0 * 1536 * Tp;
-    printf("rec f16x3 ablate=%d: %.3f ms  %.1f TFLOP/s of 16-bit MFMA (floor at 2088: %.3f ms)\n", FSN_PROBE_ABLATE, best,
-           flops / best / 1e9, flops / 2088e9);
+    printf("rec f16x3: %.3f ms  %.1f TFLOP/s of 16-bit MFMA (floor at 2088: %.3f ms)\n", best, flops / best / 1e9, flops / 2088e9);
     return 0;
 }

@@ -1,5 +1,8 @@
 // Timing probe for the fp32 weight-gradient product (gemm_tn_kernel, not part of the library): config 3's shape
-// C[1536][384] = sum over 395 264 rows of dgates^T h, 16 K splits of 192 x 192 tiles on 256 CUs.
+// C[1536][384] = sum over 395 264 rows of dgates^T h, 16 K splits of 192 x 192 tiles on 256 CUs.  The shipped tile and ring
+// depth beside the other tile / ring depth the template offers; the run without operand loads (the matrix stream alone) is
+// on record in profiles/r04_tn_probe.txt, and that variant is in git history before the commit that retired the kernel's
+// experiment switch.
 #include <cstdio>
 #include <cstdlib>
 #include "../fullsubnet_amd/csrc/lstm_train_kernels.hip"
@@ -34,10 +37,8 @@ int main() {
     const double flops = 2.0 * M * Nc * (double)K;
     auto rep = [&](const char* what, float ms) { printf("  %-58s: %.3f ms = %.1f TFLOP/s (%.3f of 157.3)\n", what, ms, flops / ms * 1e-9, flops / ms * 1e-9 / 157.3); };
     rep("gemm_tn_kernel: 192 x 192 tiles (6 x 6 per wave), ring depth 2", run(gemm_tn_kernel<6, 6, 2, 2, FSN_ARITH_F32, 2>, A, B, part, asum, M, Nc, K, 8, 2, 16));
-    rep("  operands not loaded (matrix stream + structure alone)", run(gemm_tn_kernel<6, 6, 2, 2, FSN_ARITH_F32, 2, 1>, A, B, part, asum, M, Nc, K, 8, 2, 16));
     rep("  ring depth 1", run(gemm_tn_kernel<6, 6, 2, 2, FSN_ARITH_F32, 1>, A, B, part, asum, M, Nc, K, 8, 2, 16));
     rep("256 x 128 tiles (8 x 4 per wave), 18 tiles x 14 splits", run(gemm_tn_kernel<8, 4, 2, 2, FSN_ARITH_F32, 2>, A, B, part, asum, M, Nc, K, 6, 3, 14));
-    rep("  operands not loaded", run(gemm_tn_kernel<8, 4, 2, 2, FSN_ARITH_F32, 2, 1>, A, B, part, asum, M, Nc, K, 6, 3, 14));
     rep("shipped again", run(gemm_tn_kernel<6, 6, 2, 2, FSN_ARITH_F32, 2>, A, B, part, asum, M, Nc, K, 8, 2, 16));
     return 0;
 }
