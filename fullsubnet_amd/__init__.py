@@ -11,6 +11,7 @@ from .graphs import GraphedCall  # noqa: F401
 from .inferencer import Inferencer  # noqa: F401
 from .model import Model  # noqa: F401
 from .optim import ClipAdam  # noqa: F401
+from .stream_pool import SessionBook, StreamPool  # noqa: F401
 from .streaming import StreamingEnhancer  # noqa: F401
 
 __version__ = "0.1.0"

@@ -98,23 +98,6 @@ __global__ __launch_bounds__(64 * kBinsumTG) void binsum_kernel(const float* __r
     }
 }
 
-// reflect(j) of F.pad(mode="reflect") for j in [-N, F+N)
-__device__ __forceinline__ int reflect_idx(int j, int F) {
-    j = j < 0 ? -j : j;
-    return j >= F ? 2 * (F - 1) - j : j;
-}
-
-__device__ __forceinline__ double block_sum(double v, double* scratch) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0) scratch[wave] = v;
-    __syncthreads();
-    double tot = 0.0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += scratch[w];
-    return tot;
-}
-
 // offline_laplace_norm (base_model.py:204-218): one mean per utterance, eps 1e-5.
 //   which == 0: den_fb[b] = mean_{f,t}(mag) + 1e-5                        (fullsubnet/model.py:92)
 //   which == 1: den_sb[b] = mean over the concatenated [F, 2nb+2, Tp] sub-band tensor + 1e-5
@@ -134,7 +117,7 @@ __global__ __launch_bounds__(256) void offline_den_kernel(const double* __restri
     double acc = 0.0;
     if (which == 0) {
         for (int f = threadIdx.x; f < F; f += blockDim.x) acc += binsum[(long)b * FP + f];
-        const double tot = block_sum(acc, scratch);
+        const double tot = fsn_block_sum(acc, scratch);
         if (threadIdx.x == 0) den_fb[b] = (float)(tot / ((double)F * Tpb)) + 1e-5f;
     } else {
         for (int f = threadIdx.x; f < F; f += blockDim.x) {
@@ -152,7 +135,7 @@ __global__ __launch_bounds__(256) void offline_den_kernel(const double* __restri
             const f32x4 v = p[i];
             acc += ((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3]);
         }
-        const double tot = block_sum(acc, scratch);
+        const double tot = fsn_block_sum(acc, scratch);
         if (threadIdx.x == 0) den_sb[b] = (float)(tot / ((double)F * (2 * nb + 2) * Tpb)) + 1e-5f;
     }
 }
@@ -169,9 +152,9 @@ __global__ __launch_bounds__(256) void cumulative_den_fb_kernel(const float* __r
     for (int t = 0; t < Tp; ++t) {
         double acc = 0.0;
         for (int f = threadIdx.x; f < F; f += blockDim.x) acc += (double)mag[((long)b * Tp + t) * FP + f];
-        run += block_sum(acc, scratch);
+        run += fsn_block_sum(acc, scratch);
         if (threadIdx.x == 0)
-            den[(long)b * Tp + t] = (float)(run / ((double)F * (t0 + t + 1))) + 1.1920928955078125e-07f;
+            den[(long)b * Tp + t] = (float)(run / ((double)F * (t0 + t + 1))) + kFsnEpsilon;
     }
     if (carry && threadIdx.x == 0) carry[b] = run;
 }
@@ -192,9 +175,9 @@ __global__ __launch_bounds__(256) void cumulative_den_sb_kernel(const float* __r
     for (int t = 0; t < Tp; ++t) {
         const float* row = mag + ((long)b * Tp + t) * FP;
         double acc = (double)fb_out[((long)b * Tp + t) * FP + f];
-        for (int k = -nb; k <= nb; ++k) acc += (double)row[reflect_idx(f + k, F)];
+        for (int k = -nb; k <= nb; ++k) acc += (double)row[fsn_reflect_idx(f + k, F)];
         run += acc;
-        den[(long)t * Npad + n] = (float)(run / ((double)(2 * nb + 2) * (t0 + t + 1))) + 1.1920928955078125e-07f;
+        den[(long)t * Npad + n] = (float)(run / ((double)(2 * nb + 2) * (t0 + t + 1))) + kFsnEpsilon;
     }
     if (carry) carry[n] = run;
 }

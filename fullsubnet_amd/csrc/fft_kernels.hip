@@ -357,7 +357,241 @@ __global__ __launch_bounds__(256) void ola_kernel(const float* __restrict__ wfra
     y[gid] = out;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Streaming pool (fsn_stream_pool_analysis / _synthesis): the same transforms one FRAME at a time for a list of
+// sessions, with the carried samples in the sessions' slot records (FsnPoolLayout).  The two frames a wave packs into one
+// complex FFT are two sessions' frames.  A row whose slot id is outside the pool transforms zeros and writes no state.
+// ---------------------------------------------------------------------------------------------
+// Analysis: frame = in_tail[slot] ++ hops[i], window, 512-point real FFT -> ring_re / ring_im[slot][frame_no % R][FP]
+// (columns F.. zero) and mag [n][F]; then in_tail[slot] = hops[i].  A lane reads and writes the same in_tail elements, in
+// that order.  Frame 0 of a session (frame_no[i] == 0) takes the reflected samples y[256..1] as its left half: prime[i]
+// holds y[1..256] and is read backwards.  prime == NULL is the caller's promise that no listed session is at frame 0
+// (fsn_hip.h): a frame 0 then takes in_tail like any other frame - zeros on a fresh slot, not the reflection.
+__global__ __launch_bounds__(256) void pool_analysis_kernel(char* __restrict__ state, FsnPoolLayout L, int capacity,
+                                                            const int* __restrict__ slots, int n,
+                                                            const float* __restrict__ hops, const float* __restrict__ prime,
+                                                            const int* __restrict__ frame_no,
+                                                            const float* __restrict__ window, float* __restrict__ mag) {
+    __shared__ double lds[kWavesPerBlock][2][kLdsPoints];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int iA = 2 * (blockIdx.x * kWavesPerBlock + wave), iB = iA + 1;
+    char* recA = fsn_pool_record(state, L, capacity, slots, n, iA);
+    char* recB = fsn_pool_record(state, L, capacity, slots, n, iB);
+    const int tA = recA ? frame_no[iA] : 0, tB = recB ? frame_no[iB] : 0;
+    if (tA < 0) recA = nullptr;  // no such frame: skipped like a bad slot id
+    if (tB < 0) recB = nullptr;
+    double* sre = lds[wave][0];
+    double* sim = lds[wave][1];
+
+    cd v[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int nn = lane + 64 * r;
+        const float w = window[nn];
+        float x[2] = {0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            char* rec = q ? recB : recA;
+            const int i = q ? iB : iA, t = q ? tB : tA;
+            if (!rec) continue;
+            float* tail = reinterpret_cast<float*>(rec + L.in_tail);
+            float xs;
+            if (r < 4) {
+                xs = (t == 0 && prime) ? prime[(long)i * 256 + 255 - nn] : tail[nn];  // y[256 - nn]
+            } else {
+                xs = hops[(long)i * 256 + nn - 256];
+                tail[nn - 256] = xs;  // this lane read tail[nn - 256] four iterations ago
+            }
+            x[q] = xs * w;
+        }
+        v[r] = cd{(double)x[0], (double)x[1]};
+    }
+    pass8<false, 1>(v, sre, sim, lane);
+    wave_lds_sync();
+    load8(v, sre, sim, lane);
+    wave_lds_sync();
+    pass8<false, 8>(v, sre, sim, lane);
+    wave_lds_sync();
+    load8(v, sre, sim, lane);
+    wave_lds_sync();
+    pass8<false, 64>(v, sre, sim, lane);
+    wave_lds_sync();
+
+    const int F = L.F, FP = L.FP;
+#pragma unroll
+    for (int m = 0; m < 5; ++m) {
+        const int k = lane + 64 * m;
+        if (k >= FP) break;
+        float ar = 0.f, ai = 0.f, br = 0.f, bi = 0.f;
+        if (k < F) {  // the split of stft_kernel
+            const int kn = (512 - k) & 511;
+            const double zr = sre[lpad(k)], zi = sim[lpad(k)], wr = sre[lpad(kn)], wi = sim[lpad(kn)];
+            ar = (float)(0.5 * (zr + wr));
+            ai = (float)(0.5 * (zi - wi));
+            br = (float)(0.5 * (zi + wi));
+            bi = (float)(-0.5 * (zr - wr));
+        }
+        if (recA) {
+            const long o = (long)(tA % L.R) * FP + k;
+            reinterpret_cast<float*>(recA + L.ring_re)[o] = ar;
+            reinterpret_cast<float*>(recA + L.ring_im)[o] = ai;
+        }
+        if (recB) {
+            const long o = (long)(tB % L.R) * FP + k;
+            reinterpret_cast<float*>(recB + L.ring_re)[o] = br;
+            reinterpret_cast<float*>(recB + L.ring_im)[o] = bi;
+        }
+        if (k < F) {
+            if (iA < n) mag[(long)iA * F + k] = recA ? (float)sqrt((double)ar * ar + (double)ai * ai) : 0.f;
+            if (iB < n) mag[(long)iB * F + k] = recB ? (float)sqrt((double)br * br + (double)bi * bi) : 0.f;
+        }
+    }
+}
+
+// Synthesis, part 1: mask_irfft_kernel on column j of row i = output frame m = first_frame[i] + j of slots[i], its spectrum
+// taken from the slot's ring and its mask from crm [n][2][F][k]: wframes [n][k][512].  Columns with m < 0 (model steps of
+// the first look_ahead frames, which belong to no output frame) and skipped rows are written as zeros.
+__global__ __launch_bounds__(256) void pool_mask_irfft_kernel(char* __restrict__ state, FsnPoolLayout L, int capacity,
+                                                              const int* __restrict__ slots, int n,
+                                                              const float* __restrict__ crm, int k,
+                                                              const int* __restrict__ first_frame,
+                                                              const float* __restrict__ window,
+                                                              float* __restrict__ wframes) {
+    __shared__ double lds[kWavesPerBlock][2][kLdsPoints];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long qA = 2 * ((long)blockIdx.x * kWavesPerBlock + wave);
+    const long total = (long)n * k;
+    const int F = L.F, FP = L.FP;
+    double* sre = lds[wave][0];
+    double* sim = lds[wave][1];
+    const float* ring_re[2] = {nullptr, nullptr};
+    const float* ring_im[2] = {nullptr, nullptr};
+    const float* mask[2] = {nullptr, nullptr};
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const long qq = qA + q;
+        if (qq >= total) continue;
+        const int i = (int)(qq / k), j = (int)(qq % k);
+        char* rec = fsn_pool_record(state, L, capacity, slots, n, i);
+        const int m = rec ? first_frame[i] + j : -1;
+        if (m < 0) continue;
+        ring_re[q] = reinterpret_cast<const float*>(rec + L.ring_re) + (long)(m % L.R) * FP;
+        ring_im[q] = reinterpret_cast<const float*>(rec + L.ring_im) + (long)(m % L.R) * FP;
+        mask[q] = crm + (long)i * 2 * F * k + j;
+    }
+#pragma unroll
+    for (int m = 0; m < 5; ++m) {
+        const int kk = lane + 64 * m;
+        if (kk > 256) break;
+        float s[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            if (!ring_re[q]) continue;
+            const float xr = ring_re[q][kk], xi = ring_im[q][kk];
+            const float mr = decompress1(mask[q][(long)kk * k]), mi = decompress1(mask[q][(long)(F + kk) * k]);
+            s[q][0] = mr * xr - mi * xi;
+            s[q][1] = mi * xr + mr * xi;
+        }
+        if (kk == 0 || kk == 256) {  // C2R ignores the imaginary part of DC / Nyquist
+            s[0][1] = 0.f;
+            s[1][1] = 0.f;
+        }
+        const double ar = s[0][0], ai = s[0][1], br = s[1][0], bi = s[1][1];
+        sre[lpad(kk)] = ar - bi;
+        sim[lpad(kk)] = ai + br;
+        if (kk > 0 && kk < 256) {
+            sre[lpad(512 - kk)] = ar + bi;
+            sim[lpad(512 - kk)] = br - ai;
+        }
+    }
+    wave_lds_sync();
+    cd v[8];
+    load8(v, sre, sim, lane);
+    wave_lds_sync();
+    pass8<true, 1>(v, sre, sim, lane);
+    wave_lds_sync();
+    load8(v, sre, sim, lane);
+    wave_lds_sync();
+    pass8<true, 8>(v, sre, sim, lane);
+    wave_lds_sync();
+    load8(v, sre, sim, lane);
+    wave_lds_sync();
+    pass8<true, 64>(v, sre, sim, lane);
+    wave_lds_sync();
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int nn = lane + 64 * r;
+        const float w = window[nn];
+        const float fa = (float)(sre[lpad(nn)] * (1.0 / 512.0));
+        const float fb = (float)(sim[lpad(nn)] * (1.0 / 512.0));
+        if (qA < total) wframes[qA * 512 + nn] = ring_re[0] ? fa * w : 0.f;
+        if (qA + 1 < total) wframes[(qA + 1) * 512 + nn] = ring_re[1] ? fb * w : 0.f;
+    }
+}
+
+// Synthesis, part 2: ola_kernel one hop at a time.  Thread (i, s) walks row i's columns: output frame m >= 1 emits
+// out[i][256 j + s] = (partner + wframe_m[s]) / (w[s + 256]^2 + w[s]^2), partner = second half of frame m - 1 (ola_tail[slot]
+// for the first column); frame 0 emits nothing (its first half is the trimmed centre pad).  Then ola_tail[slot] = second half
+// of the last frame.  tail_samples[i] >= 0: the session ends with this frame - the first tail_samples samples of that second
+// half, divided by the one-frame envelope, go to column k.  Everything else of out [n][(k + 1) 256] is written as zeros.
+__global__ __launch_bounds__(256) void pool_ola_kernel(char* __restrict__ state, FsnPoolLayout L, int capacity,
+                                                       const int* __restrict__ slots, int n, int k,
+                                                       const int* __restrict__ first_frame,
+                                                       const int* __restrict__ tail_samples,
+                                                       const float* __restrict__ window,
+                                                       const float* __restrict__ wframes, float* __restrict__ out) {
+    const int i = blockIdx.x, s = threadIdx.x;
+    char* rec = fsn_pool_record(state, L, capacity, slots, n, i);
+    float* o = out + (long)i * (k + 1) * 256;
+    if (!rec) {
+        for (int j = 0; j <= k; ++j) o[j * 256 + s] = 0.f;
+        return;
+    }
+    float* tail = reinterpret_cast<float*>(rec + L.ola_tail);
+    const float w_lo = window[s + 256], w_hi = window[s];
+    float env = w_lo * w_lo;
+    env = env + w_hi * w_hi;
+    float prev = tail[s];
+    const int m0 = first_frame[i];
+    for (int j = 0; j < k; ++j) {
+        const int m = m0 + j;
+        float y = 0.f;
+        if (m >= 0) {
+            const float* wf = wframes + ((long)i * k + j) * 512;
+            if (m >= 1) {
+                const float acc = prev + wf[s];
+                y = acc / env;
+            }
+            prev = wf[s + 256];
+        }
+        o[j * 256 + s] = y;
+    }
+    tail[s] = prev;
+    const int rem = tail_samples[i];
+    o[k * 256 + s] = s < rem ? prev / (w_lo * w_lo) : 0.f;
+}
+
 }  // namespace
+
+int fsn_launch_pool_analysis(void* state, const FsnPoolLayout& L, int capacity, const int* slots, int n, const float* hops,
+                             const float* prime, const int* frame_no, const float* window, float* mag, hipStream_t s) {
+    const int pairs = (n + 1) / 2;
+    hipLaunchKernelGGL(pool_analysis_kernel, dim3((pairs + kWavesPerBlock - 1) / kWavesPerBlock), dim3(256), 0, s,
+                       static_cast<char*>(state), L, capacity, slots, n, hops, prime, frame_no, window, mag);
+    return fsn_check_launch("pool_analysis_kernel");
+}
+
+int fsn_launch_pool_synthesis(void* state, const FsnPoolLayout& L, int capacity, const int* slots, int n, const float* crm,
+                              int k, const int* first_frame, const int* tail_samples, const float* window, float* wframes,
+                              float* out, hipStream_t s) {
+    const long pairs = ((long)n * k + 1) / 2;
+    hipLaunchKernelGGL(pool_mask_irfft_kernel, dim3((unsigned)((pairs + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(256), 0,
+                       s, static_cast<char*>(state), L, capacity, slots, n, crm, k, first_frame, window, wframes);
+    FSN_TRY_LAUNCH("pool_mask_irfft_kernel");
+    hipLaunchKernelGGL(pool_ola_kernel, dim3(n), dim3(256), 0, s, static_cast<char*>(state), L, capacity, slots, n, k,
+                       first_frame, tail_samples, window, wframes, out);
+    return fsn_check_launch("pool_ola_kernel");
+}
 
 int fsn_launch_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag, int T,
                     int Tp, int F, int FP, bool frame_major, hipStream_t s, const int* lengths) {

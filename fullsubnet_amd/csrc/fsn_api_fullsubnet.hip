@@ -1110,8 +1110,203 @@ extern "C" int fsn_fullsubnet_stream_step(const fsn_fullsubnet_cfg* cfg, const v
     return FSN_OK;
 }
 
+// ---- streaming pool: the same step over a subset of the slots of a pool --------------------------------------------
+// State: one record per slot (FsnPoolLayout, fsn_common.h).  A step gathers the listed slots' (h, c) rows into compact
+// tiles in the workspace, runs the sequence of fsn_fullsubnet_stream_step on them with per-slot norm carries and step
+// counts, and scatters the rows back (stream_pool_kernels.hip).
+static FsnPoolLayout pool_layout(const fsn_fullsubnet_cfg* cfg) {
+    return fsn_pool_layout(cfg->num_freqs, cfg->fb_hidden, cfg->sb_hidden, cfg->look_ahead);
+}
+static int check_pool(const fsn_fullsubnet_cfg* cfg, int capacity) {
+    FSN_TRY(check_stream(cfg, 1, 1));
+    FSN_REQUIRE(capacity >= 1 && capacity <= 4096, "streaming pool: capacity %d out of range [1, 4096]", capacity);
+    return FSN_OK;
+}
+static int check_pool_call(const fsn_fullsubnet_cfg* cfg, const void* state, size_t state_bytes, int capacity,
+                           const int* slots, int n) {
+    FSN_TRY(check_pool(cfg, capacity));
+    FSN_REQUIRE(state && slots, "NULL pointer argument");
+    FSN_REQUIRE(n >= 1 && n <= capacity, "streaming pool: %d slots listed, need 1 .. capacity = %d", n, capacity);
+    if (state_bytes < (size_t)capacity * pool_layout(cfg).slot_bytes) {
+        fsn_set_error("streaming pool: state buffer too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    return FSN_OK;
+}
+struct PoolTilesWs {
+    float *fb[4], *sb[4];  // h0, h1, c0, c1
+};
+static PoolTilesWs pool_tiles_carve(Carver& cv, const fsn_fullsubnet_cfg* cfg, int n) {
+    PoolTilesWs t;
+    const size_t nfb = (size_t)fsn_round_up(n, 16) * cfg->fb_hidden;
+    const size_t nsb = (size_t)fsn_round_up(n * cfg->num_freqs, 16) * cfg->sb_hidden;
+    for (int a = 0; a < 4; ++a) t.fb[a] = cv.take<float>(nfb);
+    for (int a = 0; a < 4; ++a) t.sb[a] = cv.take<float>(nsb);
+    return t;
+}
+
+extern "C" size_t fsn_fullsubnet_stream_pool_state_bytes(const fsn_fullsubnet_cfg* cfg, int capacity) {
+    if (check_pool(cfg, capacity) != FSN_OK) return 0;
+    return (size_t)capacity * pool_layout(cfg).slot_bytes;
+}
+extern "C" size_t fsn_fullsubnet_stream_pool_workspace_bytes(const fsn_fullsubnet_cfg* cfg, int n, int k) {
+    if (check_stream(cfg, n, k) != FSN_OK) return 0;
+    Carver cv(nullptr);
+    stream_ws_carve(cv, cfg, n, k);
+    pool_tiles_carve(cv, cfg, n);
+    return fsn_round_up_sz(cv.off, 256);
+}
+
+extern "C" int fsn_fullsubnet_stream_pool_reset(const fsn_fullsubnet_cfg* cfg, void* state, size_t state_bytes,
+                                                int capacity, const int* slots, int n, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_pool_call(cfg, state, state_bytes, capacity, slots, n));
+    return fsn_launch_pool_reset(state, pool_layout(cfg), capacity, slots, n, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fsn_fullsubnet_stream_pool_step(const fsn_fullsubnet_cfg* cfg, const void* packed, void* state,
+                                               size_t state_bytes, int capacity, const int* slots, int n, const float* mag,
+                                               int k, float* crm_out, void* workspace, size_t workspace_bytes,
+                                               void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_pool_call(cfg, state, state_bytes, capacity, slots, n));
+    FSN_TRY(check_stream(cfg, n, k));
+    FSN_REQUIRE(packed && mag && crm_out && workspace, "NULL pointer argument");
+    if (workspace_bytes < fsn_fullsubnet_stream_pool_workspace_bytes(cfg, n, k)) {
+        fsn_set_error("streaming pool: workspace buffer too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Packed p = packed_layout(cfg);
+    const FsnPoolLayout L = pool_layout(cfg);
+    const float* pk = static_cast<const float*>(packed);
+    const int F = cfg->num_freqs, FP = fsn_fpad(F), Hf = cfg->fb_hidden, Hs = cfg->sb_hidden, nb = cfg->sb_num_neighbors;
+    const int Npad_fb = fsn_round_up(n, 16), N = n * F, Npad = fsn_round_up(N, 16);
+    Carver cw(workspace);
+    const StreamWs w = stream_ws_carve(cw, cfg, n, k);
+    const PoolTilesWs t = pool_tiles_carve(cw, cfg, n);
+    // [n, 1, F, k] -> frame-major [n][k][FP]
+    FSN_TRY(fsn_launch_transpose(mag, w.magT, n, FP, k, k, (long)F * k, FP, (long)k * FP, F, k, s));
+    FSN_TRY(fsn_launch_pool_gather(state, L, capacity, slots, n, 0, t.fb[0], t.fb[1], t.fb[2], t.fb[3], Npad_fb, s));
+    FSN_TRY(fsn_launch_pool_gather(state, L, capacity, slots, n, 1, t.sb[0], t.sb[1], t.sb[2], t.sb[3], Npad, s));
+    FSN_TRY(fsn_launch_pool_den_fb(w.magT, w.den_fb, state, L, capacity, slots, n, k, s));
+    FsnGemmA a{};
+    FsnGemmC c{};
+    a.kind = 1;
+    a.p0 = w.magT;
+    a.den = w.den_fb;
+    a.den_mode = 1;
+    a.B = n;
+    a.Tp = k;
+    a.F = F;
+    a.FP = FP;
+    a.Npad = Npad_fb;
+    c.kind = 0;
+    c.p0 = w.gx_fb;
+    c.bias = pk + p.fb_b0;
+    const int fb_rt = k * Npad_fb / 16;
+    FSN_TRY(fsn_launch_gemm(a, pk + p.fb_wih0, c, fb_rt, 4 * Hf / 16, FP / 16, s));
+    FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_fb, Npad_fb / 16, 0, pk + p.fb_whh0, pk + p.fb_wih1, pk + p.fb_b1_frag,
+                                       pk + p.fb_whh1, w.hseq_fb0, w.hseq_fb1, Npad_fb, 0, t.fb[2], t.fb[3], k,
+                                       Npad_fb / 16, Hf, s, t.fb[0], t.fb[1]));
+    a = FsnGemmA{};
+    c = FsnGemmC{};
+    a.kind = 0;
+    a.p0 = w.hseq_fb1;
+    a.ld = Hf;
+    c.kind = 1;
+    c.p0 = w.fb_out;
+    c.bias = pk + p.fb_fcb;
+    c.B = n;
+    c.Tp = k;
+    c.F = F;
+    c.FP = FP;
+    c.Npad = Npad_fb;
+    FSN_TRY(fsn_launch_gemm(a, pk + p.fb_fc, c, fb_rt, FP / 16, Hf / 16, s));
+    FSN_TRY(fsn_launch_pool_den_sb(w.magT, w.fb_out, w.den_sb, state, L, capacity, slots, n, k, nb, Npad, s));
+    a = FsnGemmA{};
+    c = FsnGemmC{};
+    a.kind = 2;
+    a.p0 = w.magT;
+    a.p1 = w.fb_out;
+    a.den = w.den_sb;
+    a.den_mode = 1;
+    a.den_stride = Npad;
+    a.B = n;
+    a.Tp = k;
+    a.F = F;
+    a.FP = FP;
+    a.Npad = Npad;
+    a.n_offset = 0;
+    a.N = N;
+    a.nb = nb;
+    c.kind = 0;
+    c.p0 = w.gx_sb;
+    c.bias = pk + p.sb_b0;
+    const int sb_rt = (int)((long)k * Npad / 16);
+    FSN_TRY(fsn_launch_gemm(a, pk + p.sb_wih0, c, sb_rt, 4 * Hs / 16, p.sb_kin_pad / 16, s));
+    FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_sb, Npad / 16, 0, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_b1_frag,
+                                       pk + p.sb_whh1, w.hseq_sb0, w.hseq_sb1, Npad, 0, t.sb[2], t.sb[3], k, Npad / 16, Hs,
+                                       s, t.sb[0], t.sb[1]));
+    a = FsnGemmA{};
+    c = FsnGemmC{};
+    a.kind = 0;
+    a.p0 = w.hseq_sb1;
+    a.ld = Hs;
+    c.kind = 2;
+    c.p0 = w.crm_r;
+    c.p1 = w.crm_i;
+    c.bias = pk + p.sb_fcb;
+    c.T = k;
+    c.F = F;
+    c.FP = FP;
+    c.Npad = Npad;
+    c.N = N;
+    c.la = 0;  // every model step is handed back, as in fsn_fullsubnet_stream_step
+    FSN_TRY(fsn_launch_gemm(a, pk + p.sb_fc, c, sb_rt, 1, Hs / 16, s));
+    FSN_TRY(fsn_launch_transpose(w.crm_r, crm_out, n, k, F, FP, (long)k * FP, k, 2L * F * k, k, F, s));
+    FSN_TRY(fsn_launch_transpose(w.crm_i, crm_out + (size_t)F * k, n, k, F, FP, (long)k * FP, k, 2L * F * k, k, F, s));
+    FSN_TRY(fsn_launch_pool_scatter(state, L, capacity, slots, n, 0, t.fb[0], t.fb[1], t.fb[2], t.fb[3], Npad_fb, k, s));
+    // last: it advances the listed slots' step counts
+    return fsn_launch_pool_scatter(state, L, capacity, slots, n, 1, t.sb[0], t.sb[1], t.sb[2], t.sb[3], Npad, k, s);
+}
+
 // ---- STFT / iSTFT boundary -------------------------------------------------------------------
 static bool fast_fft(int n_fft, int hop) { return n_fft == 512 && hop == 256; }
+
+// Streaming pool, frame analysis / synthesis for a list of sessions (fft_kernels.hip): 512 / 256 only, like fsn_enhance
+static int check_pool_fft(const fsn_fullsubnet_cfg* cfg, int n_fft, int hop) {
+    FSN_REQUIRE(fast_fft(n_fft, hop), "streaming pool: only n_fft = 512, hop = 256 is built (got %d/%d)", n_fft, hop);
+    FSN_REQUIRE(cfg->num_freqs == n_fft / 2 + 1, "num_freqs %d != n_fft/2+1", cfg->num_freqs);
+    return FSN_OK;
+}
+extern "C" int fsn_stream_pool_analysis(const fsn_fullsubnet_cfg* cfg, void* state, size_t state_bytes, int capacity,
+                                        const int* slots, int n, const float* hops, const float* prime,
+                                        const int* frame_no, int n_fft, int hop, const float* window, float* mag,
+                                        void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_pool_call(cfg, state, state_bytes, capacity, slots, n));
+    FSN_TRY(check_pool_fft(cfg, n_fft, hop));
+    FSN_REQUIRE(hops && frame_no && window && mag, "NULL pointer argument");
+    return fsn_launch_pool_analysis(state, pool_layout(cfg), capacity, slots, n, hops, prime, frame_no, window, mag,
+                                    static_cast<hipStream_t>(stream));
+}
+extern "C" int fsn_stream_pool_synthesis(const fsn_fullsubnet_cfg* cfg, void* state, size_t state_bytes, int capacity,
+                                         const int* slots, int n, const float* crm, int k, const int* first_frame,
+                                         const int* tail_samples, int n_fft, int hop, const float* window, float* out,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_pool_call(cfg, state, state_bytes, capacity, slots, n));
+    FSN_TRY(check_pool_fft(cfg, n_fft, hop));
+    FSN_REQUIRE(crm && first_frame && tail_samples && window && out && workspace, "NULL pointer argument");
+    FSN_REQUIRE(k >= 1 && k <= 4096, "streaming pool: frames %d out of range", k);
+    if (workspace_bytes < (size_t)n * k * n_fft * sizeof(float)) {
+        fsn_set_error("streaming pool: synthesis workspace too small (n k n_fft floats)");
+        return FSN_ERR_WORKSPACE;
+    }
+    return fsn_launch_pool_synthesis(state, pool_layout(cfg), capacity, slots, n, crm, k, first_frame, tail_samples, window,
+                                     static_cast<float*>(workspace), out, static_cast<hipStream_t>(stream));
+}
 
 // fsn_enhance's fused path is built for the FullSubNet recipe's transform only
 static int check_fft(int n_fft, int hop, int win_length) {

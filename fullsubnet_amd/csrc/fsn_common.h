@@ -250,6 +250,92 @@ int fsn_launch_mask_irfft(const float* re, const float* im, const float* crm_r, 
 int fsn_launch_ola(const float* wframes, const float* window, int B, int T, int length, float* y,
                    hipStream_t s, const int* lengths = nullptr);
 
+// ---- streaming pool (fsn_fullsubnet_stream_pool_*) --------------------------------------------------------------------
+// The pool's state blob is `capacity` records of slot_bytes each, one per slot; all zeros is a fresh slot.  Byte offsets
+// into a record (every array 256-byte aligned, slot_bytes a multiple of 256):
+//   fb[a] / sb[a]   a = h0, h1, c0, c1 of the full-band model [Hf] / of the sub-band model [F][Hs]
+//   fb_sum, sb_sum  running fp64 sums of the two cumulative norms (1 and F doubles)
+//   steps           model steps this slot has taken (int; read and advanced on the device)
+//   in_tail         the last 256 input samples (left half of the next analysis frame)
+//   ola_tail        second half of the last synthesised frame (overlap-add partner of the next one)
+//   ring_re/_im     spectra of the last R = look_ahead + 1 analysed frames, [R][FP], frame t at t % R
+struct FsnPoolLayout {
+    size_t fb[4], sb[4], fb_sum, sb_sum, steps, in_tail, ola_tail, ring_re, ring_im, slot_bytes;
+    int F, FP, Hf, Hs, R;
+};
+static inline FsnPoolLayout fsn_pool_layout(int F, int Hf, int Hs, int look_ahead) {
+    FsnPoolLayout L;
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        const size_t r = o;
+        o = fsn_round_up_sz(o + bytes, 256);
+        return r;
+    };
+    L.F = F;
+    L.FP = fsn_fpad(F);
+    L.Hf = Hf;
+    L.Hs = Hs;
+    L.R = look_ahead + 1;
+    for (int a = 0; a < 4; ++a) L.fb[a] = take((size_t)Hf * sizeof(float));
+    for (int a = 0; a < 4; ++a) L.sb[a] = take((size_t)F * Hs * sizeof(float));
+    L.fb_sum = take(sizeof(double));
+    L.sb_sum = take((size_t)F * sizeof(double));
+    L.steps = take(sizeof(int));
+    L.in_tail = take(256 * sizeof(float));
+    L.ola_tail = take(256 * sizeof(float));
+    L.ring_re = take((size_t)L.R * L.FP * sizeof(float));
+    L.ring_im = take((size_t)L.R * L.FP * sizeof(float));
+    L.slot_bytes = o;
+    return L;
+}
+// the record of slots[i], or NULL for i >= n or an id outside the pool (such a row is skipped by every pool kernel)
+__device__ __forceinline__ char* fsn_pool_record(char* state, const FsnPoolLayout& L, int capacity, const int* slots, int n,
+                                                 int i) {
+    if (i >= n) return nullptr;
+    const int slot = slots[i];
+    return (slot >= 0 && slot < capacity) ? state + (size_t)slot * L.slot_bytes : nullptr;
+}
+
+// Shared by the cumulative-norm kernels of elementwise_kernels.hip and their per-slot forms in stream_pool_kernels.hip
+// (the pool's bit-identity to the lockstep entry rests on both using exactly this arithmetic).
+constexpr float kFsnEpsilon = 1.1920928955078125e-07f;  // audio_zen/constant.py:9
+// reflect(j) of F.pad(mode="reflect") for j in [-N, F+N)
+__device__ __forceinline__ int fsn_reflect_idx(int j, int F) {
+    j = j < 0 ? -j : j;
+    return j >= F ? 2 * (F - 1) - j : j;
+}
+// sum of v over the workgroup (whole waves, at most 16), every thread gets it; fixed order
+__device__ __forceinline__ double fsn_block_sum(double v, double* scratch) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __syncthreads();
+    if (lane == 0) scratch[wave] = v;
+    __syncthreads();
+    double tot = 0.0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += scratch[w];
+    return tot;
+}
+
+// stream_pool_kernels.hip.  slots: device, n ids; a row whose id is outside [0, capacity) is skipped by every kernel.
+// which: 0 full-band model (Npad = round_up(n, 16) rows), 1 sub-band model (Npad = round_up(n F, 16) rows, row i F + f).
+int fsn_launch_pool_gather(void* state, const FsnPoolLayout& L, int capacity, const int* slots, int n, int which, float* h0,
+                           float* h1, float* c0, float* c1, int Npad, hipStream_t s);
+// which == 1 also advances the listed slots' step counts by k: it is the last launch of a step
+int fsn_launch_pool_scatter(void* state, const FsnPoolLayout& L, int capacity, const int* slots, int n, int which, float* h0,
+                            float* h1, float* c0, float* c1, int Npad, int k, hipStream_t s);
+// mag / fb_out [n][k][FP]; den [n][k] (full band) and [k][Npad] (sub band), as fsn_launch_cumulative_den_*
+int fsn_launch_pool_den_fb(const float* mag, float* den, void* state, const FsnPoolLayout& L, int capacity, const int* slots,
+                           int n, int k, hipStream_t s);
+int fsn_launch_pool_den_sb(const float* mag, const float* fb_out, float* den, void* state, const FsnPoolLayout& L,
+                           int capacity, const int* slots, int n, int k, int nb, int Npad, hipStream_t s);
+int fsn_launch_pool_reset(void* state, const FsnPoolLayout& L, int capacity, const int* slots, int n, hipStream_t s);
+// fft_kernels.hip: one analysis frame per listed slot / k synthesis frames per listed slot (see the kernels)
+int fsn_launch_pool_analysis(void* state, const FsnPoolLayout& L, int capacity, const int* slots, int n, const float* hops,
+                             const float* prime, const int* frame_no, const float* window, float* mag, hipStream_t s);
+int fsn_launch_pool_synthesis(void* state, const FsnPoolLayout& L, int capacity, const int* slots, int n, const float* crm,
+                              int k, const int* first_frame, const int* tail_samples, const float* window, float* wframes,
+                              float* out, hipStream_t s);
+
 // dft_kernels.hip (any even n_fft / any hop: direct fp64 DFT; reference layout [B][F][T] only)
 int fsn_launch_dft_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag, int T,
                         int N, int hop, hipStream_t s);

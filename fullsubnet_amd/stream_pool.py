@@ -1,0 +1,346 @@
+"""A pool of streaming sessions that open, advance and close on their own and share ONE model step per tick.
+
+``StreamingEnhancer`` runs a fixed batch in lockstep; a server that enhances calls has sessions that arrive and hang up
+at any time, whose hops are not phase-aligned and of which only some have a frame ready on a given 16 ms tick:
+
+    pool = StreamPool(model, capacity=64)      # fused FullSubNet config, norm_type == "cumulative_laplace_norm"
+    sid  = pool.open()                         # raises when the pool is full
+    pool.push(sid, chunk)                      # 1-D samples, any length >= 0, host or device
+    out  = pool.step()                         # {sid: samples}: ONE frame for every session that has one ready
+    out  = pool.drain()                        # step() until no session has a frame ready; samples concatenated per sid
+    tail = pool.close(sid)                     # last frame, look_ahead zero frames, OLA tail; the slot is free again
+
+Per session, the ``drain()`` outputs followed by ``close()`` equal ``model.enhance(utterance[None])[0]``, whatever the
+other sessions do.  A tick is three C calls on the list of ready slots - frame analysis (``fsn_stream_pool_analysis``), the
+model step (``fsn_fullsubnet_stream_pool_step``) and frame synthesis (``fsn_stream_pool_synthesis``) - around one
+``torch.stack`` of the new hops (two on a tick where a session starts: the samples its first frame reflects) and one small
+host-to-device copy of the slot list.  Everything a session carries (LSTM states, norm sums, its own step count, the last
+hop, the spectra waiting for their mask, the overlap-add half frame) lives in its slot of one device blob.
+
+``SessionBook`` is the host book-keeping (which frame is next, who is ready, model steps versus output frames, the
+look-ahead drop); it makes no device call, so it is tested without a GPU.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+
+N_FFT, HOP = 512, 256
+
+
+class _Session:
+    __slots__ = ("slot", "n_in", "t_next", "frames_out", "frames_out_at_close", "steps", "n_out", "closing")
+
+    def __init__(self, slot):
+        self.slot = slot
+        self.n_in = 0                  # samples received
+        self.t_next = 0                # next frame to analyse = model steps on real frames so far
+        self.frames_out = 0            # output frames synthesised (frame 0 counts: it emits no samples)
+        self.frames_out_at_close = 0   # ... of which by close()
+        self.steps = 0                 # model steps, the look-ahead zero frames at the end included
+        self.n_out = 0                 # samples emitted
+        self.closing = False
+
+
+class SessionBook:
+    """Host book-keeping of a pool of ``capacity`` slots; no device calls.
+
+    Frame t of a session covers samples [t hop - hop, t hop + hop) (torch.stft, center=True): frame 0 reflects sample
+    ``hop`` on its left, so it needs hop + 1 samples; frame t >= 1 is complete with (t + 1) hop samples.  A complete frame
+    is never the utterance's last one (T - 1 = L // hop), which reflects at the right edge and is only known at close.
+    Model step s of a session takes frame s and yields the mask of output frame s - look_ahead (none for the first
+    look_ahead steps: the drop of ``StreamingEnhancer._advance``); output frame m >= 1 emits hop samples."""
+
+    def __init__(self, capacity, look_ahead, hop=HOP):
+        if capacity < 1:
+            raise ValueError(f"capacity {capacity} < 1")
+        self.capacity, self.la, self.hop = int(capacity), int(look_ahead), int(hop)
+        self._free = list(range(self.capacity))  # kept sorted: lowest id first
+        self._s = {}
+        self._next_sid = 0
+
+    # ---- slots --------------------------------------------------------------------------------
+    def open(self):
+        if not self._free:
+            raise RuntimeError(f"StreamPool is full: all {self.capacity} slots hold an open session")
+        sid = self._next_sid
+        self._next_sid += 1
+        self._s[sid] = _Session(self._free.pop(0))
+        return sid
+
+    def session(self, sid):
+        try:
+            return self._s[sid]
+        except KeyError:
+            raise KeyError(f"StreamPool: no open session {sid!r}") from None
+
+    def slot(self, sid):
+        return self.session(sid).slot
+
+    def sids(self):
+        return sorted(self._s, key=lambda i: self._s[i].slot)
+
+    def release(self, sid):
+        s = self.session(sid)
+        del self._s[sid]
+        self._free.append(s.slot)
+        self._free.sort()
+        return s.slot
+
+    # ---- frames -------------------------------------------------------------------------------
+    def push(self, sid, n):
+        s = self.session(sid)
+        if n < 0:
+            raise ValueError("negative sample count")
+        s.n_in += int(n)
+
+    def has_frame(self, sid):
+        s = self.session(sid)
+        return not s.closing and s.n_in >= max((s.t_next + 1) * self.hop, self.hop + 1)
+
+    def ready(self):
+        """Sessions with a complete frame waiting, in slot order."""
+        return [sid for sid in self.sids() if self.has_frame(sid)]
+
+    def keep_from(self, sid):
+        """Index of the oldest sample the session still needs: two hops of history (the last frame's right-edge
+        reflection reaches one sample beyond the previous hop)."""
+        return max(self.session(sid).t_next - 2, 0) * self.hop
+
+    def take_frame(self, sid):
+        """Advance the session by its next complete frame: (frame, first_frame, samples) - the frame to analyse, the
+        output frame its model step yields (negative: none) and the samples that output frame emits."""
+        s = self.session(sid)
+        if not (self.has_frame(sid) or (s.closing and s.t_next < s.n_in // self.hop)):
+            raise RuntimeError(f"session {sid}: no complete frame")
+        t = s.t_next
+        m = t - self.la
+        n = self.hop if m >= 1 else 0
+        s.t_next += 1
+        s.steps += 1
+        if m >= 0:
+            s.frames_out += 1
+            s.frames_out_at_close += int(s.closing)
+        s.n_out += n
+        return t, m, n
+
+    def begin_close(self, sid):
+        """End of the session's input: returns the number of complete frames still to run one by one (take_frame)
+        before the last frame (take_last)."""
+        s = self.session(sid)
+        if s.n_in <= self.hop:
+            raise _lib.FsnError(f"session shorter than n_fft / 2 + 1 = {self.hop + 1} samples (reflect padding), like torch.stft")
+        s.closing = True
+        return s.n_in // self.hop - s.t_next
+
+    def take_last(self, sid):
+        """The utterance's last frame T - 1 plus the look_ahead zero frames: (frame, first_frame, k, skip, tail,
+        samples) - k = 1 + look_ahead model steps whose columns are output frames first_frame .., of which the first
+        `skip` emit nothing (frames < 1); `tail` samples follow the last frame; `samples` is the total."""
+        s = self.session(sid)
+        t = s.n_in // self.hop
+        if not s.closing or s.t_next != t:
+            raise RuntimeError(f"session {sid}: take_last before its other frames were taken")
+        k = 1 + self.la
+        m0 = t - self.la
+        skip = min(max(1 - m0, 0), k)
+        tail = s.n_in - t * self.hop
+        n = (k - skip) * self.hop + tail
+        s.t_next += 1
+        s.steps += k
+        new = k - max(-m0, 0)
+        s.frames_out += new
+        s.frames_out_at_close += new
+        s.n_out += n
+        return t, m0, k, skip, tail, n
+
+
+def _check_slots(slots, capacity):
+    ids = [int(x) for x in slots]
+    if not ids:
+        raise ValueError("empty slot list")
+    if any(i < 0 or i >= capacity for i in ids):
+        raise ValueError(f"slot ids {ids} outside [0, {capacity})")
+    if len(set(ids)) != len(ids):
+        raise ValueError(f"slot ids {ids} are not distinct")
+    return ids
+
+
+class StreamPool:
+    def __init__(self, model, capacity=64, poison_buffers=False):
+        if not getattr(model, "_fused", False):
+            raise NotImplementedError("StreamPool runs the fused FullSubNet configuration only (model._fused is false: "
+                                      "use one StreamingEnhancer per stream for composed configurations)")
+        if model.norm_type != "cumulative_laplace_norm":
+            raise ValueError("streaming needs a causal norm: build the model with norm_type = 'cumulative_laplace_norm' "
+                             "(fullsubnet/train_cumulativeLaplaceNorm.toml)")
+        self.model = model.eval()
+        self.device = next(model.parameters()).device
+        if self.device.type != "cuda":
+            raise _lib.FsnError("StreamPool needs the model on a ROCm device; this path has no CPU implementation")
+        if model.num_freqs != N_FFT // 2 + 1:
+            raise NotImplementedError(f"StreamPool is built for the 512 / 256 transform (num_freqs 257, got {model.num_freqs})")
+        self.capacity = int(capacity)
+        self._cfg = model._cfg
+        nbytes = _lib.lib().fsn_fullsubnet_stream_pool_state_bytes(ctypes.byref(self._cfg), self.capacity)
+        if nbytes == 0:
+            raise _lib.FsnError(_lib.lib().fsn_last_error().decode())
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self.slot_bytes = nbytes // self.capacity
+        self.book = SessionBook(self.capacity, model.look_ahead)
+        self._window = torch.hann_window(N_FFT, device=self.device)
+        self.poison_buffers = bool(poison_buffers)  # debugging: NaN-fill every workspace and output before its call
+        self._buf = {}   # sid -> (device samples from global index buf0 on, buf0)
+
+    # ---- the three entries on a list of slots -------------------------------------------------
+    def _ints(self, rows):
+        return torch.tensor(rows, dtype=torch.int32, device=self.device)
+
+    def _state_args(self):
+        return ctypes.byref(self._cfg), self.state.data_ptr(), self.state.numel(), self.capacity
+
+    def analysis(self, slots_dev, n, hops, prime, frame_no_dev):
+        """hops [n, hop] (and prime [n, hop] = samples 1 .. hop of the sessions at frame 0, or None) -> mag [n, 1, F, 1]."""
+        mag = torch.empty((n, 1, self.model.num_freqs, 1), dtype=torch.float32, device=self.device)
+        if self.poison_buffers:
+            mag.fill_(float("nan"))
+        _lib.check(_lib.lib().fsn_stream_pool_analysis(
+            *self._state_args(), slots_dev.data_ptr(), n, _lib.dev_ptr(hops, "hops"),
+            _lib.dev_ptr(prime, "prime", allow_none=True), frame_no_dev.data_ptr(), N_FFT, HOP, _lib.dev_ptr(self._window),
+            _lib.dev_ptr(mag), _lib.stream_ptr(self.device)))
+        return mag
+
+    def model_step(self, slots, mag, slots_dev=None):
+        """Advance the listed slots (distinct ids in [0, capacity)) by the k frames of mag [n, 1, F, k], each from its
+        own step count -> compressed cIRM [n, 2, F, k]."""
+        ids = _check_slots(slots, self.capacity)
+        n, k = len(ids), mag.shape[-1]
+        if tuple(mag.shape) != (n, 1, self.model.num_freqs, k) or k < 1:
+            raise ValueError(f"mag {tuple(mag.shape)}: need [{n}, 1, {self.model.num_freqs}, k >= 1]")
+        if slots_dev is None:
+            slots_dev = self._ints(ids)
+        L = _lib.lib()
+        crm = torch.empty((n, 2, self.model.num_freqs, k), dtype=torch.float32, device=self.device)
+        ws = _lib.workspace(L.fsn_fullsubnet_stream_pool_workspace_bytes(ctypes.byref(self._cfg), n, k), self.device)
+        if self.poison_buffers:
+            ws.view(torch.float32).fill_(float("nan"))
+            crm.fill_(float("nan"))
+        _lib.check(L.fsn_fullsubnet_stream_pool_step(
+            ctypes.byref(self._cfg), self.model.packed_weights().data_ptr(), self.state.data_ptr(), self.state.numel(),
+            self.capacity, slots_dev.data_ptr(), n, _lib.dev_ptr(mag.contiguous(), "mag"), k, _lib.dev_ptr(crm),
+            ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device)))
+        return crm
+
+    def synthesis(self, slots_dev, n, crm, first_frame_dev, tail_dev):
+        """crm [n, 2, F, k] -> out [n, (k + 1) hop]: the hop of every column that is an output frame >= 1, then the tail."""
+        k = crm.shape[-1]
+        out = torch.empty((n, (k + 1) * HOP), dtype=torch.float32, device=self.device)
+        ws = _lib.workspace(n * k * N_FFT * 4, self.device)
+        if self.poison_buffers:
+            ws.view(torch.float32).fill_(float("nan"))
+            out.fill_(float("nan"))
+        _lib.check(_lib.lib().fsn_stream_pool_synthesis(
+            *self._state_args(), slots_dev.data_ptr(), n, _lib.dev_ptr(crm, "crm"), k, first_frame_dev.data_ptr(),
+            tail_dev.data_ptr(), N_FFT, HOP, _lib.dev_ptr(self._window), _lib.dev_ptr(out), ws.data_ptr(), ws.numel(),
+            _lib.stream_ptr(self.device)))
+        return out
+
+    def reset_slots(self, slots):
+        ids = _check_slots(slots, self.capacity)
+        _lib.check(_lib.lib().fsn_fullsubnet_stream_pool_reset(*self._state_args(), self._ints(ids).data_ptr(), len(ids),
+                                                               _lib.stream_ptr(self.device)))
+
+    # ---- sessions -----------------------------------------------------------------------------
+    def open(self):
+        sid = self.book.open()
+        self._buf[sid] = (torch.zeros(0, dtype=torch.float32, device=self.device), 0)
+        return sid
+
+    def slot(self, sid):
+        return self.book.slot(sid)
+
+    def push(self, sid, chunk):
+        s = self.book.session(sid)
+        if s.closing:
+            raise RuntimeError(f"session {sid} is closing")
+        chunk = torch.as_tensor(chunk).to(self.device, torch.float32)
+        if chunk.dim() != 1:
+            raise ValueError(f"chunk must be 1-D samples, got shape {tuple(chunk.shape)}")
+        if chunk.numel():
+            buf, b0 = self._buf[sid]
+            self._buf[sid] = (torch.cat([buf, chunk]), b0)
+            self.book.push(sid, chunk.numel())
+
+    def _trim(self, sid):
+        buf, b0 = self._buf[sid]
+        keep = self.book.keep_from(sid)
+        if keep > b0:
+            self._buf[sid] = (buf[keep - b0:], keep)
+
+    @torch.no_grad()
+    def _tick(self, sids):
+        """One frame of each listed session (all have one complete): {sid: samples}."""
+        n = len(sids)
+        hops, primes, rows = [], [], [[], [], [], []]  # slots, frame numbers, first output frames, tail samples
+        counts, any_first = [], False
+        for sid in sids:
+            t, m, cnt = self.book.take_frame(sid)
+            buf, b0 = self._buf[sid]
+            hop = buf[t * HOP - b0:(t + 1) * HOP - b0]
+            hops.append(hop)
+            primes.append(buf[1 - b0:HOP + 1 - b0] if t == 0 else hop)  # only read for frame 0
+            any_first |= t == 0
+            rows[0].append(self.book.slot(sid))
+            rows[1].append(t)
+            rows[2].append(m)
+            rows[3].append(-1)
+            counts.append(cnt)
+        meta = self._ints(rows)
+        mag = self.analysis(meta[0], n, torch.stack(hops), torch.stack(primes) if any_first else None, meta[1])
+        crm = self.model_step(rows[0], mag, slots_dev=meta[0])
+        out = self.synthesis(meta[0], n, crm, meta[2], meta[3])
+        for sid in sids:
+            self._trim(sid)
+        return {sid: out[i, :cnt] for i, (sid, cnt) in enumerate(zip(sids, counts))}
+
+    def step(self):
+        """One frame for every session that has one ready: {sid: samples} (empty while the look-ahead fills)."""
+        sids = self.book.ready()
+        return self._tick(sids) if sids else {}
+
+    def drain(self):
+        """step() until no session has a frame ready; the samples concatenated per session."""
+        parts = {}
+        while True:
+            out = self.step()
+            if not out:
+                break
+            for sid, y in out.items():
+                parts.setdefault(sid, []).append(y)
+        return {sid: torch.cat(ys) for sid, ys in parts.items()}
+
+    @torch.no_grad()
+    def close(self, sid):
+        """End of the session: its remaining samples.  Complete frames that were not stepped yet run one by one (n = 1);
+        then the last frame (right-edge reflection) and the look_ahead zero frames run as ONE model call with n = 1,
+        k = 1 + look_ahead, the overlap-add tail follows, and the slot is reset and freed."""
+        left = self.book.begin_close(sid)
+        parts = [self._tick([sid])[sid] for _ in range(left)]
+        L = self.book.session(sid).n_in
+        t, m0, k, skip, tail, cnt = self.book.take_last(sid)
+        buf, b0 = self._buf[sid]
+        j = torch.arange(t * HOP, (t + 1) * HOP, device=self.device)
+        j = torch.where(j >= L, 2 * (L - 1) - j, j)  # torch.stft's reflect padding at the right edge
+        hop = buf[j - b0][None]
+        slot = self.book.slot(sid)
+        meta = self._ints([[slot], [t], [m0], [tail]])
+        mag = self.analysis(meta[0], 1, hop, None, meta[1])  # t = T - 1 >= 1: never a session's frame 0
+        mag = torch.cat([mag, mag.new_zeros(1, 1, mag.shape[2], k - 1)], dim=-1)  # fullsubnet/model.py:85
+        crm = self.model_step([slot], mag, slots_dev=meta[0])
+        out = self.synthesis(meta[0], 1, crm, meta[2], meta[3])
+        parts.append(out[0, skip * HOP:skip * HOP + cnt])
+        self.reset_slots([slot])
+        self.book.release(sid)
+        del self._buf[sid]
+        return torch.cat(parts)

@@ -221,6 +221,56 @@ int fsn_fullsubnet_stream_step(const fsn_fullsubnet_cfg* cfg, const void* packed
                                int steps_done, const float* mag, int B, int k, float* crm_out, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* ---- streaming pool: sessions that open, advance and close on their own --------------------- */
+
+/* fsn_fullsubnet_stream_step for streams that are NOT in lockstep.  `state` is a pool of `capacity` slots (1 .. 4096),
+ * fsn_fullsubnet_stream_pool_state_bytes(cfg, capacity) bytes = capacity equal records, slot s at byte
+ * s * (state_bytes / capacity).  A record holds (h, c) of the four LSTM layers, the two running fp64 norm sums, the slot's
+ * own step count (on the device: the kernels read and advance it) and the transform state of the two entries below.  All
+ * zeros is a fresh pool; fsn_fullsubnet_stream_pool_reset returns the n listed slots to that state (stream-ordered).
+ *
+ * fsn_fullsubnet_stream_pool_step advances the n listed slots (`slots`: device memory, n DISTINCT ids) by k model steps,
+ * each from its own step count: row i of mag [n, 1, F, k] and crm_out [n, 2, F, k] belongs to slots[i], and is what
+ * fsn_fullsubnet_stream_step gives a batch of one with the same history.  Slots that are not listed are not written.  A
+ * row whose id is outside [0, capacity) is skipped (its crm_out row is finite, no state is touched); listing an id twice
+ * is the caller's error.  Both size queries return 0 (fsn_last_error) for a non-causal norm or a size out of range. */
+size_t fsn_fullsubnet_stream_pool_state_bytes(const fsn_fullsubnet_cfg* cfg, int capacity);
+size_t fsn_fullsubnet_stream_pool_workspace_bytes(const fsn_fullsubnet_cfg* cfg, int n, int k);
+int fsn_fullsubnet_stream_pool_reset(const fsn_fullsubnet_cfg* cfg, void* state, size_t state_bytes, int capacity,
+                                     const int* slots, int n, void* stream);
+int fsn_fullsubnet_stream_pool_step(const fsn_fullsubnet_cfg* cfg, const void* packed, void* state, size_t state_bytes,
+                                    int capacity, const int* slots, int n, const float* mag, int k, float* crm_out,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* The transform around that step, one frame at a time for the listed slots of the same pool (n_fft = 512, hop = 256 only;
+ * cfg->num_freqs = 257).  All int arrays are device memory, [n].
+ *
+ * fsn_stream_pool_analysis: frame = the slot's last hop ++ hops[i] (hops [n][hop]) -> window -> real FFT.  The spectrum
+ * goes to the slot's ring of look_ahead + 1 frames at frame_no[i] (the session's frame index, >= 0), its magnitude to
+ * mag [n, 1, F, 1]; hops[i] becomes the slot's last hop.  The caller makes the two edges of torch.stft(center=True) by what
+ * it passes: for frame 0 (frame_no[i] == 0) the left half is the reflection y[hop], y[hop - 1] .. y[1], read backwards from
+ * prime[i] = y[1 .. hop] (prime [n][hop]; rows of sessions not at frame 0 are not read).  CONTRACT: prime may be NULL only
+ * when no listed session is at frame 0.  frame_no lives on the device, so the entry cannot check this: a frame 0 with
+ * prime == NULL takes the slot's carried hop like any other frame - zeros on a fresh slot, i.e. a zero-padded left edge
+ * instead of torch.stft's reflection - and no error is raised.  The session's last frame gets a hop that continues
+ * past the end L by reflection (sample j >= L is y[2 (L - 1) - j]).
+ *
+ * fsn_stream_pool_synthesis: column j of crm [n, 2, F, k] is the compressed mask of output frame m = first_frame[i] + j of
+ * slots[i] (m < 0: a model step of the first look_ahead frames, no output).  Frame m's spectrum is taken from the ring
+ * (so m must be one of the last look_ahead + 1 analysed frames), decompress_cIRM and the complex mask applied, then
+ * irfft, window and overlap-add with the slot's carried half frame as torch.istft does: frame m >= 1 gives the hop samples
+ * [(m - 1) hop, m hop) at out[i][j hop ..]; frame 0 gives none.  tail_samples[i] >= 0 marks the session's last frame:
+ * the samples [(T - 1) hop, L), tail_samples[i] = L - (T - 1) hop of them, follow at out[i][k hop ..] (pass -1
+ * otherwise).  out [n][(k + 1) hop] is written completely (zeros where there is no sample);
+ * workspace >= n k n_fft floats. */
+int fsn_stream_pool_analysis(const fsn_fullsubnet_cfg* cfg, void* state, size_t state_bytes, int capacity,
+                             const int* slots, int n, const float* hops, const float* prime, const int* frame_no,
+                             int n_fft, int hop, const float* window, float* mag, void* stream);
+int fsn_stream_pool_synthesis(const fsn_fullsubnet_cfg* cfg, void* state, size_t state_bytes, int capacity,
+                              const int* slots, int n, const float* crm, int k, const int* first_frame,
+                              const int* tail_samples, int n_fft, int hop, const float* window, float* out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- training step: one nn.LSTM layer with back-propagation through time ----------------- */
 
 /* audio_zen/model/module/sequence_model.py:52-58 (nn.LSTM, one layer, batch_first, h0 = c0 = 0) as
