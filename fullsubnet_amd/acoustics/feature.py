@@ -93,6 +93,11 @@ def istft(features, n_fft, hop_length, win_length, length=None, input_type="comp
     real, imag = real.contiguous(), imag.contiguous()
     B, F, T = real.shape
     assert F == n_fft // 2 + 1
+    if hop_length >= n_fft:
+        # tap 0 of the periodic Hann window is zero: sample n_fft * t is covered by that tap alone and the overlap-added
+        # squared window is zero there (fsn_hip.h, fsn_istft's contract)
+        raise RuntimeError(f"istft: window overlap add min is zero at hop_length {hop_length} >= n_fft {n_fft} "
+                           "(torch.istft raises here too)")
     if length is None:
         length = hop_length * (T - 1)
     y = torch.empty((B, length), dtype=torch.float32, device=real.device)

@@ -263,8 +263,12 @@ int fsn_launch_dft_stft(const float* y, int B, int L, const float* window, float
                            hop, F, P, N / P, frames);
         return fsn_check_launch("dft2_stft_kernel");
     }
-    hipLaunchKernelGGL(dft_stft_kernel, dim3((unsigned)(B * T), (F + 255) / 256), dim3(256), 3 * N * sizeof(double), s, y,
-                       window, re, im, mag, L, T, N, hop, F);
+    const size_t lds = 3 * N * sizeof(double);  // 96 KB at N = 4096: above 64 KB a launch needs the attribute raised
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft_stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+    hipLaunchKernelGGL(dft_stft_kernel, dim3((unsigned)(B * T), (F + 255) / 256), dim3(256), lds, s, y, window, re, im, mag, L,
+                       T, N, hop, F);
     return fsn_check_launch("dft_stft_kernel");
 }
 
@@ -281,8 +285,12 @@ int fsn_launch_dft_istft(const float* re, const float* im, const float* window, 
                            P, N / P, frames);
         FSN_TRY_LAUNCH("dft2_irfft_kernel");
     } else {
-        hipLaunchKernelGGL(dft_irfft_kernel, dim3((unsigned)(B * T), (N + 255) / 256), dim3(256),
-                           (2 * F + 2 * N) * sizeof(double), s, re, im, window, wframes, T, N, F);
+        const size_t lds = (2 * F + 2 * N) * sizeof(double);
+        if (lds > 64 * 1024)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft_irfft_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(dft_irfft_kernel, dim3((unsigned)(B * T), (N + 255) / 256), dim3(256), lds, s, re, im, window,
+                           wframes, T, N, F);
         FSN_TRY_LAUNCH("dft_irfft_kernel");
     }
     const long n = (long)B * length;

@@ -147,6 +147,7 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ y, 
     double* sim = lds[wave][1];
 
     cd v[8];
+    bool nzA = false, nzB = false;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const int n = lane + 64 * r;
@@ -164,8 +165,13 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ y, 
             j = j >= Lb ? 2 * (Lb - 1) - j : j;
             xb = y[(long)b * L + j] * w;
         }
+        nzA |= xa != 0.f;
+        nzB |= xb != 0.f;
         v[r] = cd{(double)xa, (double)xb};
     }
+    // A frame of zeros beside a live partner comes out of the split as the partner's rounding residue (~1e-16 of it), not
+    // as the zeros its transform is: such a frame is written as exact zeros.
+    const bool zeroA = __ballot(nzA) == 0, zeroB = __ballot(nzB) == 0;
     pass8<false, 1>(v, sre, sim, lane);
     wave_lds_sync();
     load8(v, sre, sim, lane);
@@ -191,6 +197,8 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ y, 
             ai = (float)(0.5 * (zi - wi));
             br = (float)(0.5 * (zi + wi));
             bi = (float)(-0.5 * (zr - wr));
+            if (zeroA) ar = ai = 0.f;
+            if (zeroB) br = bi = 0.f;
         }
         const float am = (float)sqrt((double)ar * ar + (double)ai * ai);
         const float bm = (float)sqrt((double)br * br + (double)bi * bi);
@@ -384,6 +392,7 @@ __global__ __launch_bounds__(256) void pool_analysis_kernel(char* __restrict__ s
     double* sim = lds[wave][1];
 
     cd v[8];
+    bool nzA = false, nzB = false;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const int nn = lane + 64 * r;
@@ -404,8 +413,11 @@ __global__ __launch_bounds__(256) void pool_analysis_kernel(char* __restrict__ s
             }
             x[q] = xs * w;
         }
+        nzA |= x[0] != 0.f;
+        nzB |= x[1] != 0.f;
         v[r] = cd{(double)x[0], (double)x[1]};
     }
+    const bool zeroA = __ballot(nzA) == 0, zeroB = __ballot(nzB) == 0;  // as in stft_kernel: a frame of zeros is written as zeros
     pass8<false, 1>(v, sre, sim, lane);
     wave_lds_sync();
     load8(v, sre, sim, lane);
@@ -430,6 +442,8 @@ __global__ __launch_bounds__(256) void pool_analysis_kernel(char* __restrict__ s
             ai = (float)(0.5 * (zi - wi));
             br = (float)(0.5 * (zi + wi));
             bi = (float)(-0.5 * (zr - wr));
+            if (zeroA) ar = ai = 0.f;
+            if (zeroB) br = bi = 0.f;
         }
         if (recA) {
             const long o = (long)(tA % L.R) * FP + k;

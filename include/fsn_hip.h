@@ -76,7 +76,12 @@ int fsn_stft(const float* y, int B, int L, int n_fft, int hop, int win_length, c
              float* real, float* imag, float* mag, void* stream);
 
 /* feature.py:53-91  istft((real, imag), n_fft, hop, win, length, input_type="real_imag").
- * real/imag [B, F, T] -> y [B, length].  workspace >= fsn_istft_workspace_bytes(B, T, n_fft). */
+ * real/imag [B, F, T] -> y [B, length].  workspace >= fsn_istft_workspace_bytes(B, T, n_fft).
+ * Contract: the overlap-added squared window must be non-zero at every sample written (p = n_fft/2 + j < n_fft +
+ * hop (T - 1)); the entry divides by it unchecked, like ATen's kernel after torch.istft's own check.  With a window whose
+ * first tap is zero (the periodic Hann) hop == n_fft breaks it - sample p = n_fft t is covered by tap 0 of frame t alone
+ * and comes out as 0/0 = NaN - and fullsubnet_amd's istft raises there as torch.istft does; every hop < n_fft is fine.
+ * fsn_stft at hop == n_fft is supported.  Samples at and past n_fft/2 + hop (T - 1) are written as zeros. */
 size_t fsn_istft_workspace_bytes(int B, int T, int n_fft);
 int fsn_istft(const float* real, const float* imag, int B, int T, int n_fft, int hop, int win_length,
               const float* window, int length, float* y, void* workspace, size_t workspace_bytes,
