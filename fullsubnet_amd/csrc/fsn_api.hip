@@ -484,13 +484,31 @@ extern "C" int fsn_profile_read(void* stream, float* ms, int n) {
 // ---- auxiliary stream for the left-over sub-band rows (see fsn_lstm_rec_plan) -------------------
 // One per (device, caller stream), created lazily on the caller stream's device (StreamCtx).  The fork / join
 // below uses events only, so it is also legal under stream capture.
-int aux_init(StreamCtx* c) {
+static int aux_init(StreamCtx* c) {
     if (c->aux) return FSN_OK;
     if (hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
         fsn_set_error("cannot create the auxiliary stream / events");
         c->aux = nullptr;
+        return FSN_ERR_LAUNCH;
+    }
+    return FSN_OK;
+}
+int aux_fork(hipStream_t s, hipStream_t* aux) {
+    StreamCtx* c = cur_ctx();
+    FSN_TRY(aux_init(c));
+    if (hipEventRecord(c->ev_fork, s) != hipSuccess || hipStreamWaitEvent(c->aux, c->ev_fork, 0) != hipSuccess) {
+        fsn_set_error("aux stream fork failed");
+        return FSN_ERR_LAUNCH;
+    }
+    *aux = c->aux;
+    return FSN_OK;
+}
+int aux_join(hipStream_t s) {
+    StreamCtx* c = cur_ctx();
+    if (hipEventRecord(c->ev_join, c->aux) != hipSuccess || hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess) {
+        fsn_set_error("aux stream join failed");
         return FSN_ERR_LAUNCH;
     }
     return FSN_OK;

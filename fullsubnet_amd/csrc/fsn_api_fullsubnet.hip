@@ -223,16 +223,10 @@ static CoreWs core_carve(Carver& cv, const CoreDims& d, int norm_type) {
 }
 
 // One sub-band LSTM layer over all Tp steps: the persistent kernel on `s` and, concurrently, the
-// few left-over row tiles as per-step launches on the auxiliary stream.
-// Main kernel: input projection either precomputed (`gx`, tile (t, i) at t * tiles + i) or built
-// in-kernel from `xin`.  Left-over tiles: projection tiles in `gx_left` at t * left_stride + left_off + i.
-// x_main (with wih_main, bias_main): the main rows run on lstm_rec_x_kernel, which reads the hidden sequence of the
-// layer below (x_main [Tp][Npad][H]) and forms its input projection itself.  hseq_left: the left-over rows' hidden
-// sequence goes to this compact [t][left rows][H] buffer instead of rows [main rows, Npad) of hseq.
-int run_recurrence(const float* gx, const FsnSbInput* xin, const float* gx_left, long left_stride, long left_off,
-                   const float* whh, float* hseq, float* c_left, int Tp, int Npad, int H, const FsnRecPlan& r, hipStream_t s,
-                   const FsnRecFc* fc, long left_hs_stride, const void* whh_f16x3, const void* wih_f16x3,
-                   const float* x_main, const float* wih_main, const float* bias_main, float* hseq_left) {
+// few left-over row tiles as per-step launches on the auxiliary stream (the fields of RecArgs, fsn_api_internal.h).
+int run_recurrence(const RecArgs& a, hipStream_t s) {
+    const FsnRecPlan& r = a.plan;
+    const int Tp = a.Tp, Npad = a.Npad, H = a.H;
     // No persistent part (fewer than ~160 tiles): the steps run on `s` itself - groups of four tiles through the
     // one-workgroup-per-CU step kernel, the up to three tiles that do not fill a group beside it on the
     // auxiliary stream (a 33rd group of 8 workgroups would be a second round on 8 CUs and double the step).
@@ -240,109 +234,89 @@ int run_recurrence(const float* gx, const FsnSbInput* xin, const float* gx_left,
     const int aux_tiles = r.left_tiles - cu_tiles;
     const bool fork = aux_tiles > 0 && (r.main_wgs > 0 || cu_tiles > 0);
     hipStream_t ls = s;
-    StreamCtx* cx = nullptr;
-    if (fork) {
-        cx = cur_ctx();
-        FSN_TRY(aux_init(cx));
-        if (hipEventRecord(cx->ev_fork, s) != hipSuccess || hipStreamWaitEvent(cx->aux, cx->ev_fork, 0) != hipSuccess) {
-            fsn_set_error("aux stream fork failed");
-            return FSN_ERR_LAUNCH;
-        }
-        ls = cx->aux;
-    }
+    if (fork) FSN_TRY(aux_fork(s, &ls));
     if (r.main_wgs > 0) {
-        if (x_main)
-            FSN_TRY(fsn_launch_lstm_rec_x(x_main, wih_main, whh, bias_main, Tp, Npad, H, r.rt, r.main_wgs, s, fc,
-                                          fc ? nullptr : hseq));  // no output layer: a layer inside a stack, h_t stored
-        else if (xin && !fc && !whh_f16x3 && fsn_lstm_rec_in_supported(xin, whh, H, r.rt))
-            FSN_TRY(fsn_launch_lstm_rec_in(xin, whh, hseq, Tp, Npad, H, r.rt, r.main_wgs, s));
-        else if (whh_f16x3 && fc && !xin && r.rt >= 2)  // experimental split-precision persistent kernel (FSN_F16X3=1)
-            FSN_TRY(fsn_launch_lstm_rec_f16x3(gx, whh_f16x3, Tp, Npad, H, r.rt, r.main_wgs, fc, s));
-        else if (whh_f16x3 && wih_f16x3 && xin && !xin->x_rows && xin->kin_chunks == 2 && r.rt >= 2)
-            FSN_TRY(fsn_launch_lstm_rec_xin_f16x3(xin, wih_f16x3, whh_f16x3, hseq, Tp, Npad, H, r.rt, r.main_wgs, s));
+        if (a.x_main)
+            FSN_TRY(fsn_launch_lstm_rec_x(a.x_main, a.wih_main, a.whh, a.bias_main, Tp, Npad, H, r.rt, r.main_wgs, s, a.fc,
+                                          a.fc ? nullptr : a.hseq));  // no output layer: a layer inside a stack, h_t stored
+        else if (a.xin && !a.fc && !a.whh_f16x3 && fsn_lstm_rec_in_supported(a.xin, a.whh, H, r.rt))
+            FSN_TRY(fsn_launch_lstm_rec_in(a.xin, a.whh, a.hseq, Tp, Npad, H, r.rt, r.main_wgs, s));
+        else if (a.whh_f16x3 && a.fc && !a.xin && r.rt >= 2)  // experimental split-precision persistent kernel (FSN_F16X3=1)
+            FSN_TRY(fsn_launch_lstm_rec_f16x3(a.gx, a.whh_f16x3, Tp, Npad, H, r.rt, r.main_wgs, a.fc, s));
+        else if (a.whh_f16x3 && a.wih_f16x3 && a.xin && !a.xin->x_rows && a.xin->kin_chunks == 2 && r.rt >= 2)
+            FSN_TRY(fsn_launch_lstm_rec_xin_f16x3(a.xin, a.wih_f16x3, a.whh_f16x3, a.hseq, Tp, Npad, H, r.rt, r.main_wgs, s));
         else
-            FSN_TRY(fsn_launch_lstm_rec(gx, xin, whh, hseq, Tp, Npad, H, r.rt, r.main_wgs, s, fc));
+            FSN_TRY(fsn_launch_lstm_rec(a.gx, a.xin, a.whh, a.hseq, Tp, Npad, H, r.rt, r.main_wgs, s, a.fc));
     }
     if (r.left_tiles > 0) {
         // left-over rows of step t: rows [main_rows, Npad) of the full [t][Npad] matrix, or - when the
         // persistent part stores nothing (fused output layer) - a compact [t][left rows] matrix
-        if (hseq_left) left_hs_stride = (long)r.left_tiles * 16;
-        float* hl = hseq_left ? hseq_left : hseq;
+        const long left_hs_stride = a.hseq_left ? (long)r.left_tiles * 16 : a.left_hs_stride;
+        float* hl = a.hseq_left ? a.hseq_left : a.hseq;
         const long hs_stride = left_hs_stride >= 0 ? left_hs_stride : Npad;
         const long hs_off = left_hs_stride >= 0 ? 0 : (long)r.main_wgs * r.rt * 16;
         for (int t = 0; t < Tp; ++t) {
             float* h_out = hl + ((size_t)t * hs_stride + hs_off) * H;
             const float* h_prev = t ? hl + ((size_t)(t - 1) * hs_stride + hs_off) * H : h_out;
-            const long gx_rt0 = (long)t * left_stride + left_off;
+            const long gx_rt0 = (long)t * a.left_stride + a.left_off;
             if (cu_tiles > 0)
-                FSN_TRY(fsn_launch_lstm_step_cu(gx_left, whh, h_prev, h_out, c_left, gx_rt0, cu_tiles, H, t == 0, s));
+                FSN_TRY(fsn_launch_lstm_step_cu(a.gx_left, a.whh, h_prev, h_out, a.c_left, gx_rt0, cu_tiles, H, t == 0, s));
             if (aux_tiles > 0) {
                 const size_t ro = (size_t)cu_tiles * 16 * H;
-                FSN_TRY(fsn_launch_lstm_step(gx_left, whh, h_prev + ro, h_out + ro, c_left + ro, gx_rt0 + cu_tiles,
+                FSN_TRY(fsn_launch_lstm_step(a.gx_left, a.whh, h_prev + ro, h_out + ro, a.c_left + ro, gx_rt0 + cu_tiles,
                                              aux_tiles, H, t == 0, ls, fork ? 1 : 0));
             }
         }
     }
-    if (fork) {
-        if (hipEventRecord(cx->ev_join, cx->aux) != hipSuccess || hipStreamWaitEvent(s, cx->ev_join, 0) != hipSuccess) {
-            fsn_set_error("aux stream join failed");
-            return FSN_ERR_LAUNCH;
-        }
-    }
+    if (fork) FSN_TRY(aux_join(s));
     return FSN_OK;
 }
 
-static int run_sb_recurrence(const float* gx, const FsnSbInput* xin, const float* gx_left, long left_stride,
-                             long left_off, const float* whh, float* hseq, float* c_left, const CoreDims& d,
-                             hipStream_t s, const FsnRecFc* fc = nullptr, const void* whh_f16x3 = nullptr,
-                             const void* wih_f16x3 = nullptr, const float* x_main = nullptr,
-                             const float* wih_main = nullptr, const float* bias_main = nullptr,
-                             float* hseq_left = nullptr) {
-    return run_recurrence(gx, xin, gx_left, left_stride, left_off, whh, hseq, c_left, d.Tp, d.Npad, d.Hs, d.rec, s,
-                          fc, fc ? (long)d.rec.left_tiles * 16 : -1, whh_f16x3, wih_f16x3, x_main, wih_main,
-                          bias_main, hseq_left);
+// ---- one core call, stage by stage ------------------------------------------------------------------------------------
+// What every stage reads.  lengths (device, [d.B], may be NULL): a ragged batch (fsn_enhance_ragged) - only the offline
+// norm's divisors depend on an utterance's length (magT is zero past its frames); the cumulative norm and the models are
+// causal and run to d.Tp.
+struct CoreCall {
+    const fsn_fullsubnet_cfg* cfg;
+    Packed p;
+    const float* pk;
+    const float* magT;
+    const CoreDims& d;
+    const CoreWs& w;
+    ModelGeom g;
+    bool cum;
+    float *crm_r, *crm_i;
+    const int* lengths;
+    hipStream_t s;
+};
+static CoreCall core_call(const fsn_fullsubnet_cfg* cfg, const float* pk, const float* magT, const CoreDims& d, const CoreWs& w,
+                          float* crm_r, float* crm_i, hipStream_t s, const int* lengths) {
+    return CoreCall{cfg, packed_layout(cfg), pk, magT, d, w, ModelGeom{d.B, d.Tp, d.T, d.F, d.FP, d.nb, d.la},
+                    cfg->norm_type == FSN_NORM_CUMULATIVE_LAPLACE, crm_r, crm_i, lengths, s};
 }
 
-// lengths (device, [d.B], may be NULL): a ragged batch (fsn_enhance_ragged) - only the offline norm's divisors depend on
-// an utterance's length (magT is zero past its frames); the cumulative norm and the models are causal and run to d.Tp.
-static int run_core(const fsn_fullsubnet_cfg* cfg, const float* pk, const float* magT, const CoreDims& d,
-                    const CoreWs& w, float* crm_r, float* crm_i, hipStream_t s, bool fullband_only = false,
-                    const int* lengths = nullptr) {
-    const Packed p = packed_layout(cfg);
-    const bool cum = cfg->norm_type == FSN_NORM_CUMULATIVE_LAPLACE;
-
-    // full-band norm divisor (fullsubnet/model.py:92)
+// full-band norm divisor (fullsubnet/model.py:92) and model (model.py:95): 2 LSTM layers + Linear + ReLU -> w.fb_out
+static int core_fullband(const CoreCall& k) {
+    const CoreDims& d = k.d;
+    const CoreWs& w = k.w;
+    const Packed& p = k.p;
+    const float* pk = k.pk;
+    hipStream_t s = k.s;
     {
         StageTimer st(ST_NORM, s);
-        if (cum) {
-            FSN_TRY(fsn_launch_cumulative_den_fb(magT, w.den_fb, d.B, d.Tp, d.F, d.FP, s));
+        if (k.cum) {
+            FSN_TRY(fsn_launch_cumulative_den_fb(k.magT, w.den_fb, d.B, d.Tp, d.F, d.FP, s));
         } else {
-            FSN_TRY(fsn_launch_binsum(magT, w.binsum, d.B, d.Tp, d.FP, s));
+            FSN_TRY(fsn_launch_binsum(k.magT, w.binsum, d.B, d.Tp, d.FP, s));
             FSN_TRY(fsn_launch_offline_den(w.binsum, nullptr, w.den_fb, nullptr, d.B, d.Tp, d.F, d.FP, d.nb, 0, s,
-                                           lengths, d.T));
+                                           k.lengths, d.T));
         }
     }
-    // full-band model (model.py:95): 2 LSTM layers + Linear + ReLU
     const int fb_rt = d.Tp * d.Npad_fb / 16;
-    FsnGemmA a{};
-    FsnGemmC c{};
     {
         StageTimer st(ST_FB_GEMM, s);
-        a = FsnGemmA{};
-        c = FsnGemmC{};
-        a.kind = 1;
-        a.p0 = magT;
-        a.den = w.den_fb;
-        a.den_mode = cum ? 1 : 0;
-        a.B = d.B;
-        a.Tp = d.Tp;
-        a.F = d.F;
-        a.FP = d.FP;
-        a.Npad = d.Npad_fb;
-        c.kind = 0;
-        c.p0 = w.gx_fb;
-        c.bias = pk + p.fb_b0;
-        FSN_TRY(fsn_launch_gemm(a, pk + p.fb_wih0, c, fb_rt, 4 * d.Hf / 16, d.FP / 16, s));
+        FSN_TRY(fsn_launch_gemm(gemm_a_fullband(k.g, k.magT, w.den_fb, k.cum ? 1 : 0, d.Npad_fb), pk + p.fb_wih0,
+                                gemm_c_frag(w.gx_fb, pk + p.fb_b0), fb_rt, 4 * d.Hf / 16, d.FP / 16, s));
     }
     {
         // N = B rows only: a chain of tiny dependent launches, so the two layers advance as a wavefront
@@ -360,293 +334,193 @@ static int run_core(const fsn_fullsubnet_cfg* cfg, const float* pk, const float*
                                                w.c_fb, w.c_fb + (size_t)d.Npad_fb * d.Hf, d.Tp, d.Npad_fb / 16, d.Hf, s));
         }
     }
+    StageTimer st(ST_FB_GEMM, s);
+    return fsn_launch_gemm(gemm_a_rows(w.hseq_fb1, d.Hf), pk + p.fb_fc, gemm_c_fb_out(k.g, w.fb_out, pk + p.fb_fcb, d.Npad_fb),
+                           fb_rt, d.FP / 16, d.Hf / 16, s);
+}
+
+// sub-band norm divisor over the (virtual) concatenated sub-band input (model.py:110-111)
+static int core_sb_divisor(const CoreCall& k) {
+    const CoreDims& d = k.d;
+    const CoreWs& w = k.w;
+    StageTimer st(ST_NORM, k.s);
+    if (k.cum) return fsn_launch_cumulative_den_sb(k.magT, w.fb_out, w.den_sb, d.B, d.Tp, d.F, d.FP, d.nb, d.den_stride, k.s);
+    return fsn_launch_offline_den(w.binsum, w.fb_out, nullptr, w.den_sb, d.B, d.Tp, d.F, d.FP, d.nb, 1, k.s, k.lengths, d.T);
+}
+
+// Projection of layer 0 for the `tiles` row tiles per step from local row `first` on -> w.gx_sb (rows that run step by step)
+static int core_sb_projection(const CoreCall& k, const FsnSbInput& xin, long first, int tiles) {
+    StageTimer st(ST_SB_GEMM_L0, k.s);
+    // the provider works on global rows: first row and row limit
+    return fsn_launch_gemm(gemm_a_subband(xin, k.d.row0 + first, tiles * 16), k.pk + k.p.sb_wih0,
+                           gemm_c_frag(k.w.gx_sb, k.pk + k.p.sb_b0), k.d.Tp * tiles, 4 * k.d.Hs / 16, k.p.sb_kin_pad / 16, k.s);
+}
+// Output layer (model.py:53-61,129-135) of the `tiles` row tiles per step from local row `first` on, w.hseq_sb1 -> mask planes
+static int core_sb_output(const CoreCall& k, long first, int tiles, hipStream_t s) {
+    const CoreDims& d = k.d;
+    // global rows, like the A provider above
+    return fsn_launch_gemm(gemm_a_rows(k.w.hseq_sb1, d.Hs), k.pk + k.p.sb_fc,
+                           gemm_c_masks(k.g, k.crm_r, k.crm_i, k.pk + k.p.sb_fcb, tiles * 16, d.row0 + first, d.row0 + d.N),
+                           d.Tp * tiles, 1, d.Hs / 16, s);
+}
+
+// Few rows (6 - 9 utterances): both layers + output layer of the first 64 x clusters rows as ONE persistent launch
+// (lstm_group_kernels.hip); what does not fill a cluster runs beside it on the auxiliary stream as the two-layer
+// wavefront of per-step launches (its projection GEMM first, its output layer last).
+static int core_sb_group(const CoreCall& k, const FsnSbInput& xin, const FsnRecFc& fc) {
+    const CoreDims& d = k.d;
+    const CoreWs& w = k.w;
+    const Packed& p = k.p;
+    const float* pk = k.pk;
+    hipStream_t s = k.s;
+    const long grp_rows = (long)d.grp_clusters * 64;
+    const int aux_tiles = d.rec.tiles - d.grp_clusters * 4;
+    FsnSbInput gin = xin;  // the launch's own rows only
+    gin.N = d.N < grp_rows ? d.N : (int)grp_rows;
+    FsnRecFc gfc = fc;
+    gfc.N = gin.N;
+    // The group kernel fills every CU with two 216-register workgroups: what runs beside it must fit in the 80
+    // registers per lane that are left - the two-layer wavefront step kernel (78) and the output-layer GEMM (52) do,
+    // the projection GEMM of the left-over rows does not, so it goes first, on the caller's stream.
+    hipStream_t as = s;
+    if (aux_tiles > 0) {
+        FSN_TRY(core_sb_projection(k, xin, grp_rows, aux_tiles));
+        FSN_TRY(aux_fork(s, &as));
+    }
     {
-        StageTimer st(ST_FB_GEMM, s);
-        a = FsnGemmA{};
-        c = FsnGemmC{};
-        a.kind = 0;
-        a.p0 = w.hseq_fb1;
-        a.ld = d.Hf;
-        c.kind = 1;
-        c.p0 = w.fb_out;
-        c.bias = pk + p.fb_fcb;
-        c.B = d.B;
-        c.Tp = d.Tp;
-        c.F = d.F;
-        c.FP = d.FP;
-        c.Npad = d.Npad_fb;
-        FSN_TRY(fsn_launch_gemm(a, pk + p.fb_fc, c, fb_rt, d.FP / 16, d.Hf / 16, s));
+        StageTimer st(ST_SB_REC_L0, s);
+        FSN_PERSIST_BEGIN(s);
+        FSN_TRY(fsn_launch_lstm2_group(&gin, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_whh1, pk + p.sb_b1,
+                                       w.grp_exchange, w.grp_flags, &gfc, d.Tp, d.grp_clusters, d.Hs, s));
     }
-    if (fullband_only) return FSN_OK;  // fsn_fullsubnet_fullband: w.fb_out is the result
-    // sub-band norm divisor over the (virtual) concatenated sub-band input (model.py:110-111)
+    if (aux_tiles > 0) {
+        FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_sb, aux_tiles, 0, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_b1_frag,
+                                           pk + p.sb_whh1, w.hseq_sb0, w.hseq_sb1, (long)aux_tiles * 16, 0, w.c_left,
+                                           w.c_left + (size_t)aux_tiles * 16 * d.Hs, d.Tp, aux_tiles, d.Hs, as, nullptr,
+                                           nullptr, 1));
+        FSN_TRY(core_sb_output(k, grp_rows, aux_tiles, as));
+        FSN_TRY(aux_join(s));
+    }
+    // a spin bound hit inside the group launch (see fsn_launch_poison_if): the mask planes become NaN instead of
+    // garbage - AFTER the join: the left-over rows' output layer on the auxiliary stream writes into the same planes
+    // (poisoned before it, a launch that gave up early left those rows finite: one run of the residency test in many)
+    const unsigned* st_word = w.grp_flags + fsn_lstm2_group_status_word(d.grp_clusters);
+    FSN_TRY(fsn_launch_poison_if(st_word, k.crm_r, (size_t)d.B * d.T * d.FP, s));
+    return fsn_launch_poison_if(st_word, k.crm_i, (size_t)d.B * d.T * d.FP, s);
+}
+
+// Small batches (no persistent part, below the group kernel's range): the projection of every row, both layers as one
+// wavefront of per-step launches on it, the output layer as a GEMM.
+static int core_sb_wavefront(const CoreCall& k, const FsnSbInput& xin) {
+    const CoreDims& d = k.d;
+    const CoreWs& w = k.w;
+    const Packed& p = k.p;
+    const float* pk = k.pk;
+    hipStream_t s = k.s;
+    FSN_TRY(core_sb_projection(k, xin, 0, d.rec.left_tiles));
     {
-        StageTimer st(ST_NORM, s);
-        if (cum) {
-            FSN_TRY(fsn_launch_cumulative_den_sb(magT, w.fb_out, w.den_sb, d.B, d.Tp, d.F, d.FP, d.nb, d.den_stride, s));
-        } else {
-            FSN_TRY(fsn_launch_offline_den(w.binsum, w.fb_out, nullptr, w.den_sb, d.B, d.Tp, d.F, d.FP, d.nb, 1, s,
-                                           lengths, d.T));
-        }
-    }
-    if (d.grp_clusters > 0) {
-        // Few rows (6 - 9 utterances): both layers + output layer of the first 64 x clusters rows as ONE persistent launch
-        // (lstm_group_kernels.hip); what does not fill a cluster runs beside it on the auxiliary stream as the two-layer
-        // wavefront of per-step launches (its projection GEMM first, its output layer last).
-        const long grp_rows = (long)d.grp_clusters * 64;
-        const int aux_tiles = d.rec.tiles - d.grp_clusters * 4;
-        FsnSbInput xin{};
-        xin.mag = magT;
-        xin.fb_out = w.fb_out;
-        xin.den = w.den_sb;
-        xin.wih_p = pk + p.sb_wih0;
-        xin.bias = pk + p.sb_b0;
-        xin.den_mode = cum ? 1 : 0;
-        xin.den_stride = d.den_stride;
-        xin.row0 = d.row0;
-        xin.B = d.B;
-        xin.Tp = d.Tp;
-        xin.F = d.F;
-        xin.FP = d.FP;
-        xin.N = d.N < grp_rows ? d.N : (int)grp_rows;
-        xin.nb = d.nb;
-        xin.kin_chunks = p.sb_kin_pad / 16;
-        FsnRecFc gfc{};
-        gfc.w_p = pk + p.sb_fc;
-        gfc.bias = pk + p.sb_fcb;
-        gfc.crm_r = crm_r;
-        gfc.crm_i = crm_i;
-        gfc.N = xin.N;
-        gfc.row0 = d.row0;
-        gfc.F = d.F;
-        gfc.FP = d.FP;
-        gfc.T = d.T;
-        gfc.la = d.la;
-        // The group kernel fills every CU with two 216-register workgroups: what runs beside it must fit in the 80
-        // registers per lane that are left - the two-layer wavefront step kernel (78) and the output-layer GEMM (52) do,
-        // the projection GEMM of the left-over rows does not, so it goes first, on the caller's stream.
-        StreamCtx* cx = nullptr;
-        hipStream_t as = s;
-        if (aux_tiles > 0) {
-            a = FsnGemmA{};
-            c = FsnGemmC{};
-            a.kind = 2;
-            a.p0 = magT;
-            a.p1 = w.fb_out;
-            a.den = w.den_sb;
-            a.den_mode = cum ? 1 : 0;
-            a.den_stride = d.den_stride;
-            a.B = d.B;
-            a.Tp = d.Tp;
-            a.F = d.F;
-            a.FP = d.FP;
-            a.Npad = aux_tiles * 16;
-            a.n_offset = (int)(d.row0 + grp_rows);
-            a.N = (int)(d.row0 + d.N);
-            a.nb = d.nb;
-            c.kind = 0;
-            c.p0 = w.gx_sb;
-            c.bias = pk + p.sb_b0;
-            {
-                StageTimer st(ST_SB_GEMM_L0, s);
-                FSN_TRY(fsn_launch_gemm(a, pk + p.sb_wih0, c, d.Tp * aux_tiles, 4 * d.Hs / 16, p.sb_kin_pad / 16, s));
-            }
-            cx = cur_ctx();
-            FSN_TRY(aux_init(cx));
-            if (hipEventRecord(cx->ev_fork, s) != hipSuccess || hipStreamWaitEvent(cx->aux, cx->ev_fork, 0) != hipSuccess) {
-                fsn_set_error("aux stream fork failed");
-                return FSN_ERR_LAUNCH;
-            }
-            as = cx->aux;
-        }
-        {
-            StageTimer st(ST_SB_REC_L0, s);
-            FSN_PERSIST_BEGIN(s);
-            FSN_TRY(fsn_launch_lstm2_group(&xin, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_whh1, pk + p.sb_b1,
-                                           w.grp_exchange, w.grp_flags, &gfc, d.Tp, d.grp_clusters, d.Hs, s));
-        }
-        if (aux_tiles > 0) {
-            FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_sb, aux_tiles, 0, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_b1_frag,
-                                               pk + p.sb_whh1, w.hseq_sb0, w.hseq_sb1, (long)aux_tiles * 16, 0, w.c_left,
-                                               w.c_left + (size_t)aux_tiles * 16 * d.Hs, d.Tp, aux_tiles, d.Hs, as, nullptr,
-                                               nullptr, 1));
-            a = FsnGemmA{};
-            c = FsnGemmC{};
-            a.kind = 0;
-            a.p0 = w.hseq_sb1;
-            a.ld = d.Hs;
-            c.kind = 2;
-            c.p0 = crm_r;
-            c.p1 = crm_i;
-            c.bias = pk + p.sb_fcb;
-            c.T = d.T;
-            c.F = d.F;
-            c.FP = d.FP;
-            c.Npad = aux_tiles * 16;
-            c.N = (int)(d.row0 + d.N);
-            c.n_off = (int)(d.row0 + grp_rows);
-            c.la = d.la;
-            FSN_TRY(fsn_launch_gemm(a, pk + p.sb_fc, c, d.Tp * aux_tiles, 1, d.Hs / 16, as));
-            if (hipEventRecord(cx->ev_join, cx->aux) != hipSuccess || hipStreamWaitEvent(s, cx->ev_join, 0) != hipSuccess) {
-                fsn_set_error("aux stream join failed");
-                return FSN_ERR_LAUNCH;
-            }
-        }
-        // a spin bound hit inside the group launch (see fsn_launch_poison_if): the mask planes become NaN instead of
-        // garbage - AFTER the join: the left-over rows' output layer on the auxiliary stream writes into the same planes
-        // (poisoned before it, a launch that gave up early left those rows finite: one run of the residency test in many)
-        const unsigned* st_word = w.grp_flags + fsn_lstm2_group_status_word(d.grp_clusters);
-        FSN_TRY(fsn_launch_poison_if(st_word, crm_r, (size_t)d.B * d.T * d.FP, s));
-        FSN_TRY(fsn_launch_poison_if(st_word, crm_i, (size_t)d.B * d.T * d.FP, s));
-        return FSN_OK;
-    }
-    // sub-band model (model.py:121-128): N = B F sequences, 2 LSTM layers + Linear(2)
-    const int sb_rt = (int)((long)d.Tp * d.Npad / 16);
-    // Layer 0: the K = 2nb+2 input projection is fused into the persistent recurrent kernel (no 19 GB
-    // gx round trip); only the few left-over tiles, which run step by step, get a precomputed gx.
-    const long main_rows = (long)d.rec.main_wgs * d.rec.rt * 16;
-    if (d.rec.left_tiles > 0) {
-        StageTimer st(ST_SB_GEMM_L0, s);
-        a = FsnGemmA{};
-        c = FsnGemmC{};
-        a.kind = 2;
-        a.p0 = magT;
-        a.p1 = w.fb_out;
-        a.den = w.den_sb;
-        a.den_mode = cum ? 1 : 0;
-        a.den_stride = d.den_stride;
-        a.B = d.B;
-        a.Tp = d.Tp;
-        a.F = d.F;
-        a.FP = d.FP;
-        a.Npad = d.rec.left_tiles * 16;
-        a.n_offset = (int)(d.row0 + main_rows);  // the provider works on global rows: first row and row limit
-        a.N = (int)(d.row0 + d.N);
-        a.nb = d.nb;
-        c.kind = 0;
-        c.p0 = w.gx_sb;
-        c.bias = pk + p.sb_b0;
-        FSN_TRY(fsn_launch_gemm(a, pk + p.sb_wih0, c, d.Tp * d.rec.left_tiles, 4 * d.Hs / 16, p.sb_kin_pad / 16, s));
-    }
-    // Small batches (no persistent part): both layers as one wavefront of per-step launches on the
-    // projection computed above.
-    const bool sb_wave = d.rec.main_wgs == 0 && d.rec.left_tiles < kWavefrontBelowTiles;
-    if (sb_wave) {
         StageTimer st(ST_SB_REC_L0, s);
         FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_sb, d.rec.left_tiles, 0, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_b1_frag,
                                            pk + p.sb_whh1, w.hseq_sb0, w.hseq_sb1, d.Npad, 0, w.c_left,
                                            w.c_left + (size_t)d.rec.left_tiles * 16 * d.Hs, d.Tp, d.rec.left_tiles,
                                            d.Hs, s));
-    } else {
-        StageTimer st(ST_SB_REC_L0, s);
-        FsnSbInput xin{};
-        xin.mag = magT;
-        xin.fb_out = w.fb_out;
-        xin.den = w.den_sb;
-        xin.wih_p = pk + p.sb_wih0;
-        xin.bias = pk + p.sb_b0;
-        xin.den_mode = cum ? 1 : 0;
-        xin.den_stride = d.den_stride;
-        xin.row0 = d.row0;
-        xin.B = d.B;
-        xin.Tp = d.Tp;
-        xin.F = d.F;
-        xin.FP = d.FP;
-        xin.N = d.N;
-        xin.nb = d.nb;
-        xin.kin_chunks = p.sb_kin_pad / 16;
-        const bool f16x3 = cfg->arith == FSN_ARITH_F16X3;  // opt-in experiment, chosen by the caller
-        const bool l0_split = f16x3 && d.Hs == 384 && 2 * d.nb + 2 == 32;
-        FSN_TRY(run_sb_recurrence(nullptr, &xin, w.gx_sb, d.rec.left_tiles, 0, pk + p.sb_whh0, w.hseq_sb0, w.c_left,
-                                  d, s, nullptr, l0_split ? pk + p.sb_whh0_f16x3 : nullptr,
-                                  l0_split ? pk + p.sb_wih0_f16x3 : nullptr, nullptr, nullptr, nullptr,
-                                  d.l1x ? w.hseq_left0 : nullptr));
     }
-    if (!sb_wave && d.l1x) {
+    StageTimer st(ST_SB_FC, s);
+    return core_sb_output(k, 0, d.Npad / 16, s);
+}
+
+// The persistent pair: each layer as one persistent launch over its main rows, the few left-over row tiles step by step
+// beside it (run_recurrence).
+static int core_sb_persistent(const CoreCall& k, const FsnSbInput& xin, const FsnRecFc& fc) {
+    const CoreDims& d = k.d;
+    const CoreWs& w = k.w;
+    const Packed& p = k.p;
+    const float* pk = k.pk;
+    hipStream_t s = k.s;
+    const int sb_rt = (int)((long)d.Tp * d.Npad / 16);
+    const long main_rows = (long)d.rec.main_wgs * d.rec.rt * 16;
+    const bool f16x3 = k.cfg->arith == FSN_ARITH_F16X3;  // opt-in experiment, chosen by the caller
+    // Output layer: where the persistent 4-pass kernel runs layer 1 it forms the two mask values of a row from h_t in
+    // LDS and that layer's 4.8 GB hidden sequence is never written or read back; only rows that went step by step
+    // (the left-over tiles) go through the GEMM at the end.
+    const bool fc_fused = d.fc_fused;
+    RecArgs both;  // what the two layers' calls share
+    both.gx_left = w.gx_sb;
+    both.c_left = w.c_left;
+    both.Tp = d.Tp;
+    both.Npad = d.Npad;
+    both.H = d.Hs;
+    both.plan = d.rec;
+    // Layer 0: the K = 2nb+2 input projection is fused into the persistent recurrent kernel (no 19 GB
+    // gx round trip); only the few left-over tiles, which run step by step, get a precomputed gx.
+    if (d.rec.left_tiles > 0) FSN_TRY(core_sb_projection(k, xin, main_rows, d.rec.left_tiles));
+    {
+        StageTimer st(ST_SB_REC_L0, s);
+        const bool l0_split = f16x3 && d.Hs == 384 && 2 * d.nb + 2 == 32;
+        RecArgs l0 = both;
+        l0.xin = &xin;
+        l0.left_stride = d.rec.left_tiles;
+        l0.whh = pk + p.sb_whh0;
+        l0.hseq = w.hseq_sb0;
+        l0.whh_f16x3 = l0_split ? pk + p.sb_whh0_f16x3 : nullptr;
+        l0.wih_f16x3 = l0_split ? pk + p.sb_wih0_f16x3 : nullptr;
+        l0.hseq_left = d.l1x ? w.hseq_left0 : nullptr;
+        FSN_TRY(run_recurrence(l0, s));
+    }
+    RecArgs l1 = both;
+    l1.whh = pk + p.sb_whh1;
+    l1.hseq = w.hseq_sb1;
+    l1.fc = fc_fused ? &fc : nullptr;
+    l1.left_hs_stride = fc_fused ? (long)d.rec.left_tiles * 16 : -1;
+    if (d.l1x) {
         // the main rows form this projection inside lstm_rec_x_kernel; only the left-over rows (step kernels) get one
         if (d.rec.left_tiles > 0) {
             StageTimer st(ST_SB_GEMM_L1, s);
-            a = FsnGemmA{};
-            c = FsnGemmC{};
-            a.kind = 0;
-            a.p0 = w.hseq_left0;
-            a.ld = d.Hs;
-            c.kind = 0;
-            c.p0 = w.gx_sb;
-            c.bias = pk + p.sb_b1;
-            FSN_TRY(fsn_launch_gemm(a, pk + p.sb_wih1, c, d.Tp * d.rec.left_tiles, 4 * d.Hs / 16, d.Hs / 16, s));
+            FSN_TRY(fsn_launch_gemm(gemm_a_rows(w.hseq_left0, d.Hs), pk + p.sb_wih1, gemm_c_frag(w.gx_sb, pk + p.sb_b1),
+                                    d.Tp * d.rec.left_tiles, 4 * d.Hs / 16, d.Hs / 16, s));
         }
-    } else if (!sb_wave) {
+        l1.left_stride = d.rec.left_tiles;
+        l1.x_main = w.hseq_sb0;
+        l1.wih_main = pk + p.sb_wih1;
+        l1.bias_main = pk + p.sb_b1;
+    } else {
         StageTimer st(ST_SB_GEMM_L1, s);
-        a = FsnGemmA{};
-        c = FsnGemmC{};
-        a.kind = 0;
-        a.p0 = w.hseq_sb0;
-        a.ld = d.Hs;
-        c.kind = 0;
-        c.p0 = w.gx_sb;
-        c.bias = pk + p.sb_b1;
-        const bool f16x3 = cfg->arith == FSN_ARITH_F16X3;  // opt-in experiment, chosen by the caller
         if (f16x3)
             FSN_TRY(fsn_launch_gemm_f16x3(w.hseq_sb0, d.Hs, pk + p.sb_wih1_f16x3, pk + p.sb_b1, w.gx_sb, sb_rt, 4 * d.Hs,
                                           d.Hs, s));
         else
-            FSN_TRY(fsn_launch_gemm(a, pk + p.sb_wih1, c, sb_rt, 4 * d.Hs / 16, d.Hs / 16, s));
+            FSN_TRY(fsn_launch_gemm(gemm_a_rows(w.hseq_sb0, d.Hs), pk + p.sb_wih1, gemm_c_frag(w.gx_sb, pk + p.sb_b1), sb_rt,
+                                    4 * d.Hs / 16, d.Hs / 16, s));
+        l1.gx = w.gx_sb;
+        l1.left_stride = d.rec.tiles;
+        l1.left_off = main_rows / 16;
+        l1.whh_f16x3 = f16x3 && fc_fused ? pk + p.sb_whh1_f16x3 : nullptr;
     }
-    // Output layer (model.py:53-61,129-135).  Where the persistent 4-pass kernel runs layer 1 it forms the two
-    // mask values of a row from h_t in LDS and that layer's 4.8 GB hidden sequence is never written or read
-    // back; only rows that went step by step (left-over tiles, small batches) go through the GEMM below.
-    const bool fc_fused = d.fc_fused;
-    FsnRecFc fc{};
-    if (fc_fused) {
-        fc.w_p = pk + p.sb_fc;
-        fc.bias = pk + p.sb_fcb;
-        fc.crm_r = crm_r;
-        fc.crm_i = crm_i;
-        fc.N = d.N;
-        fc.row0 = d.row0;
-        fc.F = d.F;
-        fc.FP = d.FP;
-        fc.T = d.T;
-        fc.la = d.la;
-    }
-    if (!sb_wave && d.l1x) {
+    {
         StageTimer st(ST_SB_REC_L1, s);
-        FSN_TRY(run_sb_recurrence(nullptr, nullptr, w.gx_sb, d.rec.left_tiles, 0, pk + p.sb_whh1, w.hseq_sb1, w.c_left, d,
-                                  s, &fc, nullptr, nullptr, w.hseq_sb0, pk + p.sb_wih1, pk + p.sb_b1));
-    } else if (!sb_wave) {
-        StageTimer st(ST_SB_REC_L1, s);
-        const bool f16x3 = cfg->arith == FSN_ARITH_F16X3;  // opt-in experiment, chosen by the caller
-        FSN_TRY(run_sb_recurrence(w.gx_sb, nullptr, w.gx_sb, d.rec.tiles, main_rows / 16, pk + p.sb_whh1, w.hseq_sb1,
-                                  w.c_left, d, s, fc_fused ? &fc : nullptr,
-                                  f16x3 && fc_fused ? pk + p.sb_whh1_f16x3 : nullptr));
+        FSN_TRY(run_recurrence(l1, s));
     }
     if (!fc_fused || d.rec.left_tiles > 0) {
         StageTimer st(ST_SB_FC, s);
-        a = FsnGemmA{};
-        c = FsnGemmC{};
-        a.kind = 0;
-        a.p0 = w.hseq_sb1;
-        a.ld = d.Hs;
-        c.kind = 2;
-        c.p0 = crm_r;
-        c.p1 = crm_i;
-        c.bias = pk + p.sb_fcb;
-        c.T = d.T;
-        c.F = d.F;
-        c.FP = d.FP;
-        c.Npad = d.Npad;
-        c.N = (int)(d.row0 + d.N);  // global rows, like the A provider above
-        c.n_off = (int)d.row0;
-        c.la = d.la;
-        int rows_t = sb_rt;
-        if (fc_fused) {  // only the left-over rows: hseq_sb1 is the compact [t][left rows][H] matrix
-            c.Npad = d.rec.left_tiles * 16;
-            c.n_off = (int)(d.row0 + main_rows);
-            rows_t = d.Tp * d.rec.left_tiles;
-        }
-        FSN_TRY(fsn_launch_gemm(a, pk + p.sb_fc, c, rows_t, 1, d.Hs / 16, s));
+        // fused: only the left-over rows, hseq_sb1 is the compact [t][left rows][H] matrix
+        FSN_TRY(fc_fused ? core_sb_output(k, main_rows, d.rec.left_tiles, s) : core_sb_output(k, 0, d.Npad / 16, s));
     }
     return FSN_OK;
+}
+
+// magT [B][Tp][FP] -> crm_r, crm_i [B][T][FP]: the full-band model, then the sub-band model (model.py:121-128: N = B F
+// sequences, 2 LSTM layers + Linear(2)) in the regime of the plan `d`
+static int run_core(const fsn_fullsubnet_cfg* cfg, const float* pk, const float* magT, const CoreDims& d,
+                    const CoreWs& w, float* crm_r, float* crm_i, hipStream_t s, const int* lengths = nullptr) {
+    const CoreCall k = core_call(cfg, pk, magT, d, w, crm_r, crm_i, s, lengths);
+    FSN_TRY(core_fullband(k));
+    FSN_TRY(core_sb_divisor(k));
+    const FsnSbInput xin = sb_input_model(k.g, magT, w.fb_out, w.den_sb, k.cum ? 1 : 0, d.den_stride, pk + k.p.sb_wih0,
+                                          pk + k.p.sb_b0, k.p.sb_kin_pad / 16, d.N, d.row0);
+    const FsnRecFc fc = rec_fc(pk + k.p.sb_fc, pk + k.p.sb_fcb, crm_r, crm_i, d.N, d.row0, d.F, d.FP, d.T, d.la);
+    if (d.grp_clusters > 0) return core_sb_group(k, xin, fc);
+    if (d.rec.main_wgs == 0 && d.rec.left_tiles < kWavefrontBelowTiles) return core_sb_wavefront(k, xin);
+    return core_sb_persistent(k, xin, fc);
 }
 
 static int check_bt(int B, int T) {
@@ -768,7 +642,7 @@ static int run_core_chunks(const fsn_fullsubnet_cfg* cfg, const float* pk, const
         Carver cv(scratch);
         const CoreWs w = core_carve(cv, d, cfg->norm_type);
         FSN_TRY(run_core(cfg, pk, magT + (size_t)b0 * d.Tp * d.FP, d, w, crm_r + (size_t)b0 * d.T * d.FP,
-                         crm_i + (size_t)b0 * d.T * d.FP, s, false, lengths ? lengths + b0 : nullptr));
+                         crm_i + (size_t)b0 * d.T * d.FP, s, lengths ? lengths + b0 : nullptr));
         b0 += b;
     }
     FSN_REQUIRE(b0 == B, "internal: the chunks cover %d of %d utterances", b0, B);
@@ -874,7 +748,7 @@ extern "C" int fsn_fullsubnet_fullband(const fsn_fullsubnet_cfg* cfg, const void
     const CoreWs w = core_carve(cv, d, cfg->norm_type);
     prof_reset();
     FSN_TRY(fsn_launch_transpose(noisy_mag, magT, B, d.FP, d.Tp, T, (long)d.F * T, d.FP, (long)d.Tp * d.FP, d.F, T, s));
-    FSN_TRY(run_core(cfg, static_cast<const float*>(packed), magT, d, w, nullptr, nullptr, s, true));
+    FSN_TRY(core_fullband(core_call(cfg, static_cast<const float*>(packed), magT, d, w, nullptr, nullptr, s, nullptr)));
     // frame-major [B][T'][FP] -> [B, F, T']
     FSN_TRY(fsn_launch_transpose(w.fb_out, fb_output, B, d.Tp, d.F, d.FP, (long)d.Tp * d.FP, d.Tp, (long)d.F * d.Tp,
                                  d.Tp, d.F, s));
@@ -1009,6 +883,42 @@ extern "C" size_t fsn_fullsubnet_stream_workspace_bytes(const fsn_fullsubnet_cfg
     return fsn_round_up_sz(cv.off, 256);
 }
 
+// The model step on n rows for k frames with carried state: w.magT [n][k][FP] -> w.crm_r / w.crm_i -> crm_out [n, 2, F, k].
+// fb / sb: the (h0, h1, c0, c1) rows of the full-band / sub-band layers, updated in place; den_fb() / den_sb() launch the
+// cumulative norm's divisors (w.den_fb from w.magT; w.den_sb from w.magT and w.fb_out) from wherever the carries live.
+template <class DenFb, class DenSb>
+static int stream_sequence(const fsn_fullsubnet_cfg* cfg, const float* pk, const StreamWs& w, float* const fb[4],
+                           float* const sb[4], int n, int k, float* crm_out, const DenFb& den_fb, const DenSb& den_sb,
+                           hipStream_t s) {
+    const Packed p = packed_layout(cfg);
+    const int F = cfg->num_freqs, FP = fsn_fpad(F), Hf = cfg->fb_hidden, Hs = cfg->sb_hidden;
+    const int Npad_fb = fsn_round_up(n, 16), N = n * F, Npad = fsn_round_up(N, 16);
+    // la = 0: every model step is handed back; the caller matches step s to output frame s - look_ahead
+    const ModelGeom g{n, k, k, F, FP, cfg->sb_num_neighbors, 0};
+    FSN_TRY(den_fb());
+    const int fb_rt = k * Npad_fb / 16;
+    FSN_TRY(fsn_launch_gemm(gemm_a_fullband(g, w.magT, w.den_fb, 1, Npad_fb), pk + p.fb_wih0, gemm_c_frag(w.gx_fb, pk + p.fb_b0),
+                            fb_rt, 4 * Hf / 16, FP / 16, s));
+    FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_fb, Npad_fb / 16, 0, pk + p.fb_whh0, pk + p.fb_wih1, pk + p.fb_b1_frag,
+                                       pk + p.fb_whh1, w.hseq_fb0, w.hseq_fb1, Npad_fb, 0, fb[2], fb[3], k, Npad_fb / 16, Hf,
+                                       s, fb[0], fb[1]));
+    FSN_TRY(fsn_launch_gemm(gemm_a_rows(w.hseq_fb1, Hf), pk + p.fb_fc, gemm_c_fb_out(g, w.fb_out, pk + p.fb_fcb, Npad_fb), fb_rt,
+                            FP / 16, Hf / 16, s));
+    FSN_TRY(den_sb());
+    const FsnSbInput xin = sb_input_model(g, w.magT, w.fb_out, w.den_sb, 1, Npad, pk + p.sb_wih0, pk + p.sb_b0,
+                                          p.sb_kin_pad / 16, N, 0);
+    const int sb_rt = (int)((long)k * Npad / 16);
+    FSN_TRY(fsn_launch_gemm(gemm_a_subband(xin, 0, Npad), pk + p.sb_wih0, gemm_c_frag(w.gx_sb, pk + p.sb_b0), sb_rt,
+                            4 * Hs / 16, p.sb_kin_pad / 16, s));
+    FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_sb, Npad / 16, 0, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_b1_frag,
+                                       pk + p.sb_whh1, w.hseq_sb0, w.hseq_sb1, Npad, 0, sb[2], sb[3], k, Npad / 16, Hs, s,
+                                       sb[0], sb[1]));
+    FSN_TRY(fsn_launch_gemm(gemm_a_rows(w.hseq_sb1, Hs), pk + p.sb_fc,
+                            gemm_c_masks(g, w.crm_r, w.crm_i, pk + p.sb_fcb, Npad, 0, N), sb_rt, 1, Hs / 16, s));
+    FSN_TRY(fsn_launch_transpose(w.crm_r, crm_out, n, k, F, FP, (long)k * FP, k, 2L * F * k, k, F, s));
+    return fsn_launch_transpose(w.crm_i, crm_out + (size_t)F * k, n, k, F, FP, (long)k * FP, k, 2L * F * k, k, F, s);
+}
+
 extern "C" int fsn_fullsubnet_stream_step(const fsn_fullsubnet_cfg* cfg, const void* packed, void* state,
                                           size_t state_bytes, int steps_done, const float* mag, int B, int k,
                                           float* crm_out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1021,99 +931,27 @@ extern "C" int fsn_fullsubnet_stream_step(const fsn_fullsubnet_cfg* cfg, const v
         return FSN_ERR_WORKSPACE;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Packed p = packed_layout(cfg);
-    const float* pk = static_cast<const float*>(packed);
-    const int F = cfg->num_freqs, FP = fsn_fpad(F), Hf = cfg->fb_hidden, Hs = cfg->sb_hidden, nb = cfg->sb_num_neighbors;
-    const int Npad_fb = fsn_round_up(B, 16), N = B * F, Npad = fsn_round_up(N, 16);
+    const int F = cfg->num_freqs, FP = fsn_fpad(F), nb = cfg->sb_num_neighbors, Npad = fsn_round_up(B * F, 16);
     Carver cs(state), cw(workspace);
     const StreamState st = stream_carve(cs, cfg, B);
     const StreamWs w = stream_ws_carve(cw, cfg, B, k);
+    float* const fb[4] = {st.fb_h0, st.fb_h1, st.fb_c0, st.fb_c1};
+    float* const sb[4] = {st.sb_h0, st.sb_h1, st.sb_c0, st.sb_c1};
     // [B, 1, F, k] -> frame-major [B][k][FP]
     FSN_TRY(fsn_launch_transpose(mag, w.magT, B, FP, k, k, (long)F * k, FP, (long)k * FP, F, k, s));
-    FSN_TRY(fsn_launch_cumulative_den_fb(w.magT, w.den_fb, B, k, F, FP, s, st.fb_sum, steps_done));
-    FsnGemmA a{};
-    FsnGemmC c{};
-    a.kind = 1;
-    a.p0 = w.magT;
-    a.den = w.den_fb;
-    a.den_mode = 1;
-    a.B = B;
-    a.Tp = k;
-    a.F = F;
-    a.FP = FP;
-    a.Npad = Npad_fb;
-    c.kind = 0;
-    c.p0 = w.gx_fb;
-    c.bias = pk + p.fb_b0;
-    const int fb_rt = k * Npad_fb / 16;
-    FSN_TRY(fsn_launch_gemm(a, pk + p.fb_wih0, c, fb_rt, 4 * Hf / 16, FP / 16, s));
-    FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_fb, Npad_fb / 16, 0, pk + p.fb_whh0, pk + p.fb_wih1, pk + p.fb_b1_frag,
-                                       pk + p.fb_whh1, w.hseq_fb0, w.hseq_fb1, Npad_fb, 0, st.fb_c0, st.fb_c1, k,
-                                       Npad_fb / 16, Hf, s, st.fb_h0, st.fb_h1));
-    a = FsnGemmA{};
-    c = FsnGemmC{};
-    a.kind = 0;
-    a.p0 = w.hseq_fb1;
-    a.ld = Hf;
-    c.kind = 1;
-    c.p0 = w.fb_out;
-    c.bias = pk + p.fb_fcb;
-    c.B = B;
-    c.Tp = k;
-    c.F = F;
-    c.FP = FP;
-    c.Npad = Npad_fb;
-    FSN_TRY(fsn_launch_gemm(a, pk + p.fb_fc, c, fb_rt, FP / 16, Hf / 16, s));
-    FSN_TRY(fsn_launch_cumulative_den_sb(w.magT, w.fb_out, w.den_sb, B, k, F, FP, nb, Npad, s, st.sb_sum, steps_done));
-    a = FsnGemmA{};
-    c = FsnGemmC{};
-    a.kind = 2;
-    a.p0 = w.magT;
-    a.p1 = w.fb_out;
-    a.den = w.den_sb;
-    a.den_mode = 1;
-    a.den_stride = Npad;
-    a.B = B;
-    a.Tp = k;
-    a.F = F;
-    a.FP = FP;
-    a.Npad = Npad;
-    a.n_offset = 0;
-    a.N = N;
-    a.nb = nb;
-    c.kind = 0;
-    c.p0 = w.gx_sb;
-    c.bias = pk + p.sb_b0;
-    const int sb_rt = (int)((long)k * Npad / 16);
-    FSN_TRY(fsn_launch_gemm(a, pk + p.sb_wih0, c, sb_rt, 4 * Hs / 16, p.sb_kin_pad / 16, s));
-    FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_sb, Npad / 16, 0, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_b1_frag,
-                                       pk + p.sb_whh1, w.hseq_sb0, w.hseq_sb1, Npad, 0, st.sb_c0, st.sb_c1, k, Npad / 16,
-                                       Hs, s, st.sb_h0, st.sb_h1));
-    a = FsnGemmA{};
-    c = FsnGemmC{};
-    a.kind = 0;
-    a.p0 = w.hseq_sb1;
-    a.ld = Hs;
-    c.kind = 2;
-    c.p0 = w.crm_r;
-    c.p1 = w.crm_i;
-    c.bias = pk + p.sb_fcb;
-    c.T = k;
-    c.F = F;
-    c.FP = FP;
-    c.Npad = Npad;
-    c.N = N;
-    c.la = 0;  // every model step is handed back; the caller matches step s to output frame s - look_ahead
-    FSN_TRY(fsn_launch_gemm(a, pk + p.sb_fc, c, sb_rt, 1, Hs / 16, s));
-    FSN_TRY(fsn_launch_transpose(w.crm_r, crm_out, B, k, F, FP, (long)k * FP, k, 2L * F * k, k, F, s));
-    FSN_TRY(fsn_launch_transpose(w.crm_i, crm_out + (size_t)F * k, B, k, F, FP, (long)k * FP, k, 2L * F * k, k, F, s));
-    return FSN_OK;
+    return stream_sequence(
+        cfg, static_cast<const float*>(packed), w, fb, sb, B, k, crm_out,
+        [&] { return fsn_launch_cumulative_den_fb(w.magT, w.den_fb, B, k, F, FP, s, st.fb_sum, steps_done); },
+        [&] {
+            return fsn_launch_cumulative_den_sb(w.magT, w.fb_out, w.den_sb, B, k, F, FP, nb, Npad, s, st.sb_sum, steps_done);
+        },
+        s);
 }
 
 // ---- streaming pool: the same step over a subset of the slots of a pool --------------------------------------------
 // State: one record per slot (FsnPoolLayout, fsn_common.h).  A step gathers the listed slots' (h, c) rows into compact
-// tiles in the workspace, runs the sequence of fsn_fullsubnet_stream_step on them with per-slot norm carries and step
-// counts, and scatters the rows back (stream_pool_kernels.hip).
+// tiles in the workspace, runs stream_sequence on them with per-slot norm carries and step counts, and scatters the rows
+// back (stream_pool_kernels.hip).
 static FsnPoolLayout pool_layout(const fsn_fullsubnet_cfg* cfg) {
     return fsn_pool_layout(cfg->num_freqs, cfg->fb_hidden, cfg->sb_hidden, cfg->look_ahead);
 }
@@ -1177,11 +1015,9 @@ extern "C" int fsn_fullsubnet_stream_pool_step(const fsn_fullsubnet_cfg* cfg, co
         return FSN_ERR_WORKSPACE;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Packed p = packed_layout(cfg);
     const FsnPoolLayout L = pool_layout(cfg);
-    const float* pk = static_cast<const float*>(packed);
-    const int F = cfg->num_freqs, FP = fsn_fpad(F), Hf = cfg->fb_hidden, Hs = cfg->sb_hidden, nb = cfg->sb_num_neighbors;
-    const int Npad_fb = fsn_round_up(n, 16), N = n * F, Npad = fsn_round_up(N, 16);
+    const int F = cfg->num_freqs, FP = fsn_fpad(F), nb = cfg->sb_num_neighbors;
+    const int Npad_fb = fsn_round_up(n, 16), Npad = fsn_round_up(n * F, 16);
     Carver cw(workspace);
     const StreamWs w = stream_ws_carve(cw, cfg, n, k);
     const PoolTilesWs t = pool_tiles_carve(cw, cfg, n);
@@ -1189,83 +1025,10 @@ extern "C" int fsn_fullsubnet_stream_pool_step(const fsn_fullsubnet_cfg* cfg, co
     FSN_TRY(fsn_launch_transpose(mag, w.magT, n, FP, k, k, (long)F * k, FP, (long)k * FP, F, k, s));
     FSN_TRY(fsn_launch_pool_gather(state, L, capacity, slots, n, 0, t.fb[0], t.fb[1], t.fb[2], t.fb[3], Npad_fb, s));
     FSN_TRY(fsn_launch_pool_gather(state, L, capacity, slots, n, 1, t.sb[0], t.sb[1], t.sb[2], t.sb[3], Npad, s));
-    FSN_TRY(fsn_launch_pool_den_fb(w.magT, w.den_fb, state, L, capacity, slots, n, k, s));
-    FsnGemmA a{};
-    FsnGemmC c{};
-    a.kind = 1;
-    a.p0 = w.magT;
-    a.den = w.den_fb;
-    a.den_mode = 1;
-    a.B = n;
-    a.Tp = k;
-    a.F = F;
-    a.FP = FP;
-    a.Npad = Npad_fb;
-    c.kind = 0;
-    c.p0 = w.gx_fb;
-    c.bias = pk + p.fb_b0;
-    const int fb_rt = k * Npad_fb / 16;
-    FSN_TRY(fsn_launch_gemm(a, pk + p.fb_wih0, c, fb_rt, 4 * Hf / 16, FP / 16, s));
-    FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_fb, Npad_fb / 16, 0, pk + p.fb_whh0, pk + p.fb_wih1, pk + p.fb_b1_frag,
-                                       pk + p.fb_whh1, w.hseq_fb0, w.hseq_fb1, Npad_fb, 0, t.fb[2], t.fb[3], k,
-                                       Npad_fb / 16, Hf, s, t.fb[0], t.fb[1]));
-    a = FsnGemmA{};
-    c = FsnGemmC{};
-    a.kind = 0;
-    a.p0 = w.hseq_fb1;
-    a.ld = Hf;
-    c.kind = 1;
-    c.p0 = w.fb_out;
-    c.bias = pk + p.fb_fcb;
-    c.B = n;
-    c.Tp = k;
-    c.F = F;
-    c.FP = FP;
-    c.Npad = Npad_fb;
-    FSN_TRY(fsn_launch_gemm(a, pk + p.fb_fc, c, fb_rt, FP / 16, Hf / 16, s));
-    FSN_TRY(fsn_launch_pool_den_sb(w.magT, w.fb_out, w.den_sb, state, L, capacity, slots, n, k, nb, Npad, s));
-    a = FsnGemmA{};
-    c = FsnGemmC{};
-    a.kind = 2;
-    a.p0 = w.magT;
-    a.p1 = w.fb_out;
-    a.den = w.den_sb;
-    a.den_mode = 1;
-    a.den_stride = Npad;
-    a.B = n;
-    a.Tp = k;
-    a.F = F;
-    a.FP = FP;
-    a.Npad = Npad;
-    a.n_offset = 0;
-    a.N = N;
-    a.nb = nb;
-    c.kind = 0;
-    c.p0 = w.gx_sb;
-    c.bias = pk + p.sb_b0;
-    const int sb_rt = (int)((long)k * Npad / 16);
-    FSN_TRY(fsn_launch_gemm(a, pk + p.sb_wih0, c, sb_rt, 4 * Hs / 16, p.sb_kin_pad / 16, s));
-    FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_sb, Npad / 16, 0, pk + p.sb_whh0, pk + p.sb_wih1, pk + p.sb_b1_frag,
-                                       pk + p.sb_whh1, w.hseq_sb0, w.hseq_sb1, Npad, 0, t.sb[2], t.sb[3], k, Npad / 16, Hs,
-                                       s, t.sb[0], t.sb[1]));
-    a = FsnGemmA{};
-    c = FsnGemmC{};
-    a.kind = 0;
-    a.p0 = w.hseq_sb1;
-    a.ld = Hs;
-    c.kind = 2;
-    c.p0 = w.crm_r;
-    c.p1 = w.crm_i;
-    c.bias = pk + p.sb_fcb;
-    c.T = k;
-    c.F = F;
-    c.FP = FP;
-    c.Npad = Npad;
-    c.N = N;
-    c.la = 0;  // every model step is handed back, as in fsn_fullsubnet_stream_step
-    FSN_TRY(fsn_launch_gemm(a, pk + p.sb_fc, c, sb_rt, 1, Hs / 16, s));
-    FSN_TRY(fsn_launch_transpose(w.crm_r, crm_out, n, k, F, FP, (long)k * FP, k, 2L * F * k, k, F, s));
-    FSN_TRY(fsn_launch_transpose(w.crm_i, crm_out + (size_t)F * k, n, k, F, FP, (long)k * FP, k, 2L * F * k, k, F, s));
+    FSN_TRY(stream_sequence(
+        cfg, static_cast<const float*>(packed), w, t.fb, t.sb, n, k, crm_out,
+        [&] { return fsn_launch_pool_den_fb(w.magT, w.den_fb, state, L, capacity, slots, n, k, s); },
+        [&] { return fsn_launch_pool_den_sb(w.magT, w.fb_out, w.den_sb, state, L, capacity, slots, n, k, nb, Npad, s); }, s));
     FSN_TRY(fsn_launch_pool_scatter(state, L, capacity, slots, n, 0, t.fb[0], t.fb[1], t.fb[2], t.fb[3], Npad_fb, k, s));
     // last: it advances the listed slots' step counts
     return fsn_launch_pool_scatter(state, L, capacity, slots, n, 1, t.sb[0], t.sb[1], t.sb[2], t.sb[3], Npad, k, s);

@@ -49,15 +49,7 @@ extern "C" int fsn_gru2_forward(const float* x, long ldx, const float* w_ih0, co
     FSN_TRY(fsn_launch_pack(whh0_4, whh0_p, G, H, G, H, s));
     FSN_TRY(fsn_launch_pack(wih1_4, wih1_p, G, H, G, H, s));
     FSN_TRY(fsn_launch_pack(whh1_4, whh1_p, G, H, G, H, s));
-    FsnGemmA a{};
-    a.kind = 0;
-    a.p0 = x;
-    a.ld = ldx;
-    FsnGemmC c{};
-    c.kind = 0;
-    c.p0 = gx;
-    c.bias = b0;
-    FSN_TRY(fsn_launch_gemm(a, wih0_p, c, T * (N / 16), G / 16, Ipad / 16, s));
+    FSN_TRY(fsn_launch_gemm(gemm_a_rows(x, ldx), wih0_p, gemm_c_frag(gx, b0), T * (N / 16), G / 16, Ipad / 16, s));
     FSN_PERSIST_BEGIN(s);
     FSN_TRY(fsn_launch_fb_chain(gx, whh0_p, wih1_p, whh1_p, b1, exchange, flags, hseq1, T, N, H, s, nullptr, nullptr, nullptr, 1));
     return fsn_launch_poison_if(flags + fsn_fb_chain_status_word(), hseq1, (size_t)T * N * H, s);
@@ -149,15 +141,7 @@ static int gru_layer_steps_prepare(const float* x, long ldx, const float* w_ih, 
     // bias of the projection: b_ih everywhere + b_hh for r and z (b_hn stays inside r * (W_hn h + b_hn))
     FSN_TRY(fsn_launch_bias_sum(b_ih, nullptr, bias, G, G, s));
     FSN_TRY(fsn_launch_bias_sum(b_ih, b_hh, bias, 2 * H, 2 * H, s));
-    FsnGemmA a{};
-    a.kind = 0;
-    a.p0 = x;
-    a.ld = ldx;
-    FsnGemmC c{};
-    c.kind = 0;
-    c.p0 = gx;
-    c.bias = bias;
-    FSN_TRY(fsn_launch_gemm(a, wih_p, c, T * (N / 16), G / 16, Ipad / 16, s));
+    FSN_TRY(fsn_launch_gemm(gemm_a_rows(x, ldx), wih_p, gemm_c_frag(gx, bias), T * (N / 16), G / 16, Ipad / 16, s));
     out->whh_p = whh_p;
     out->gx = gx;
     return FSN_OK;
@@ -196,45 +180,18 @@ static int gru_layer_forward_persistent(const GruPlan& p, const float* x, long l
     FSN_TRY(fsn_launch_pack(wih4, wih4_p, G4, I, G4, Ipad, s));
     FSN_TRY(fsn_launch_pack(whh4, whh4_p, G4, H, G4, H, s));
     hipStream_t ls = s;
-    StreamCtx* cx = nullptr;
     GruStepBufs sb{};
     if (left > 0) {
         // rows [main_rows, N) of every step as compact [T][left] matrices (columns [0, Ipad) of a row; one 2-D copy when the
         // rows are exactly that wide, one per step otherwise) and their input projection - on `s`, AHEAD of the persistent
         // launch: the projection GEMM's workgroups (160 registers, 96 KB of LDS) do not fit beside a resident workgroup of it
         // and would wait for the whole launch (measured: the step launches then ran after it, +2.7 ms per batch of 64)
-        bool ok = true;
-        if (ldx == Ipad)
-            ok = hipMemcpy2DAsync(x_left, (size_t)left * Ipad * sizeof(float), x + (size_t)main_rows * ldx,
-                                  (size_t)N * ldx * sizeof(float), (size_t)left * Ipad * sizeof(float), (size_t)T,
-                                  hipMemcpyDeviceToDevice, s) == hipSuccess;
-        else
-            for (int t = 0; t < T && ok; ++t)
-                ok = hipMemcpy2DAsync(x_left + (size_t)t * left * Ipad, (size_t)Ipad * sizeof(float),
-                                      x + ((size_t)t * N + main_rows) * ldx, (size_t)ldx * sizeof(float),
-                                      (size_t)Ipad * sizeof(float), (size_t)left, hipMemcpyDeviceToDevice, s) == hipSuccess;
-        if (!ok) {
-            fsn_set_error("gru layer forward: copy of the left-over rows failed");
-            return FSN_ERR_LAUNCH;
-        }
+        FSN_TRY(gather_step_rows(x_left, x, ldx, T, N, main_rows, left, Ipad, s));
         FSN_TRY(gru_layer_steps_prepare(x_left, Ipad, w_ih, w_hh, b_ih, b_hh, T, left, I, H, step_ws, s, &sb));
-        cx = cur_ctx();
-        FSN_TRY(aux_init(cx));
-        if (hipEventRecord(cx->ev_fork, s) != hipSuccess || hipStreamWaitEvent(cx->aux, cx->ev_fork, 0) != hipSuccess) {
-            fsn_set_error("aux stream fork failed");
-            return FSN_ERR_LAUNCH;
-        }
-        ls = cx->aux;
+        FSN_TRY(aux_fork(s, &ls));
     }
     if (Ipad <= 32) {
-        FsnSbInput xin{};
-        xin.x_rows = x;
-        xin.x_ld = ldx;
-        xin.x_step = N;
-        xin.N = main_rows;
-        xin.kin_chunks = Ipad / 16;
-        xin.wih_p = wih4_p;
-        xin.bias = b4;
+        const FsnSbInput xin = sb_input_rows(x, ldx, N, main_rows, Ipad / 16, wih4_p, b4);
         FSN_TRY(fsn_launch_lstm_rec_in(&xin, whh4_p, hseq, T, N, H, p.rt, p.main_wgs, s, 1));
     } else {
         FSN_TRY(fsn_launch_lstm_rec_x(x, wih4_p, whh4_p, b4, T, N, H, p.rt, p.main_wgs, s, nullptr, hseq, 1));
@@ -242,15 +199,8 @@ static int gru_layer_forward_persistent(const GruPlan& p, const float* x, long l
     if (left > 0) {
         // the left-over rows' T step launches beside the persistent launch, then back into rows [main_rows, N) of hseq
         FSN_TRY(gru_layer_steps_run(sb, b_hh, T, left, H, h_left, nullptr, ls, 1));
-        if (hipMemcpy2DAsync(hseq + (size_t)main_rows * H, (size_t)N * H * sizeof(float), h_left, (size_t)left * H * sizeof(float),
-                             (size_t)left * H * sizeof(float), (size_t)T, hipMemcpyDeviceToDevice, ls) != hipSuccess) {
-            fsn_set_error("gru layer forward: copy of the left-over rows failed");
-            return FSN_ERR_LAUNCH;
-        }
-        if (hipEventRecord(cx->ev_join, cx->aux) != hipSuccess || hipStreamWaitEvent(s, cx->ev_join, 0) != hipSuccess) {
-            fsn_set_error("aux stream join failed");
-            return FSN_ERR_LAUNCH;
-        }
+        FSN_TRY(scatter_step_rows(hseq, H, h_left, T, N, main_rows, left, H, ls));
+        FSN_TRY(aux_join(s));
     }
     return FSN_OK;
 }
@@ -297,15 +247,7 @@ extern "C" int fsn_gru_layer_forward_state(const float* x, long ldx, const float
     FSN_TRY(fsn_launch_pack(w_hh, whh_p, G, H, G, H, s));
     FSN_TRY(fsn_launch_bias_sum(b_ih, nullptr, bias, G, G, s));
     FSN_TRY(fsn_launch_bias_sum(b_ih, b_hh, bias, 2 * H, 2 * H, s));
-    FsnGemmA a{};
-    a.kind = 0;
-    a.p0 = x;
-    a.ld = ldx;
-    FsnGemmC c{};
-    c.kind = 0;
-    c.p0 = gx;
-    c.bias = bias;
-    FSN_TRY(fsn_launch_gemm(a, wih_p, c, T * (N / 16), G / 16, Ipad / 16, s));
+    FSN_TRY(fsn_launch_gemm(gemm_a_rows(x, ldx), wih_p, gemm_c_frag(gx, bias), T * (N / 16), G / 16, Ipad / 16, s));
     const size_t step = (size_t)N * H;
     for (int t = 0; t < T; ++t)
         FSN_TRY(fsn_launch_gru_step(gx, whh_p, b_hh + 2 * H, t ? hseq + (t - 1) * step : h_state, hseq + t * step, nullptr,
@@ -374,17 +316,7 @@ extern "C" int fsn_gru_layer_backward(const float* dh, const float* x, long ldx,
                                          dgx + (size_t)t * N * G, dghn + t * step, N / 16, H, t == T - 1, t == 0, s));
     }
     if (dx) {
-        FsnGemmA a{};
-        a.kind = 0;
-        a.p0 = dgx;
-        a.ld = G;
-        FsnGemmC c{};
-        c.kind = 3;
-        c.p0 = dx;
-        c.ld = lddx;
-        c.rows = T * N;
-        c.cols = I;
-        FSN_TRY(fsn_launch_gemm(a, wihT_p, c, T * (N / 16), Ipad / 16, G / 16, s));
+        FSN_TRY(fsn_launch_gemm(gemm_a_rows(dgx, G), wihT_p, gemm_c_rows(dx, lddx, T * N, I), T * (N / 16), Ipad / 16, G / 16, s));
     }
     FSN_TRY(fsn_launch_gemm_tn(dgx, G, x, ldx, dw_ih, I, G, I, (long)T * N, scratch, s));
     if (T > 1) {

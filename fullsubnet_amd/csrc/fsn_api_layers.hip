@@ -12,6 +12,32 @@ int check_lstm_layer(int T, int N, int I, int H, long ldx) {
     return FSN_OK;
 }
 
+// `rows` rows x K columns of each of T steps between two [T][step rows][ld] matrices: one 2-D copy when both sides' rows are
+// exactly K wide, one per step otherwise
+static int copy_step_rows(float* dst, size_t dst_step, size_t dst_ld, const float* src, size_t src_step, size_t src_ld, int T,
+                          int rows, size_t K, hipStream_t s) {
+    bool ok = true;
+    if (dst_ld == K && src_ld == K)
+        ok = hipMemcpy2DAsync(dst, dst_step * K * sizeof(float), src, src_step * K * sizeof(float), rows * K * sizeof(float),
+                              (size_t)T, hipMemcpyDeviceToDevice, s) == hipSuccess;
+    else
+        for (int t = 0; t < T && ok; ++t)
+            ok = hipMemcpy2DAsync(dst + t * dst_step * dst_ld, dst_ld * sizeof(float), src + t * src_step * src_ld,
+                                  src_ld * sizeof(float), K * sizeof(float), (size_t)rows, hipMemcpyDeviceToDevice,
+                                  s) == hipSuccess;
+    if (!ok) {
+        fsn_set_error("copy of the left-over rows failed");
+        return FSN_ERR_LAUNCH;
+    }
+    return FSN_OK;
+}
+int gather_step_rows(float* dst, const float* src, long ld, int T, int N, int row0, int left, int K, hipStream_t s) {
+    return copy_step_rows(dst, left, K, src + (size_t)row0 * ld, N, ld, T, left, K, s);
+}
+int scatter_step_rows(float* dst, long ld, const float* src, int T, int N, int row0, int left, int K, hipStream_t s) {
+    return copy_step_rows(dst + (size_t)row0 * ld, N, ld, src, left, K, T, left, K, s);
+}
+
 extern "C" size_t fsn_lstm_layer_save_bytes(int T, int N, int H) {
     return fsn_round_up_sz(((size_t)T * N * 4 * H + (size_t)T * N * H) * sizeof(float), 256);
 }
@@ -126,16 +152,18 @@ extern "C" int fsn_lstm_layer_forward(const float* x, long ldx, const float* w_i
         FsnRecPlan plan = layer_plan(N, H);
         if (plan.main_wgs > 0 && (plan.rt > 4 || plan.left_tiles > 16) && (Ipad <= 32 || (I == H && ldx == H)))
             plan = layer_plan_rounds(N, H);  // more than one round's worth of rows (the two forms below take any grid)
+        RecArgs rec;  // what the forms below share
+        rec.whh = whh_p;
+        rec.hseq = hseq;
+        rec.Tp = T;
+        rec.Npad = N;
+        rec.H = H;
+        rec.plan = plan;
         if (plan.main_wgs > 0 && plan.left_tiles == 0 && Ipad <= 32) {
-            FsnSbInput xin{};
-            xin.x_rows = x;
-            xin.x_ld = ldx;
-            xin.x_step = N;
-            xin.N = N;
-            xin.kin_chunks = Ipad / 16;
-            xin.wih_p = wih_p;
-            xin.bias = bias;
-            return run_recurrence(nullptr, &xin, nullptr, 0, 0, whh_p, hseq, c_state, T, N, H, plan, s);
+            const FsnSbInput xin = sb_input_rows(x, ldx, N, N, Ipad / 16, wih_p, bias);
+            rec.xin = &xin;
+            rec.c_left = c_state;
+            return run_recurrence(rec, s);
         }
         // The same two forms with LEFT-OVER row tiles (whole rounds of 2 - 4 tiles per workgroup + a few tiles more: 64 x 257
         // rows are 256 x 4 tiles + 4): the persistent kernel takes the whole rounds, the left-over rows advance step by step
@@ -149,43 +177,21 @@ extern "C" int fsn_lstm_layer_forward(const float* x, long ldx, const float* w_i
             const int left = plan.left_tiles * 16, main_rows = N - left;
             float* gx_left = gx;                                  // [T][left / 16 tiles] fragment order
             float* x_left = gx + (size_t)T * left * 4 * H;        // [T][left][Ipad]
-            bool ok = true;
-            if (ldx == Ipad)
-                ok = hipMemcpy2DAsync(x_left, (size_t)left * Ipad * sizeof(float), x + (size_t)main_rows * ldx,
-                                      (size_t)N * ldx * sizeof(float), (size_t)left * Ipad * sizeof(float), (size_t)T,
-                                      hipMemcpyDeviceToDevice, s) == hipSuccess;
-            else
-                for (int t = 0; t < T && ok; ++t)
-                    ok = hipMemcpy2DAsync(x_left + (size_t)t * left * Ipad, (size_t)Ipad * sizeof(float),
-                                          x + ((size_t)t * N + main_rows) * ldx, (size_t)ldx * sizeof(float),
-                                          (size_t)Ipad * sizeof(float), (size_t)left, hipMemcpyDeviceToDevice, s) == hipSuccess;
-            if (!ok) {
-                fsn_set_error("lstm layer forward: copy of the left-over rows failed");
-                return FSN_ERR_LAUNCH;
-            }
-            FsnGemmA al{};
-            al.kind = 0;
-            al.p0 = x_left;
-            al.ld = Ipad;
-            FsnGemmC cl{};
-            cl.kind = 0;
-            cl.p0 = gx_left;
-            cl.bias = bias;
-            FSN_TRY(fsn_launch_gemm(al, wih_p, cl, T * (left / 16), 4 * H / 16, Ipad / 16, s));
-            float* c_left = c_state + (size_t)main_rows * H;
+            FSN_TRY(gather_step_rows(x_left, x, ldx, T, N, main_rows, left, Ipad, s));
+            FSN_TRY(fsn_launch_gemm(gemm_a_rows(x_left, Ipad), wih_p, gemm_c_frag(gx_left, bias), T * (left / 16), 4 * H / 16,
+                                    Ipad / 16, s));
+            rec.gx_left = gx_left;
+            rec.left_stride = left / 16;
+            rec.c_left = c_state + (size_t)main_rows * H;
             if (narrow) {
-                FsnSbInput xin{};
-                xin.x_rows = x;
-                xin.x_ld = ldx;
-                xin.x_step = N;
-                xin.N = main_rows;
-                xin.kin_chunks = Ipad / 16;
-                xin.wih_p = wih_p;
-                xin.bias = bias;
-                return run_recurrence(nullptr, &xin, gx_left, left / 16, 0, whh_p, hseq, c_left, T, N, H, plan, s);
+                const FsnSbInput xin = sb_input_rows(x, ldx, N, main_rows, Ipad / 16, wih_p, bias);
+                rec.xin = &xin;
+                return run_recurrence(rec, s);
             }
-            return run_recurrence(nullptr, nullptr, gx_left, left / 16, 0, whh_p, hseq, c_left, T, N, H, plan, s, nullptr, -1, nullptr,
-                                  nullptr, x, wih_p, bias);
+            rec.x_main = x;
+            rec.wih_main = wih_p;
+            rec.bias_main = bias;
+            return run_recurrence(rec, s);
         }
         // a layer of a stack on the persistent kernel (input = the hidden sequence of an equally wide layer below, e.g.
         // the second bottleneck layer of Fast FullSubNet, fast_fullsubnet/model.py:66-74): the K = H projection is
@@ -195,20 +201,23 @@ extern "C" int fsn_lstm_layer_forward(const float* x, long ldx, const float* w_i
             whh_p > wih_p)
             return fsn_launch_lstm_rec_x(x, wih_p, whh_p, bias, T, N, H, plan.rt, plan.main_wgs, s, nullptr, hseq);
     }
-    FsnGemmA a{};
-    a.kind = 0;
-    a.p0 = x;
-    a.ld = ldx;
-    FsnGemmC c{};
-    c.kind = 0;
-    c.p0 = gx;
-    c.bias = bias;
-    FSN_TRY(fsn_launch_gemm(a, wih_p, c, T * (N / 16), 4 * H / 16, Ipad / 16, s));
+    FSN_TRY(fsn_launch_gemm(gemm_a_rows(x, ldx), wih_p, gemm_c_frag(gx, bias), T * (N / 16), 4 * H / 16, Ipad / 16, s));
     if (!save) {  // inference: nothing kept but the hidden sequence
         const FsnRecPlan plan = layer_plan(N, H);
         const long main_tiles = (long)plan.main_wgs * plan.rt;
-        return run_recurrence(gx, nullptr, gx, plan.tiles, main_tiles, whh_p, hseq, c_state + main_tiles * 16 * H, T, N,
-                              H, plan, s);
+        RecArgs rec;
+        rec.gx = gx;
+        rec.gx_left = gx;
+        rec.left_stride = plan.tiles;
+        rec.left_off = main_tiles;
+        rec.whh = whh_p;
+        rec.hseq = hseq;
+        rec.c_left = c_state + main_tiles * 16 * H;
+        rec.Tp = T;
+        rec.Npad = N;
+        rec.H = H;
+        rec.plan = plan;
+        return run_recurrence(rec, s);
     }
     const size_t step = (size_t)N * H;
     for (int t = 0; t < T; ++t)
@@ -273,19 +282,9 @@ extern "C" int fsn_lstm_layer_forward_fc(const float* x, long ldx, const float* 
     FSN_TRY(fsn_launch_bias_sum(b_ih, b_hh, bias, 4 * H, 4 * H, s));
     FSN_TRY(fsn_launch_pack(fc_w, fcw_p, O, H, 16, H, s));
     FSN_TRY(fsn_launch_bias_sum(fc_b, nullptr, fcb_p, O, 16, s));
-    FsnRecFc fc{};
-    fc.w_p = fcw_p;
-    fc.bias = fcb_p;
-    fc.crm_r = out0;
-    fc.crm_i = O > 1 ? out1 : spare;
     // the kernel's destination of row n at step t is plane[((n / F) T + t) FP + n % F]: one group of F = N rows, FP = ldo
     // -> plane[t ldo + n], time-major
-    fc.N = N;
-    fc.F = N;
-    fc.FP = (int)ldo;
-    fc.T = T;
-    fc.la = 0;
-    fc.row0 = 0;
+    const FsnRecFc fc = rec_fc(fcw_p, fcb_p, out0, O > 1 ? out1 : spare, N, 0, N, (int)ldo, T, 0);
     return fsn_launch_lstm_rec_x(x, wih_p, whh_p, bias, T, N, H, plan.rt, plan.main_wgs, s, &fc, nullptr);
 }
 
@@ -392,15 +391,7 @@ extern "C" int fsn_lstm2_forward(const float* x, long ldx, const float* w_ih0, c
     FSN_TRY(fsn_launch_bias_sum(b_ih0, b_hh0, b0, G0, G0, s));
     FSN_TRY(fsn_launch_bias_sum(b_ih1, b_hh1, b1, G1, G1, s));
     FSN_TRY(fsn_launch_bias_frag(b1, b1_frag, G1, s));
-    FsnGemmA a{};
-    a.kind = 0;
-    a.p0 = x;
-    a.ld = ldx;
-    FsnGemmC c{};
-    c.kind = 0;
-    c.p0 = gx;
-    c.bias = b0;
-    FSN_TRY(fsn_launch_gemm(a, wih0_p, c, T * (N / 16), G0 / 16, Ipad / 16, s));
+    FSN_TRY(fsn_launch_gemm(gemm_a_rows(x, ldx), wih0_p, gemm_c_frag(gx, b0), T * (N / 16), G0 / 16, Ipad / 16, s));
     if (H0 == H1 && lstm2_on_chain(T, N, H0)) {  // H = 384 / 512, up to 64 rows: one persistent launch (fb_chain_kernels.hip)
         float* exchange = cv.take<float>(fsn_fb_chain_exchange_floats(T, N));
         unsigned* flags = cv.take<unsigned>(fsn_fb_chain_flag_words());
@@ -573,15 +564,7 @@ extern "C" int fsn_lstm2_forward_multi(int n, const fsn_lstm2_stack* stacks, int
         FSN_TRY(fsn_launch_pack(q.w_hh1, p.whh1, G, H, G, H, s));
         FSN_TRY(fsn_launch_bias_sum(q.b_ih0, q.b_hh0, p.b0, G, G, s));
         FSN_TRY(fsn_launch_bias_sum(q.b_ih1, q.b_hh1, p.b1, G, G, s));
-        FsnGemmA a{};
-        a.kind = 0;
-        a.p0 = q.x;
-        a.ld = q.ldx;
-        FsnGemmC c{};
-        c.kind = 0;
-        c.p0 = p.gx;
-        c.bias = p.b0;
-        FSN_TRY(fsn_launch_gemm(a, p.wih0, c, T * (q.N / 16), G / 16, Ipad / 16, s));
+        FSN_TRY(fsn_launch_gemm(gemm_a_rows(q.x, q.ldx), p.wih0, gemm_c_frag(p.gx, p.b0), T * (q.N / 16), G / 16, Ipad / 16, s));
         FsnGroupStack& g = gs[k];
         g.gx = p.gx;
         g.whh0_p = p.whh0;
@@ -637,15 +620,8 @@ extern "C" int fsn_lstm_layer_forward_state(const float* x, long ldx, const void
     const LayerPacked p = layer_packed_layout(I, H);
     const float* pk = static_cast<const float*>(packed);
     float* gx = static_cast<float*>(workspace);
-    FsnGemmA a{};
-    a.kind = 0;
-    a.p0 = x;
-    a.ld = ldx;
-    FsnGemmC c{};
-    c.kind = 0;
-    c.p0 = gx;
-    c.bias = pk + p.bias;
-    FSN_TRY(fsn_launch_gemm(a, pk + p.wih, c, T * (N / 16), 4 * H / 16, fsn_round_up(I, 16) / 16, s));
+    FSN_TRY(fsn_launch_gemm(gemm_a_rows(x, ldx), pk + p.wih, gemm_c_frag(gx, pk + p.bias), T * (N / 16), 4 * H / 16,
+                            fsn_round_up(I, 16) / 16, s));
     const size_t step = (size_t)N * H;
     for (int t = 0; t < T; ++t)
         FSN_TRY(fsn_launch_lstm_step(gx, pk + p.whh, t ? hseq + (t - 1) * step : h_state, hseq + t * step, c_state,

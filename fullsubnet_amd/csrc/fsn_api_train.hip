@@ -141,14 +141,8 @@ extern "C" int fsn_lstm2_forward_train(const float* x, long ldx, const float* w_
         if (w16 && !g16) FSN_TRY(fsn_launch_to16(wih0_p, w16, wfloats, arith, s));  // the group kernel's weight fragments in 16 bits
         float* sv0 = static_cast<float*>(save0);
         float* sv1 = static_cast<float*>(save1);
-        StreamCtx* cx = cur_ctx();
-        if (left > 0) {
-            FSN_TRY(aux_init(cx));
-            if (hipEventRecord(cx->ev_fork, s) != hipSuccess || hipStreamWaitEvent(cx->aux, cx->ev_fork, 0) != hipSuccess) {
-                fsn_set_error("aux stream fork failed");
-                return FSN_ERR_LAUNCH;
-            }
-        }
+        hipStream_t as = s;
+        if (left > 0) FSN_TRY(aux_fork(s, &as));
         {
             FSN_PERSIST_BEGIN(s);
             if (g16) {  // the 16-bit arithmetic's own kernels: they pack the raw weights their way into w16
@@ -162,27 +156,14 @@ extern "C" int fsn_lstm2_forward_train(const float* x, long ldx, const float* w_
             }
         }
         if (left > 0) {
-            hipStream_t as = cx->aux;
             const size_t stepH = (size_t)N * H, stepG = (size_t)N * 4 * H;
             for (int layer = 0; layer < 2; ++layer) {
                 // the left-over rows of this layer's input as a compact [T][left][K] matrix -> projection tiles
-                const float* src = layer ? hseq0 + (size_t)row0 * H : x + (size_t)row0 * ldx;
-                const size_t src_ld = layer ? (size_t)H : (size_t)ldx, K = layer ? (size_t)H : (size_t)Ipad;
+                const int K = layer ? H : Ipad;
                 float* dst = layer ? h0_left : x_left;
-                if (hipMemcpy2DAsync(dst, left * K * sizeof(float), src, (size_t)N * src_ld * sizeof(float),
-                                     left * src_ld * sizeof(float), T, hipMemcpyDeviceToDevice, as) != hipSuccess) {
-                    fsn_set_error("lstm2 forward (training): cannot gather the left-over rows");
-                    return FSN_ERR_LAUNCH;
-                }
-                FsnGemmA a{};
-                a.kind = 0;
-                a.p0 = dst;
-                a.ld = (long)K;
-                FsnGemmC c{};
-                c.kind = 0;
-                c.p0 = gx_left;
-                c.bias = layer ? b1 : b0;
-                FSN_TRY(fsn_launch_gemm(a, layer ? wih1_p : wih0_p, c, T * left_tiles, 4 * H / 16, (int)K / 16, as));
+                FSN_TRY(gather_step_rows(dst, layer ? hseq0 : x, layer ? H : ldx, T, N, row0, left, K, as));
+                FSN_TRY(fsn_launch_gemm(gemm_a_rows(dst, K), layer ? wih1_p : wih0_p, gemm_c_frag(gx_left, layer ? b1 : b0),
+                                        T * left_tiles, 4 * H / 16, K / 16, as));
                 float* hs = (layer ? hseq1 : hseq0) + (size_t)row0 * H;
                 float* sv = layer ? sv1 : sv0;
                 float* gates = sv + (size_t)row0 * 4 * H;
@@ -192,10 +173,7 @@ extern "C" int fsn_lstm2_forward_train(const float* x, long ldx, const float* w_
                                                        hs + t * stepH, t ? cseq + (t - 1) * stepH : cseq, cseq + t * stepH,
                                                        gates + t * stepG, (long)t * left_tiles, left_tiles, H, t == 0, as));
             }
-            if (hipEventRecord(cx->ev_join, cx->aux) != hipSuccess || hipStreamWaitEvent(s, cx->ev_join, 0) != hipSuccess) {
-                fsn_set_error("aux stream join failed");
-                return FSN_ERR_LAUNCH;
-            }
+            FSN_TRY(aux_join(s));
         }
         return FSN_OK;
     }
@@ -222,15 +200,7 @@ extern "C" int fsn_lstm2_forward_train(const float* x, long ldx, const float* w_
     FSN_TRY(fsn_launch_pack(w_hh1, whh1_p, 4 * H, H, 4 * H, H, s));
     FSN_TRY(fsn_launch_bias_sum(b_ih0, b_hh0, b0, 4 * H, 4 * H, s));
     FSN_TRY(fsn_launch_bias_sum(b_ih1, b_hh1, b1, 4 * H, 4 * H, s));
-    FsnGemmA a{};
-    a.kind = 0;
-    a.p0 = x;
-    a.ld = ldx;
-    FsnGemmC c{};
-    c.kind = 0;
-    c.p0 = gx0;
-    c.bias = b0;
-    FSN_TRY(fsn_launch_gemm(a, wih0_p, c, T * (N / 16), 4 * H / 16, Ipad / 16, s));
+    FSN_TRY(fsn_launch_gemm(gemm_a_rows(x, ldx), wih0_p, gemm_c_frag(gx0, b0), T * (N / 16), 4 * H / 16, Ipad / 16, s));
     FSN_PERSIST_BEGIN(s);
     FSN_TRY(fsn_launch_fb_chain(gx0, whh0_p, wih1_p, whh1_p, b1, exchange, flags, hseq1, T, N, H, s, hseq0,
                                 static_cast<float*>(save0), static_cast<float*>(save1)));
@@ -285,27 +255,14 @@ extern "C" int fsn_lstm_layer_backward(const float* dh, const float* x, long ldx
     FSN_TRY(fsn_launch_pack(w_hh, whhT_p, H, G, H, G, s, 1, H));
     FSN_TRY(fsn_launch_pack(w_ih, wihT_p, I, G, Ipad, G, s, 1, I));
     const size_t step = (size_t)N * H;
-    FsnGemmA a{};
-    FsnGemmC c{};
     // one fused launch per step: dh_rec = dgates_{t+1} W_hh, then the cell derivative -> dgates_t
     for (int t = T - 1; t >= 0; --t)
         FSN_TRY(fsn_launch_bptt_step(dh + t * step, t + 1 < T ? dgates + (size_t)(t + 1) * N * G : dgates, whhT_p, dc,
                                      gates + (size_t)t * N * G, cseq + t * step, t ? cseq + (t - 1) * step : cseq,
                                      dgates + (size_t)t * N * G, N / 16, H, t == T - 1, t == 0, s));
     (void)dh_rec;
-    if (dx) {
-        a = FsnGemmA{};
-        a.kind = 0;
-        a.p0 = dgates;
-        a.ld = G;
-        c = FsnGemmC{};
-        c.kind = 3;
-        c.p0 = dx;
-        c.ld = lddx;
-        c.rows = T * N;
-        c.cols = I;
-        FSN_TRY(fsn_launch_gemm(a, wihT_p, c, T * (N / 16), Ipad / 16, G / 16, s));
-    }
+    if (dx)
+        FSN_TRY(fsn_launch_gemm(gemm_a_rows(dgates, G), wihT_p, gemm_c_rows(dx, lddx, T * N, I), T * (N / 16), Ipad / 16, G / 16, s));
     // dW_ih = dgates^T X and, from the same pass over dgates, db = its column sums
     FSN_TRY(fsn_launch_gemm_tn(dgates, G, x, ldx, dw_ih, I, G, I, (long)T * N, scratch, s, db));
     if (T > 1) {
@@ -421,17 +378,7 @@ static int lstm2_backward_phases(const float* dh1, const float* x, long ldx, con
             FSN_TRY(fsn_launch_poison_if(flags + fsn_fb_chain_bptt_status_word(), dg1, (size_t)2 * T * N * G, s));
         }
         if (dx && dx_part) {
-            FsnGemmA a{};
-            a.kind = 0;
-            a.p0 = dg0;
-            a.ld = G;
-            FsnGemmC c{};
-            c.kind = 3;
-            c.p0 = dx;
-            c.ld = lddx;
-            c.rows = T * N;
-            c.cols = I;
-            FSN_TRY(fsn_launch_gemm(a, wih0T_p, c, T * (N / 16), Ipad / 16, G / 16, s));
+            FSN_TRY(fsn_launch_gemm(gemm_a_rows(dg0, G), wih0T_p, gemm_c_rows(dx, lddx, T * N, I), T * (N / 16), Ipad / 16, G / 16, s));
         }
         if (!products_part) return FSN_OK;
         FSN_TRY(fsn_launch_gemm_tn(dg1, G, hseq0, H, dw_ih1, H, G, H, (long)T * N, scratch, s, db1));
@@ -514,14 +461,8 @@ static int lstm2_backward_phases(const float* dh1, const float* x, long ldx, con
         FSN_TRY(fsn_launch_pack(w_ih0, wih0T_p, I, G, Ipad, G, s, 1, I));
     }
     if (w16 && !g16) FSN_TRY(fsn_launch_to16(whh1T_p, w16, (size_t)3 * H * G, arith, s));  // the BPTT kernel's W^T fragments in 16 bits
-    StreamCtx* cx = cur_ctx();
-    if (left > 0) {
-        FSN_TRY(aux_init(cx));
-        if (hipEventRecord(cx->ev_fork, s) != hipSuccess || hipStreamWaitEvent(cx->aux, cx->ev_fork, 0) != hipSuccess) {
-            fsn_set_error("aux stream fork failed");
-            return FSN_ERR_LAUNCH;
-        }
-    }
+    hipStream_t as = s;
+    if (left > 0) FSN_TRY(aux_fork(s, &as));
     {
         FSN_PERSIST_BEGIN(s);
         if (g16) {  // the 16-bit arithmetic's own kernel (K-split; packs the raw weights its way into w16)
@@ -544,7 +485,6 @@ static int lstm2_backward_phases(const float* dh1, const float* x, long ldx, con
     }
     if (left > 0) {
         // the rows that do not fill a cluster: step by step on the auxiliary stream, straight into the same buffers
-        hipStream_t as = cx->aux;
         const size_t stepH = (size_t)N * H, stepG = (size_t)N * G;
         for (int layer = 1; layer >= 0; --layer) {
             const float* sv = layer ? sv1 : sv0;
@@ -559,28 +499,12 @@ static int lstm2_backward_phases(const float* dh1, const float* x, long ldx, con
                                              t == T - 1, t == 0, as));
             }
             if (layer) {  // dh0 of these rows = dgates1 W_ih1: compact copy of their dgates1, one small GEMM
-                if (hipMemcpy2DAsync(dg1_left, (size_t)left * G * sizeof(float), dg, stepG * sizeof(float),
-                                     (size_t)left * G * sizeof(float), T, hipMemcpyDeviceToDevice, as) != hipSuccess) {
-                    fsn_set_error("lstm2 backward: cannot gather the left-over rows");
-                    return FSN_ERR_LAUNCH;
-                }
-                FsnGemmA a{};
-                a.kind = 0;
-                a.p0 = dg1_left;
-                a.ld = G;
-                FsnGemmC c{};
-                c.kind = 3;
-                c.p0 = dh0_left;
-                c.ld = H;
-                c.rows = T * left;
-                c.cols = H;
-                FSN_TRY(fsn_launch_gemm(a, wih1T_p, c, T * left_tiles, H / 16, G / 16, as));
+                FSN_TRY(gather_step_rows(dg1_left, dg1, G, T, N, row0, left, G, as));
+                FSN_TRY(fsn_launch_gemm(gemm_a_rows(dg1_left, G), wih1T_p, gemm_c_rows(dh0_left, H, T * left, H), T * left_tiles,
+                                        H / 16, G / 16, as));
             }
         }
-        if (hipEventRecord(cx->ev_join, cx->aux) != hipSuccess || hipStreamWaitEvent(s, cx->ev_join, 0) != hipSuccess) {
-            fsn_set_error("aux stream join failed");
-            return FSN_ERR_LAUNCH;
-        }
+        FSN_TRY(aux_join(s));
     }
     }  // chain_part
     if (dx && dx_part && in16) {
@@ -588,17 +512,7 @@ static int lstm2_backward_phases(const float* dh1, const float* x, long ldx, con
         FSN_TRY(fsn_launch_g16_left_to16(dg0, dg16, T, N, row0, left, s, arith));
         FSN_TRY(fsn_launch_gemm_dx16(dg16, G, w_ih0, wdx16, dx, lddx, (long)T * N, G, I, s, arith));
     } else if (dx && dx_part) {
-        FsnGemmA a{};
-        FsnGemmC c{};
-        a.kind = 0;
-        a.p0 = dg0;
-        a.ld = G;
-        c.kind = 3;
-        c.p0 = dx;
-        c.ld = lddx;
-        c.rows = T * N;
-        c.cols = I;
-        FSN_TRY(fsn_launch_gemm(a, wih0T_p, c, T * (N / 16), Ipad / 16, G / 16, s));
+        FSN_TRY(fsn_launch_gemm(gemm_a_rows(dg0, G), wih0T_p, gemm_c_rows(dx, lddx, T * N, I), T * (N / 16), Ipad / 16, G / 16, s));
     }
     if (!products_part) return FSN_OK;
     // dW_ih = dgates^T X (+ db = its column sums: fp32 adds in every arithmetic), dW_hh = dgates_{1..}^T H_{0..T-2}
@@ -704,20 +618,7 @@ extern "C" int fsn_linear_forward(const float* x, long ldx, const float* w, cons
     float* bp = cv.take<float>((size_t)Op);
     FSN_TRY(fsn_launch_pack(w, wp, O, I, Op, Ip, s));
     FSN_TRY(fsn_launch_bias_sum(b, nullptr, bp, O, Op, s));
-    FsnGemmA a{};
-    a.kind = 0;
-    a.p0 = x;
-    a.ld = ldx;
-    FsnGemmC c{};
-    c.kind = 3;
-    c.p0 = y;
-    c.bias = bp;
-    c.ld = O;
-    c.rows = R;
-    c.cols = O;
-    c.la = relu ? 1 : 0;  // kind 3: la doubles as the ReLU flag
-    a.N = R;
-    return fsn_launch_gemm(a, wp, c, (R + 15) / 16, Op / 16, Ip / 16, s);
+    return fsn_launch_gemm(gemm_a_rows(x, ldx, R), wp, gemm_c_rows(y, O, R, O, bp, relu != 0), (R + 15) / 16, Op / 16, Ip / 16, s);
 }
 
 // dy [R][lddy] (columns O..lddy-1 zero, lddy = round_up(O,16)) -> dx [R][lddx] (may be NULL), dw [O][I], db [O]
@@ -746,18 +647,7 @@ extern "C" int fsn_linear_backward(const float* dy, long lddy, const float* x, l
     } else if (dx) {
         // dX = dY W: "weights" W^T (out = I, k = O) = the stored [O][I] read transposed
         FSN_TRY(fsn_launch_pack(w, wtp, I, O, Ip, Op, s, 1, I));
-        FsnGemmA a{};
-        a.kind = 0;
-        a.p0 = dy;
-        a.ld = lddy;
-        FsnGemmC c{};
-        c.kind = 3;
-        c.p0 = dx;
-        c.ld = lddx;
-        c.rows = R;
-        c.cols = I;
-        a.N = R;
-        FSN_TRY(fsn_launch_gemm(a, wtp, c, (R + 15) / 16, Ip / 16, Op / 16, s));
+        FSN_TRY(fsn_launch_gemm(gemm_a_rows(dy, lddy, R), wtp, gemm_c_rows(dx, lddx, R, I), (R + 15) / 16, Ip / 16, Op / 16, s));
     }
     if (!dw) return FSN_OK;  // the input gradient alone (the parameter gradients by a second call, possibly on another stream)
     FSN_TRY(fsn_launch_gemm_tn(dy, lddy, x, ldx, dw, I, O, I, R, scratch, s));
