@@ -367,16 +367,17 @@ __global__ __launch_bounds__(256) void tr_target_kernel(const float* __restrict_
                                                        const float* __restrict__ cr, const float* __restrict__ ci,
                                                        float* __restrict__ target, TrDims d) {
     const float eps = 1.1920928955078125e-07f;  // audio_zen/constant.py:9
-    const int r = blockIdx.y;
-    int b, f;
-    tr_row_bf(d, r, b, f);
-    const size_t src = ((size_t)b * d.F + f) * d.T;
-    const size_t dst = ((size_t)(r / d.Fs) * 2 * d.Fs + r % d.Fs) * d.T;
-    for (int t = blockIdx.x * 256 + threadIdx.x; t < d.T; t += gridDim.x * 256) {
-        const float a = nr[src + t], bb = ni[src + t], c = cr[src + t], dd = ci[src + t];
-        const float den = a * a + bb * bb + eps;
-        target[dst + t] = tr_compress((a * c + bb * dd) / den);
-        target[dst + (size_t)d.Fs * d.T + t] = tr_compress((a * dd - bb * c) / den);
+    for (int r = blockIdx.y; r < d.R; r += gridDim.y) {  // grid.y stops at 65535: more rows than that stride over it
+        int b, f;
+        tr_row_bf(d, r, b, f);
+        const size_t src = ((size_t)b * d.F + f) * d.T;
+        const size_t dst = ((size_t)(r / d.Fs) * 2 * d.Fs + r % d.Fs) * d.T;
+        for (int t = blockIdx.x * 256 + threadIdx.x; t < d.T; t += gridDim.x * 256) {
+            const float a = nr[src + t], bb = ni[src + t], c = cr[src + t], dd = ci[src + t];
+            const float den = a * a + bb * bb + eps;
+            target[dst + t] = tr_compress((a * c + bb * dd) / den);
+            target[dst + (size_t)d.Fs * d.T + t] = tr_compress((a * dd - bb * c) / den);
+        }
     }
 }
 // Time-major rows [T][N][W] <-> `n` pieces [n][T][rows][W] of whole clusters (rows beyond N: zeros going in, dropped coming
@@ -570,7 +571,7 @@ extern "C" int fsn_train_cirm_target(const fsn_train_dims* dims, const float* no
     TR_REQUIRE_DIMS(dims);
     const TrDims d = tr_dims(dims);
     FSN_REQUIRE(noisy_real && noisy_imag && clean_real && clean_imag && target, "train target: NULL pointer argument");
-    hipLaunchKernelGGL(tr_target_kernel, dim3((unsigned)((d.T + 255) / 256), (unsigned)d.R), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(tr_target_kernel, dim3((unsigned)((d.T + 255) / 256), (unsigned)(d.R < 65535 ? d.R : 65535)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        noisy_real, noisy_imag, clean_real, clean_imag, target, d);
     return fsn_check_launch("tr_target_kernel");
 }

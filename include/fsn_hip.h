@@ -530,7 +530,14 @@ int fsn_mse_loss(const float* input, const float* target, size_t n, float* loss,
  *                           (offline; the mean of the unfolded tensor is taken from per-bin sums and window multiplicities) or
  *                           [Tp][Rp], one per unit and frame (cumulative: base_model.py:230-251 sees the units as samples and
  *                           a unit's 2 nb + 2 rows as its frequencies; Rp <= rows rounded up to 64).  The unfolded tensor is
- *                           never formed.
+ *                           never formed.  CALL ORDER: the offline norm reads the per-bin sums over the frames (rowsum
+ *                           [B][F], fp64, the first region of `workspace`, written by tr_rowsum_kernel) that
+ *                           fsn_train_fb_input of the same dims and the same mag left there - call fsn_train_fb_input
+ *                           first, on the same workspace.  That region is what must survive: no entry of this group
+ *                           writes it but fsn_train_fb_input (the backward overwrites the per-frame partials and the
+ *                           mean gradients, which fsn_train_sb_input forms anew), so the backward of one step may run
+ *                           before the next fsn_train_sb_input of the same mag; a call with other dims or another mag
+ *                           in between may not.  Rows >= B and columns >= F of fb_out_tm are never read.
  * fsn_train_sb_input_backward  dx [Tp][Rp][32] (d loss / d sb_in, from fsn_lstm2_backward) -> d_fb [Tp Bp][ld_dfb]: the
  *                           gradient of the full-band output layer's PRE-activation (through the ReLU: fb_out > 0), directly
  *                           (column 2 nb + 1 of the kept rows) and through the mean (cumulative: through the running means of
@@ -540,7 +547,8 @@ int fsn_mse_loss(const float* input, const float* target, size_t n, float* loss,
  *                           look-ahead frames dropped (model.py:129-135).   fsn_train_mask_grad: its adjoint, d_mask ->
  *                           dy [Tp][Rp][ld] (zeros in the look-ahead frames and the padding).
  * fsn_train_cirm_target     compressed cIRM of (noisy, clean) spectra [B][F][T] (mask.py:7-44), band-dropped like the
- *                           prediction, in its layout [B][2][Fs][T] (trainer.py:51-53).
+ *                           prediction, in its layout [B][2][Fs][T] (trainer.py:51-53).  Any row count B Fs (more than
+ *                           65535 rows stride over the grid).
  * fsn_scale_by_scalar       y = x * (*scale), scale a device scalar (the incoming gradient of the loss). */
 typedef struct fsn_train_dims {
     int B, F, T, look_ahead, nb, groups;
