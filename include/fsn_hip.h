@@ -109,7 +109,10 @@ int fsn_mask_istft(const float* crm, const float* real, const float* imag, const
 
 /* ---- cIRM mask algebra : audio_zen/acoustics/mask.py ----------------------------------- */
 
-/* mask.py:47-64  decompress_cIRM(mask, K=10, limit=9.9), elementwise over n floats. */
+/* The three entries below clamp with comparisons, not with mask.py's products of the value and a 0 / 1 condition: NaN stays
+ * NaN, and an infinite input takes the clamp's value where the tensor expression gives inf * 0 = NaN (decompress: +-inf as
+ * +-9.9f; compress: -inf as -100, +inf gives exactly 10).  Beyond the clamps the result is bit for bit the one at the clamp.
+ * mask.py:47-64  decompress_cIRM(mask, K=10, limit=9.9), elementwise over n floats. */
 int fsn_decompress_cirm(const float* mask, float* out, size_t n, void* stream);
 /* mask.py:32-44  compress_cIRM(mask, K=10, C=0.1). */
 int fsn_compress_cirm(const float* mask, float* out, size_t n, void* stream);
@@ -582,7 +585,9 @@ int fsn_scale_by_scalar(const float* x, const float* scale, float* y, size_t n, 
  *                           [T0 + look_ahead][Bp][Fp] of the mel product (model.py:157), zero beyond (T0, B, F).
  * fsn_fast_norm_rows        offline_laplace_norm (base_model.py:204-218) of x [T][Bp][C]: out = x / (mean over the
  *                           utterance's T x C values + 1e-5), rows beyond B zero (model.py:160, the encoder's input).
- *                           workspace: fsn_fast_glue_workspace_bytes.
+ *                           workspace: B floats rounded up to 256 bytes, which every fsn_fast_glue_workspace_bytes(T >= 2,
+ *                           B, ...) covers (the query itself answers 0 for T = 1, a length this entry takes); rows >= B of x
+ *                           are not read.
  * fsn_fast_bottleneck_input model.py:163-178: unit windows of mel (mel_neighbors) and of the encoder output (enc_neighbors),
  *                           reflected at the band edges (base_model.py:14-46), concatenated, down-sampled in time (frame 0
  *                           kept, then means over blocks of `shrink` frames, a shorter last block over what it has),

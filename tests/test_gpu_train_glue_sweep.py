@@ -550,16 +550,20 @@ def adam_torch(c, dtype, step=None):
 class Stat:
     """Error of one arithmetic output against fp64, accumulated over draws."""
 
-    def __init__(self, name, scalar=False):
+    def __init__(self, name, scalar=False, k=None, no_hard=None):
         """scalar: an output of one element per call or utterance (offline den, loss, total norm), whose sharp rule is
-        asserted by the *-pool rows; every other output must have pooled POOL_ELEMS elements when it is checked."""
-        self.name, self.k, self.scalar = name, K[name], scalar
+        asserted by the *-pool rows; every other output must have pooled POOL_ELEMS elements when it is checked.
+        k, no_hard: for the sweeps that share this checker and keep a k table of their own (default: this module's)."""
+        self.name, self.k, self.scalar = name, K[name] if k is None else k, scalar
+        self.no_hard = name in NO_HARD if no_hard is None else no_hard
         self.tiny = TINY if name in ("g", "m", "v", "p") else 0.0  # gradients of 1e-30: squares below the fp32 range
         self.n = 0
         self.hard = 0.0
         self.ss = {"hip": 0.0, "cpu": 0.0}
 
-    def add(self, got, ref64, S, cpu):
+    def add(self, got, ref64, S, cpu, k=None):
+        """k: per-element rounding counts where they differ within one output (default: the output's own)."""
+        k = self.k if k is None else np.asarray(k, dtype=np.float64)
         got, ref64, S, cpu = (np.asarray(a, dtype=np.float64) for a in (got, ref64, S, cpu))
         assert got.shape == ref64.shape == S.shape == cpu.shape, f"{self.name}: shapes {got.shape} {ref64.shape} {S.shape} {cpu.shape}"
         self.n += ref64.size
@@ -569,7 +573,7 @@ class Stat:
                 err = np.abs(t - ref64)
             err = np.where(np.isnan(err), np.inf, err)
             if key == "hip":
-                bound = self.k * (U * S + self.tiny)
+                bound = k * (U * S + self.tiny)
                 ok = bound > 0
                 self.hard = max(self.hard, float(np.where(ok, err / np.where(ok, bound, 1.0), np.where(err > 0, np.inf, 0.0)).max()))
             rel = np.where(pos, err / np.where(pos, S, 1.0), np.where(err > 0, np.inf, 0.0))
@@ -582,7 +586,7 @@ class Stat:
         print(f"[glue-sweep] {row_id} {self.name}: n {self.n} hard {self.hard:.4f} rms hip {self.rms('hip'):.4f} u cpu {self.rms('cpu'):.4f} u")
 
     def check(self):
-        if self.name not in NO_HARD:
+        if not self.no_hard:
             assert self.hard <= 1.0, f"{self.name}: worst element at {self.hard:.3f} of the {self.k} 2^-24 S bound"
         if not self.scalar:
             assert self.n >= POOL_ELEMS, f"{self.name}: {self.n} elements pooled, the sharp rule needs {POOL_ELEMS}"
