@@ -103,6 +103,10 @@ SIGNATURES = {
     "fsn_stft": (_c.c_int, [_f32p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _f32p, _f32p, _f32p, _f32p,
                             _c.c_void_p]),
     "fsn_stft_ragged": (_c.c_int, [_f32p, _c.c_void_p] + [_c.c_int] * 5 + [_f32p, _f32p, _f32p, _f32p, _c.c_void_p]),
+    "fsn_stft_ragged_generic": (_c.c_int, [_f32p, _c.c_void_p] + [_c.c_int] * 5 + [_f32p, _f32p, _f32p, _f32p, _c.c_void_p]),
+    "fsn_istft_ragged_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "fsn_istft_ragged": (_c.c_int, [_f32p, _f32p, _c.c_void_p] + [_c.c_int] * 5 + [_f32p, _c.c_int, _f32p, _c.c_void_p,
+                                                                               _c.c_size_t, _c.c_void_p]),
     "fsn_mask_istft_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
     "fsn_mask_istft": (_c.c_int, [_f32p, _f32p, _f32p, _c.c_void_p] + [_c.c_int] * 6 + [_f32p, _c.c_int, _f32p, _c.c_void_p,
                                                                                          _c.c_size_t, _c.c_void_p]),
@@ -179,6 +183,11 @@ SIGNATURES = {
     "fsn_improved_section_input_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int]),
     "fsn_improved_section_input": (_c.c_int, [_f32p, _f32p] + [_c.c_int] * 11 + [_c.c_float, _f32p, _c.c_int, _c.c_int,
                                                                                 _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_improved_section_input_ragged": (_c.c_int, [_f32p, _f32p, _c.c_void_p] + [_c.c_int] * 11
+                                          + [_c.c_float, _f32p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_improved_front_norm_ragged_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "fsn_improved_front_norm_ragged": (_c.c_int, [_f32p, _c.c_void_p] + [_c.c_int] * 4 + [_c.c_float, _f32p, _f32p, _c.c_void_p,
+                                                                                         _c.c_size_t, _c.c_void_p]),
     "fsn_lstm2_multi_is_persistent": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int]),
     "fsn_lstm2_multi_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_void_p, _c.c_int]),
     "fsn_lstm2_forward_multi": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),

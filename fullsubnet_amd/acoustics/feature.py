@@ -47,17 +47,48 @@ def stft(y, n_fft, hop_length, win_length, return_phase=True):
 def stft_ragged(y, lengths, n_fft, hop_length, win_length):
     """A ragged batch y [B, L_max] (row b: ``lengths[b]`` samples, device int32 [B]) -> (mag, real, imag) [B, F, T_max]:
     row b is ``stft(y[b:b + 1, :lengths[b]])`` in its first ``1 + lengths[b] // hop`` frames, zeros after them
-    (libfsn_hip ``fsn_stft_ragged``: n_fft 512 / hop 256 only)."""
+    (libfsn_hip ``fsn_stft_ragged`` at n_fft 512 / hop 256, ``fsn_stft_ragged_generic`` at every other shape ``stft``
+    takes)."""
     y = y.contiguous()
     B, num_samples = y.shape
     F, T = n_fft // 2 + 1, 1 + num_samples // hop_length
     real = torch.empty((B, F, T), dtype=torch.float32, device=y.device)
     imag = torch.empty_like(real)
     mag = torch.empty_like(real)
-    _lib.check(_lib.lib().fsn_stft_ragged(_lib.dev_ptr(y, "y"), lengths.data_ptr(), B, num_samples, n_fft, hop_length, win_length,
-                                          _lib.dev_ptr(hann_window(n_fft, y.device)), _lib.dev_ptr(real), _lib.dev_ptr(imag),
-                                          _lib.dev_ptr(mag), _lib.stream_ptr(y.device)))
+    L = _lib.lib()
+    entry = L.fsn_stft_ragged if (n_fft, hop_length) == (512, 256) else L.fsn_stft_ragged_generic
+    _lib.check(entry(_lib.dev_ptr(y, "y"), _device_lengths(lengths, B, y.device), B, num_samples, n_fft, hop_length, win_length,
+                     _lib.dev_ptr(hann_window(n_fft, y.device)), _lib.dev_ptr(real), _lib.dev_ptr(imag), _lib.dev_ptr(mag),
+                     _lib.stream_ptr(y.device)))
     return mag, real, imag
+
+
+def _device_lengths(lengths, batch, device):
+    """The address of a ragged batch's ``lengths``: a contiguous int32 [B] tensor on ``device`` (the kernels read it)."""
+    if (not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or lengths.shape != (batch,)
+            or lengths.device != device or not lengths.is_contiguous()):
+        raise _lib.FsnError(f"lengths must be a contiguous int32 [{batch}] tensor on {device}")
+    return lengths.data_ptr()
+
+
+def istft_ragged(features, lengths, n_fft, hop_length, win_length, length):
+    """``istft`` of a ragged batch: features = (real, imag) [B, F, T_max], ``lengths`` device int32 [B], ``length`` the
+    longest row (T_max = 1 + length // hop) -> [B, length]: row b is ``istft`` of its own first ``1 + lengths[b] // hop``
+    frames at ``length=lengths[b]``, zero from there on; frames past a row's end are never read (libfsn_hip
+    ``fsn_istft_ragged``, every shape ``istft`` takes)."""
+    real, imag = features
+    real, imag = real.contiguous(), imag.contiguous()
+    B, F, T = real.shape
+    assert F == n_fft // 2 + 1
+    if hop_length >= n_fft:  # as istft: the overlap-added squared window is zero at every n_fft-th sample
+        raise RuntimeError(f"istft_ragged: window overlap add min is zero at hop_length {hop_length} >= n_fft {n_fft}")
+    y = torch.empty((B, length), dtype=torch.float32, device=real.device)
+    L = _lib.lib()
+    ws = _lib.workspace(L.fsn_istft_ragged_workspace_bytes(B, T, n_fft), real.device)
+    _lib.check(L.fsn_istft_ragged(_lib.dev_ptr(real, "real"), _lib.dev_ptr(imag, "imag"), _device_lengths(lengths, B, real.device),
+                                  B, T, n_fft, hop_length, win_length, _lib.dev_ptr(hann_window(n_fft, real.device)), length,
+                                  _lib.dev_ptr(y), ws.data_ptr(), ws.numel(), _lib.stream_ptr(real.device)))
+    return y
 
 
 def mask_istft(crm, real, imag, n_fft, hop_length, win_length, length, lengths=None):

@@ -18,17 +18,44 @@ __device__ __forceinline__ void fill_twiddles(double* c, double* s, int N) {
     }
 }
 
+// Ragged batches (kRagged; fsn_stft_ragged_generic, fsn_istft_ragged): lengths [B] holds row b's sample count L_b, the
+// row stride stays L (the longest row) and T is the longest row's frame count.  Row b is the transform of its own
+// L_b samples - reflected at its own end - in its first T_b = 1 + L_b / hop frames; a frame past T_b is a zero store
+// (forward) or is skipped (inverse: the overlap-add never reads it).  Values are clamped to [N / 2 + 1, L], so no index
+// leaves the row whatever the array holds.  With L_b = L the index arithmetic, and so every bit, is the rectangular one.
+__device__ __forceinline__ int row_samples(const int* lengths, int b, int L, int N) {
+    const int l = lengths[b];
+    return l < N / 2 + 1 ? N / 2 + 1 : (l > L ? L : l);
+}
+__device__ __forceinline__ int row_frames(const int* lengths, int b, int L, int N, int hop, int T) {
+    const int t = 1 + row_samples(lengths, b, L, N) / hop;
+    return t < T ? t : T;
+}
+
 // grid (B * T, ceil(F / 256)); re / im / mag [B][F][T] (any may be NULL)
+template <bool kRagged>
 __global__ __launch_bounds__(256) void dft_stft_kernel(const float* __restrict__ y, const float* __restrict__ window,
                                                        float* __restrict__ re, float* __restrict__ im,
-                                                       float* __restrict__ mag, int L, int T, int N, int hop, int F) {
+                                                       float* __restrict__ mag, int L, int T, int N, int hop, int F,
+                                                       const int* __restrict__ lengths) {
     extern __shared__ double sh[];
     double *x = sh, *c = sh + N, *s = sh + 2 * N;
     const int b = blockIdx.x / T, t = blockIdx.x % T;
+    const int Lb = kRagged ? row_samples(lengths, b, L, N) : L;
+    if (kRagged && t >= 1 + Lb / hop) {  // past the row's end (the whole workgroup: b and t are its own)
+        const int f = blockIdx.y * blockDim.x + threadIdx.x;
+        if (f < F) {
+            const long o = ((long)b * F + f) * T + t;
+            if (re) re[o] = 0.f;
+            if (im) im[o] = 0.f;
+            if (mag) mag[o] = 0.f;
+        }
+        return;
+    }
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
         int j = hop * t + n - N / 2;  // centre padding, reflect without repeating the edge
         j = j < 0 ? -j : j;
-        j = j >= L ? 2 * (L - 1) - j : j;
+        j = j >= Lb ? 2 * (Lb - 1) - j : j;
         x[n] = (double)(y[(long)b * L + j] * window[n]);  // the frame is rounded to fp32 like ATen's
     }
     fill_twiddles(c, s, N);
@@ -52,12 +79,14 @@ __global__ __launch_bounds__(256) void dft_stft_kernel(const float* __restrict__
 }
 
 // grid (B * T, ceil(N / 256)); re / im [B][F][T] -> windowed time frames wframes [B][T][N]
+template <bool kRagged>
 __global__ __launch_bounds__(256) void dft_irfft_kernel(const float* __restrict__ re, const float* __restrict__ im,
                                                         const float* __restrict__ window, float* __restrict__ wframes,
-                                                        int T, int N, int F) {
+                                                        int T, int N, int F, const int* __restrict__ lengths, int L, int hop) {
     extern __shared__ double sh[];
     double *xr = sh, *xi = sh + F, *c = sh + 2 * F, *s = sh + 2 * F + N;
     const int b = blockIdx.x / T, t = blockIdx.x % T;
+    if (kRagged && t >= row_frames(lengths, b, L, N, hop, T)) return;  // neither read nor written: the overlap-add stops at T_b
     for (int f = threadIdx.x; f < F; f += blockDim.x) {
         const long o = ((long)b * F + f) * T + t;
         const bool edge = f == 0 || f == N / 2;  // C2R: imaginary parts of DC / Nyquist are ignored
@@ -95,20 +124,31 @@ __global__ __launch_bounds__(256) void dft_irfft_kernel(const float* __restrict_
 //     Ct[n2][k1] = conj(W_N^{n2 k1}) sum_{k2} X[k1 + P k2] conj(W_N^{P n2 k2}), X completed by Hermitian symmetry
 //     x[Q n1 + n2] = Re sum_{k1} Ct[n2][k1] conj(W_N^{Q n1 k1})              (2 fma per term)
 // LDS: table 2 N + frame N (2 N complex for the inverse) + intermediate 2 N doubles: 38 / 46 KB at N = 960.
+template <bool kRagged>
 __global__ __launch_bounds__(256) void dft2_stft_kernel(const float* __restrict__ y, const float* __restrict__ window,
                                                         float* __restrict__ re, float* __restrict__ im,
                                                         float* __restrict__ mag, int L, int T, int N, int hop, int F, int P,
-                                                        int Q, long frames) {
+                                                        int Q, long frames, const int* __restrict__ lengths) {
     extern __shared__ double sh[];
     double *c = sh, *s = sh + N, *x = sh + 2 * N, *br = sh + 3 * N, *bi = sh + 4 * N;
     fill_twiddles(c, s, N);
     for (long fr = blockIdx.x; fr < frames; fr += gridDim.x) {
         const int b = (int)(fr / T), t = (int)(fr % T);
         __syncthreads();  // table ready / previous frame's stage 2 done with x and Bt
+        const int Lb = kRagged ? row_samples(lengths, b, L, N) : L;
+        if (kRagged && t >= 1 + Lb / hop) {  // past the row's end: a zero store (every thread takes this branch)
+            for (int k = threadIdx.x; k < F; k += blockDim.x) {
+                const long o = ((long)b * F + k) * T + t;
+                if (re) re[o] = 0.f;
+                if (im) im[o] = 0.f;
+                if (mag) mag[o] = 0.f;
+            }
+            continue;
+        }
         for (int n = threadIdx.x; n < N; n += blockDim.x) {
             int j = hop * t + n - N / 2;  // centre padding, reflect without repeating the edge
             j = j < 0 ? -j : j;
-            j = j >= L ? 2 * (L - 1) - j : j;
+            j = j >= Lb ? 2 * (Lb - 1) - j : j;
             x[n] = (double)(y[(long)b * L + j] * window[n]);  // the frame is rounded to fp32 like ATen's
         }
         __syncthreads();
@@ -153,15 +193,18 @@ __global__ __launch_bounds__(256) void dft2_stft_kernel(const float* __restrict_
     }
 }
 
+template <bool kRagged>
 __global__ __launch_bounds__(256) void dft2_irfft_kernel(const float* __restrict__ re, const float* __restrict__ im,
                                                          const float* __restrict__ window, float* __restrict__ wframes,
-                                                         int T, int N, int F, int P, int Q, long frames) {
+                                                         int T, int N, int F, int P, int Q, long frames,
+                                                         const int* __restrict__ lengths, int L, int hop) {
     extern __shared__ double sh[];
     double *c = sh, *s = sh + N, *xr = sh + 2 * N, *xi = sh + 3 * N, *cr = sh + 4 * N, *ci = sh + 5 * N;
     fill_twiddles(c, s, N);
     for (long fr = blockIdx.x; fr < frames; fr += gridDim.x) {
         const int b = (int)(fr / T), t = (int)(fr % T);
         __syncthreads();
+        if (kRagged && t >= row_frames(lengths, b, L, N, hop, T)) continue;  // neither read nor written (every thread)
         for (int f = threadIdx.x; f < F; f += blockDim.x) {
             const long o = ((long)b * F + f) * T + t;
             const bool edge = f == 0 || f == N / 2;  // C2R: imaginary parts of DC / Nyquist are ignored
@@ -221,21 +264,26 @@ int dft2_factor(int N) {
 }
 
 // overlap-add (ascending frame order, fp32), division by the overlap-added squared window, centre
-// trim and length handling of torch.istft
+// trim and length handling of torch.istft.  kRagged: row b over its own Tb frames (the frame stride stays T) at its own
+// length, zeros from there on
+template <bool kRagged>
 __global__ __launch_bounds__(256) void ola_generic_kernel(const float* __restrict__ wframes,
                                                           const float* __restrict__ window, float* __restrict__ y,
-                                                          int B, int T, int N, int hop, int length) {
+                                                          int B, int T, int N, int hop, int length,
+                                                          const int* __restrict__ lengths) {
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long)B * length) return;
     const int b = (int)(gid / length), j = (int)(gid % length);
+    const int Lb = kRagged ? row_samples(lengths, b, length, N) : length;
+    const int Tb = kRagged ? row_frames(lengths, b, length, N, hop, T) : T;
     const int p = j + N / 2;
-    const long total = (long)N + (long)hop * (T - 1);
+    const long total = (long)N + (long)hop * (Tb - 1);
     float out = 0.f;
-    if (p < total) {
+    if (p < total && j < Lb) {
         int t0 = p - N + 1;
         t0 = t0 <= 0 ? 0 : (t0 + hop - 1) / hop;
         int t1 = p / hop;
-        t1 = t1 < T ? t1 : T - 1;
+        t1 = t1 < Tb ? t1 : Tb - 1;
         float acc = 0.f, env = 0.f;
         for (int t = t0; t <= t1; ++t) {
             const int n = p - hop * t;
@@ -250,51 +298,67 @@ __global__ __launch_bounds__(256) void ola_generic_kernel(const float* __restric
 
 }  // namespace
 
-int fsn_launch_dft_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag, int T,
-                        int N, int hop, hipStream_t s) {
+// Every instantiation is a kernel symbol of its own: the dynamic-LDS limit above 64 KB is raised on the one launched.
+template <bool kRagged>
+static int launch_dft_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag, int T, int N,
+                           int hop, const int* lengths, hipStream_t s) {
     const int F = N / 2 + 1;
     if (const int P = dft2_factor(N)) {
         const long frames = (long)B * T;
         const unsigned grid = (unsigned)(frames < 1024 ? frames : 1024);
         if (5 * N * sizeof(double) > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft2_stft_kernel),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft2_stft_kernel<kRagged>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(5 * N * sizeof(double)));
-        hipLaunchKernelGGL(dft2_stft_kernel, dim3(grid), dim3(256), 5 * N * sizeof(double), s, y, window, re, im, mag, L, T, N,
-                           hop, F, P, N / P, frames);
+        hipLaunchKernelGGL(dft2_stft_kernel<kRagged>, dim3(grid), dim3(256), 5 * N * sizeof(double), s, y, window, re, im, mag,
+                           L, T, N, hop, F, P, N / P, frames, lengths);
         return fsn_check_launch("dft2_stft_kernel");
     }
     const size_t lds = 3 * N * sizeof(double);  // 96 KB at N = 4096: above 64 KB a launch needs the attribute raised
     if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft_stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-    hipLaunchKernelGGL(dft_stft_kernel, dim3((unsigned)(B * T), (F + 255) / 256), dim3(256), lds, s, y, window, re, im, mag, L,
-                       T, N, hop, F);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft_stft_kernel<kRagged>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(dft_stft_kernel<kRagged>, dim3((unsigned)(B * T), (F + 255) / 256), dim3(256), lds, s, y, window, re, im,
+                       mag, L, T, N, hop, F, lengths);
     return fsn_check_launch("dft_stft_kernel");
 }
 
-int fsn_launch_dft_istft(const float* re, const float* im, const float* window, float* wframes, float* y, int B, int T,
-                         int N, int hop, int length, hipStream_t s) {
+// lengths != NULL: the ragged batch (length is then the row stride L_max of the waveforms)
+template <bool kRagged>
+static int launch_dft_istft(const float* re, const float* im, const float* window, float* wframes, float* y, int B, int T,
+                            int N, int hop, int length, const int* lengths, hipStream_t s) {
     const int F = N / 2 + 1;
     if (const int P = dft2_factor(N)) {
         const long frames = (long)B * T;
         const unsigned grid = (unsigned)(frames < 1024 ? frames : 1024);
         if (6 * N * sizeof(double) > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft2_irfft_kernel),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft2_irfft_kernel<kRagged>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(6 * N * sizeof(double)));
-        hipLaunchKernelGGL(dft2_irfft_kernel, dim3(grid), dim3(256), 6 * N * sizeof(double), s, re, im, window, wframes, T, N, F,
-                           P, N / P, frames);
+        hipLaunchKernelGGL(dft2_irfft_kernel<kRagged>, dim3(grid), dim3(256), 6 * N * sizeof(double), s, re, im, window, wframes,
+                           T, N, F, P, N / P, frames, lengths, length, hop);
         FSN_TRY_LAUNCH("dft2_irfft_kernel");
     } else {
         const size_t lds = (2 * F + 2 * N) * sizeof(double);
         if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft_irfft_kernel),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft_irfft_kernel<kRagged>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(dft_irfft_kernel, dim3((unsigned)(B * T), (N + 255) / 256), dim3(256), lds, s, re, im, window,
-                           wframes, T, N, F);
+        hipLaunchKernelGGL(dft_irfft_kernel<kRagged>, dim3((unsigned)(B * T), (N + 255) / 256), dim3(256), lds, s, re, im, window,
+                           wframes, T, N, F, lengths, length, hop);
         FSN_TRY_LAUNCH("dft_irfft_kernel");
     }
     const long n = (long)B * length;
-    hipLaunchKernelGGL(ola_generic_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, wframes, window, y, B, T,
-                       N, hop, length);
+    hipLaunchKernelGGL(ola_generic_kernel<kRagged>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, wframes, window, y, B, T,
+                       N, hop, length, lengths);
     return fsn_check_launch("ola_generic_kernel");
+}
+
+int fsn_launch_dft_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag, int T,
+                        int N, int hop, hipStream_t s, const int* lengths) {
+    return lengths ? launch_dft_stft<true>(y, B, L, window, re, im, mag, T, N, hop, lengths, s)
+                   : launch_dft_stft<false>(y, B, L, window, re, im, mag, T, N, hop, nullptr, s);
+}
+
+int fsn_launch_dft_istft(const float* re, const float* im, const float* window, float* wframes, float* y, int B, int T,
+                         int N, int hop, int length, hipStream_t s, const int* lengths) {
+    return lengths ? launch_dft_istft<true>(re, im, window, wframes, y, B, T, N, hop, length, lengths, s)
+                   : launch_dft_istft<false>(re, im, window, wframes, y, B, T, N, hop, length, nullptr, s);
 }

@@ -1139,6 +1139,44 @@ extern "C" int fsn_stft_ragged(const float* y, const int* lengths, int B, int L_
                            lengths);
 }
 
+// ragged batches at every shape fsn_stft / fsn_istft take: 512 / 256 on the radix-8 kernels' lengths path, any other
+// transform on the ragged forms of the direct-DFT kernels (improved_fullsubnet/model.py:550-557, 582-589: 512 / 128, 960 / 480)
+extern "C" int fsn_stft_ragged_generic(const float* y, const int* lengths, int B, int L_max, int n_fft, int hop, int win_length,
+                                       const float* window, float* real, float* imag, float* mag, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_fft_generic(n_fft, hop, win_length));
+    FSN_REQUIRE(y && lengths && window, "NULL pointer argument");
+    FSN_REQUIRE(B >= 1 && L_max > n_fft / 2, "need B >= 1 and L_max > n_fft/2 (reflect padding), got B=%d L_max=%d", B, L_max);
+    const int T = 1 + L_max / hop, F = n_fft / 2 + 1;
+    FSN_REQUIRE((long)B * T <= 0x7fffffffL, "too many frames");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!fast_fft(n_fft, hop)) return fsn_launch_dft_stft(y, B, L_max, window, real, imag, mag, T, n_fft, hop, s, lengths);
+    return fsn_launch_stft(y, B, L_max, window, real, imag, mag, T, T, F, fsn_fpad(F), false, s, lengths);
+}
+
+extern "C" size_t fsn_istft_ragged_workspace_bytes(int B, int T, int n_fft) { return fsn_istft_workspace_bytes(B, T, n_fft); }
+
+extern "C" int fsn_istft_ragged(const float* real, const float* imag, const int* lengths, int B, int T, int n_fft, int hop,
+                                int win_length, const float* window, int length, float* y, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_fft_generic(n_fft, hop, win_length));
+    FSN_TRY(check_bt(B, T));
+    FSN_REQUIRE(real && imag && lengths && window && y && workspace, "NULL pointer argument");
+    FSN_REQUIRE(length > n_fft / 2 && T == 1 + length / hop,
+                "fsn_istft_ragged: need length > n_fft/2 and T = 1 + length / hop (got length %d, T %d)", length, T);
+    if (workspace_bytes < fsn_istft_ragged_workspace_bytes(B, T, n_fft)) {
+        fsn_set_error("workspace too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int F = n_fft / 2 + 1;
+    float* wf = static_cast<float*>(workspace);
+    if (!fast_fft(n_fft, hop)) return fsn_launch_dft_istft(real, imag, window, wf, y, B, T, n_fft, hop, length, s, lengths);
+    FSN_TRY(fsn_launch_mask_irfft(real, imag, nullptr, nullptr, B, T, F, fsn_fpad(F), false, window, wf, s, lengths));
+    return fsn_launch_ola(wf, window, B, T, length, y, s, lengths);
+}
+
 extern "C" size_t fsn_mask_istft_workspace_bytes(int B, int T, int n_fft) {
     if (B < 1 || T < 1 || n_fft != 512) return 0;
     return fsn_istft_workspace_bytes(B, T, n_fft);

@@ -423,11 +423,10 @@ extern "C" size_t fsn_improved_section_input_workspace_bytes(int B, int F) {
     if (B < 1 || F < 2) return 0;
     return fsn_round_up_sz(fsn_section_input_workspace_floats(B, F) * sizeof(float), 256);
 }
-extern "C" int fsn_improved_section_input(const float* noisy, const float* fb_out, int B, int F, int T, int lower, int upper,
-                                          int sb_center, int sb_neighbor, int fb_center, int fb_neighbor, int unit_lo,
-                                          int unit_hi, float eps, float* out, int Np, int ldo, void* workspace,
-                                          size_t workspace_bytes, void* stream) {
-    CallScope scope(stream);
+// fsn_improved_section_input and its ragged form share one body; frames == NULL is the rectangular batch
+static int section_input(const float* noisy, const float* fb_out, const int* frames, int B, int F, int T, int lower, int upper,
+                         int sb_center, int sb_neighbor, int fb_center, int fb_neighbor, int unit_lo, int unit_hi, float eps,
+                         float* out, int Np, int ldo, void* workspace, size_t workspace_bytes, void* stream) {
     FSN_REQUIRE(noisy && fb_out && out && workspace, "NULL pointer argument");
     FSN_REQUIRE(B >= 1 && F >= 2 && T >= 1 && 0 <= lower && lower < upper && upper <= F, "section input: bad band [%d, %d) of %d bins",
                 lower, upper, F);
@@ -449,7 +448,24 @@ extern "C" int fsn_improved_section_input(const float* noisy, const float* fb_ou
         return FSN_ERR_WORKSPACE;
     }
     return fsn_launch_section_input(noisy, fb_out, B, F, T, lower, units, sb_center, sb_neighbor, fb_center, fb_neighbor, unit_lo,
-                                    unit_hi, eps, out, Np, ldo, workspace, static_cast<hipStream_t>(stream));
+                                    unit_hi, eps, out, Np, ldo, workspace, static_cast<hipStream_t>(stream), frames);
+}
+extern "C" int fsn_improved_section_input(const float* noisy, const float* fb_out, int B, int F, int T, int lower, int upper,
+                                          int sb_center, int sb_neighbor, int fb_center, int fb_neighbor, int unit_lo,
+                                          int unit_hi, float eps, float* out, int Np, int ldo, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    return section_input(noisy, fb_out, nullptr, B, F, T, lower, upper, sb_center, sb_neighbor, fb_center, fb_neighbor, unit_lo,
+                         unit_hi, eps, out, Np, ldo, workspace, workspace_bytes, stream);
+}
+extern "C" int fsn_improved_section_input_ragged(const float* noisy, const float* fb_out, const int* frames, int B, int F, int T,
+                                                 int lower, int upper, int sb_center, int sb_neighbor, int fb_center,
+                                                 int fb_neighbor, int unit_lo, int unit_hi, float eps, float* out, int Np, int ldo,
+                                                 void* workspace, size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(frames, "NULL pointer argument");
+    return section_input(noisy, fb_out, frames, B, F, T, lower, upper, sb_center, sb_neighbor, fb_center, fb_neighbor, unit_lo,
+                         unit_hi, eps, out, Np, ldo, workspace, workspace_bytes, stream);
 }
 
 // ---- several independent two-layer stacks over the same frames ------------------------------------------------------

@@ -336,11 +336,12 @@ int fsn_launch_pool_synthesis(void* state, const FsnPoolLayout& L, int capacity,
                               int k, const int* first_frame, const int* tail_samples, const float* window, float* wframes,
                               float* out, hipStream_t s);
 
-// dft_kernels.hip (any even n_fft / any hop: direct fp64 DFT; reference layout [B][F][T] only)
+// dft_kernels.hip (any even n_fft / any hop: direct fp64 DFT; reference layout [B][F][T] only).  lengths (device, [B], may
+// be NULL): per-row sample counts of a ragged batch; L / length is then the row stride and the longest row, T its frames
 int fsn_launch_dft_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag, int T,
-                        int N, int hop, hipStream_t s);
+                        int N, int hop, hipStream_t s, const int* lengths = nullptr);
 int fsn_launch_dft_istft(const float* re, const float* im, const float* window, float* wframes, float* y, int B, int T,
-                         int N, int hop, int length, hipStream_t s);
+                         int N, int hop, int length, hipStream_t s, const int* lengths = nullptr);
 
 // elementwise_kernels.hip
 int fsn_launch_decompress(const float* in, float* out, size_t n, hipStream_t s);
@@ -390,7 +391,7 @@ struct FsnGemmC {  // C store description
 size_t fsn_section_input_workspace_floats(int B, int F);
 int fsn_launch_section_input(const float* noisy, const float* fb, int B, int F, int T, int lower, int units, int sc, int sn,
                              int fc, int fn, int u_lo, int u_hi, float eps, float* out, int Np, int ldo, void* workspace,
-                             hipStream_t s);
+                             hipStream_t s, const int* frames = nullptr);  // frames (device, [B]): a ragged batch
 void fsn_tn_plan_splits(int M, int Nc, long K, int arith, int* splits, long* bound);  // lstm_train_kernels.hip (test hook)
 // nn.Linear with O <= 4 outputs and I % 64 == 0 inputs as row dot products / outer products (gemm_kernels.hip)
 bool fsn_linear_small_out_ok(int I, int O, long ldx);

@@ -182,6 +182,52 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict
     }
 }
 
+// ---- ragged front of Improved FullSubNet (fsn_improved_front_norm_ragged) ------------------------------------------------
+// out [B][F - 1][T] = mag[b][f][t] ** fdrc (sqrtf or the value: improved_front_kernel of section_kernels.hip) for
+// t < frames[b], zero from there on; mag is not read past a row's end (the caller's padding may hold anything)
+__device__ __forceinline__ int ragged_frames(const int* frames, int b, int T) {
+    const int t = frames[b];
+    return t < 1 ? 1 : (t > T ? T : t);
+}
+__global__ __launch_bounds__(256) void improved_front_ragged_kernel(const float* __restrict__ mag, const int* __restrict__ frames,
+                                                                   float* __restrict__ out, int B, int F, int T, int mode) {
+    const long n = (long)B * (F - 1) * T;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const long row = i / T;
+        const int t = (int)(i - row * T);
+        const long b = row / (F - 1), f = row - b * (F - 1);
+        float v = 0.f;
+        if (t < ragged_frames(frames, (int)b, T)) {
+            v = mag[(b * F + f) * T + t];
+            v = mode ? sqrtf(v) : v;
+        }
+        out[i] = v;
+    }
+}
+// offline_laplace_norm's divisor of a ragged batch: den[r][t] = float(sum over the row's first frames[r] frames / (Fr x
+// frames[r])) + eps for every t.  One wave per row; the per-frame sums of norm_frame_sums_kernel meet in norm_scan_kernel's
+// order (a frame's parts in index order, the lanes' frames t = lane, lane + 64, ..., a fixed butterfly), so frames[r] = T
+// gives fsn_norm's bits.
+__global__ __launch_bounds__(64) void norm_offline_laplace_ragged_kernel(const double* __restrict__ s1, const int* __restrict__ frames,
+                                                                        float* __restrict__ den, int R, int Fr, int T, float eps,
+                                                                        int parts) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const int Tb = ragged_frames(frames, r, T);
+    const long zs = (long)R * T;
+    double tot = 0.0;
+    for (int t = lane; t < Tb; t += 64) {
+        const double* p1 = s1 + (long)r * T + t;
+        double va = 0.0;
+        for (int z = 0; z < parts; ++z) va += p1[z * zs];
+        tot += va;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) tot += __shfl_xor(tot, m, 64);
+    const double n = (double)Fr * Tb;
+    const float d = (float)(tot / n) + eps;
+    for (int t = lane; t < T; t += 64) den[(long)r * T + t] = d;
+}
+
 struct NormDims {
     long R;     // statistic rows
     int Fr;     // extent summed per frame
@@ -254,5 +300,49 @@ extern "C" int fsn_norm(const float* x, float* y, int norm_type, int B, int C, i
     const unsigned gy = (unsigned)(rows < 32768 ? rows : 32768);
     hipLaunchKernelGGL(norm_apply_kernel, dim3((unsigned)((T + 255) / 256), gy), dim3(256), 0, s, x, y, shift, den, rows, T, d.Fr,
                        norm_type == FSN_NORM_OFFLINE_GAUSSIAN || norm_type == FSN_NORM_CUMULATIVE_LAYER);
+    return fsn_check_launch("norm_apply_kernel");
+}
+
+// improved_fullsubnet/model.py:565-566 and the offline Laplace norm of :567 on a ragged batch, ONE fused entry: the front
+// writes zeros past a row's end, so the per-frame sums and the division below read nothing of the caller's padding
+extern "C" size_t fsn_improved_front_norm_ragged_workspace_bytes(int B, int F, int T) {
+    if (F < 2) return 0;
+    return fsn_norm_workspace_bytes(FSN_NORM_OFFLINE_LAPLACE, B, 1, F - 1, T);
+}
+
+extern "C" int fsn_improved_front_norm_ragged(const float* mag, const int* frames, int B, int F, int T, int sqrt_mode, float eps,
+                                              float* out, float* normed, void* workspace, size_t workspace_bytes, void* stream) {
+    FsnCallScope scope(stream);
+    FSN_REQUIRE(mag && frames && out && normed && workspace, "NULL pointer argument");
+    FSN_REQUIRE(B >= 1 && F >= 2 && T >= 1 && (sqrt_mode == 0 || sqrt_mode == 1) && eps > 0.f,
+                "improved front (ragged): bad arguments [%d, %d, %d], mode %d", B, F, T, sqrt_mode);
+    if (workspace_bytes < fsn_improved_front_norm_ragged_workspace_bytes(B, F, T)) {
+        fsn_set_error("improved front (ragged): workspace too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long n = (long)B * (F - 1) * T;
+    const long g = (n + 255) / 256;
+    hipLaunchKernelGGL(improved_front_ragged_kernel, dim3((unsigned)(g < 4096 ? g : 4096)), dim3(256), 0, s, mag, frames, out, B, F, T,
+                       sqrt_mode);
+    FSN_TRY_LAUNCH("improved_front_ragged_kernel");
+    const NormDims d = norm_dims(FSN_NORM_OFFLINE_LAPLACE, B, 1, F - 1, T);  // the workspace layout of fsn_norm
+    double* s1 = static_cast<double*>(workspace);
+    double* s2 = s1 + (size_t)d.parts * d.R * T;
+    float* shift = reinterpret_cast<float*>(s2 + (size_t)d.parts * d.R * T);
+    float* den = shift + d.R * T;
+    for (long r0 = 0; r0 < d.R; r0 += 65535) {
+        const long nr = d.R - r0 < 65535 ? d.R - r0 : 65535;
+        hipLaunchKernelGGL(norm_frame_sums_kernel, dim3((unsigned)((T + 63) / 64), (unsigned)nr, (unsigned)d.parts), dim3(256), 0, s,
+                           out + r0 * (long)d.Fr * T, s1 + r0 * T, s2 + r0 * T, d.Fr, T, 0, d.R, d.f_per_part);
+    }
+    FSN_TRY_LAUNCH("norm_frame_sums_kernel");
+    hipLaunchKernelGGL(norm_offline_laplace_ragged_kernel, dim3((unsigned)d.R), dim3(64), 0, s, s1, frames, den, (int)d.R, d.Fr, T, eps,
+                       d.parts);
+    FSN_TRY_LAUNCH("norm_offline_laplace_ragged_kernel");
+    const long rows = (long)B * (F - 1);
+    const unsigned gy = (unsigned)(rows < 32768 ? rows : 32768);
+    hipLaunchKernelGGL(norm_apply_kernel, dim3((unsigned)((T + 255) / 256), gy), dim3(256), 0, s, out, normed, shift, den, rows, T, d.Fr,
+                       0);
     return fsn_check_launch("norm_apply_kernel");
 }

@@ -12,6 +12,11 @@
 //      of the unfolded tensor is a multiplicity-weighted sum of row sums (exact in fp64, rounded once like fsn_norm);
 //   3. out[t][b units_loc + u][col] = x[b][bin(u, col)][t] / (mu[b] + eps), time-major with zero padding, which is the
 //      layout the LSTM entries take (fsn_lstm2_forward, fsn_lstm2_forward_multi): a transposing gather through LDS.
+//
+// Ragged batches (kRagged, fsn_improved_section_input_ragged): utterance b has frames[b] = T_b of the T frames.  Past a
+// row's end the full-band output is NOT zero (an LSTM turns zero input into its biases' response), so the row sums stop at
+// T_b, the count is units x columns x T_b, and the gathered output is zero from T_b on.  With T_b = T every sum meets its
+// terms in the rectangular order: the same bits.
 #include "fsn_common.h"
 
 namespace {
@@ -24,7 +29,13 @@ struct SectionArgs {
     int sc, sn, fc, fn;          // centre / neighbour bins of the noisy and of the full-band window
     int u_lo, u_hi;              // units produced by this call (frequency-axis shard)
     float eps;
+    const int* frames;           // [B] frame counts of a ragged batch (kRagged kernels only)
 };
+// frames of utterance b, clamped to [1, T] whatever the array holds
+__device__ __forceinline__ int section_frames(const int* frames, int b, int T) {
+    const int t = frames[b];
+    return t < 1 ? 1 : (t > T ? T : t);
+}
 
 __device__ __forceinline__ int reflect_bin(int j, int F) {
     j = j < 0 ? -j : j;
@@ -42,14 +53,17 @@ __device__ __forceinline__ int section_bin(const SectionArgs& a, int u, int col,
 }
 
 // S[b * F + f] = sum_t x[b][f][t] (fp64), one wave per row; rows of noisy first, then of fb
+template <bool kRagged>
 __global__ __launch_bounds__(256) void section_rowsum_kernel(const float* __restrict__ noisy, const float* __restrict__ fb,
-                                                             double* __restrict__ S, long rows, int T) {
+                                                             double* __restrict__ S, long rows, int T, int F,
+                                                             const int* __restrict__ frames) {
     const int lane = threadIdx.x & 63;
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= 2 * rows) return;
     const float* p = (r < rows ? noisy + r * T : fb + (r - rows) * T);
+    const int Tb = kRagged ? section_frames(frames, (int)((r < rows ? r : r - rows) / F), T) : T;
     double s = 0.0;
-    for (int t = lane; t < T; t += 64) s += (double)p[t];
+    for (int t = lane; t < Tb; t += 64) s += (double)p[t];
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
     if (lane == 0) S[r] = s;
@@ -57,6 +71,7 @@ __global__ __launch_bounds__(256) void section_rowsum_kernel(const float* __rest
 
 // den[b] = float(sum / count) + eps: one workgroup per utterance, the (unit, column) pairs strided over its threads,
 // partial sums met in a fixed order
+template <bool kRagged>
 __global__ __launch_bounds__(256) void section_mean_kernel(const SectionArgs a, const double* __restrict__ S,
                                                            float* __restrict__ den) {
     __shared__ double red[256];
@@ -75,13 +90,14 @@ __global__ __launch_bounds__(256) void section_mean_kernel(const SectionArgs a, 
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const double n = (double)a.units * W * a.T;
+        const double n = (double)a.units * W * (kRagged ? section_frames(a.frames, b, a.T) : a.T);
         den[b] = (float)(red[0] / n) + a.eps;
     }
 }
 
 // out[t][row][col], row = b units_loc + (u - u_lo) < rows_valid, col < W: the gathered value / den[b]; zero elsewhere
 // (rows up to Np, columns up to ldo).  A workgroup = one row x 64 frames: reads run along t, writes along col.
+template <bool kRagged>
 __global__ __launch_bounds__(256) void section_gather_kernel(const SectionArgs a, const float* __restrict__ den,
                                                              float* __restrict__ out, int Np, int ldo) {
     extern __shared__ float tile[];  // [64][ldo + 1]
@@ -94,11 +110,12 @@ __global__ __launch_bounds__(256) void section_gather_kernel(const SectionArgs a
         const int b = row / uloc, u = a.u_lo + row % uloc;
         const float d = den[b];
         const int t = t0 + lane;
+        const int Tb = kRagged ? section_frames(a.frames, b, a.T) : a.T;
         for (int col = wave; col < W; col += 4) {
             int src;
             const int bin = section_bin(a, u, col, src);
             const float* p = (src ? a.fb : a.noisy) + ((long)b * a.F + bin) * a.T;
-            tile[lane * pitch + col] = t < a.T ? p[t] / d : 0.f;
+            tile[lane * pitch + col] = t < Tb ? p[t] / d : 0.f;
         }
     }
     __syncthreads();
@@ -117,7 +134,7 @@ size_t fsn_section_input_workspace_floats(int B, int F) {
 
 int fsn_launch_section_input(const float* noisy, const float* fb, int B, int F, int T, int lower, int units, int sc, int sn,
                              int fc, int fn, int u_lo, int u_hi, float eps, float* out, int Np, int ldo, void* workspace,
-                             hipStream_t s) {
+                             hipStream_t s, const int* frames) {
     SectionArgs a{};
     a.noisy = noisy;
     a.fb = fb;
@@ -126,15 +143,25 @@ int fsn_launch_section_input(const float* noisy, const float* fb, int B, int F, 
     a.sc = sc, a.sn = sn, a.fc = fc, a.fn = fn;
     a.u_lo = u_lo, a.u_hi = u_hi;
     a.eps = eps;
+    a.frames = frames;
     double* S = static_cast<double*>(workspace);
     float* den = reinterpret_cast<float*>(S + (size_t)2 * B * F);
     const long rows = (long)B * F;
-    hipLaunchKernelGGL(section_rowsum_kernel, dim3((unsigned)((2 * rows + 3) / 4)), dim3(256), 0, s, noisy, fb, S, rows, T);
+    const dim3 sum_grid((unsigned)((2 * rows + 3) / 4)), gather_grid((unsigned)((T + 63) / 64), (unsigned)Np);
+    const size_t lds = (size_t)64 * (ldo + 1) * sizeof(float);  // at most 64 x 241 floats: below the 64 KB a launch gets unasked
+    if (frames) {
+        hipLaunchKernelGGL(section_rowsum_kernel<true>, sum_grid, dim3(256), 0, s, noisy, fb, S, rows, T, F, frames);
+        FSN_TRY_LAUNCH("section_rowsum_kernel");
+        hipLaunchKernelGGL(section_mean_kernel<true>, dim3((unsigned)B), dim3(256), 0, s, a, S, den);
+        FSN_TRY_LAUNCH("section_mean_kernel");
+        hipLaunchKernelGGL(section_gather_kernel<true>, gather_grid, dim3(256), lds, s, a, den, out, Np, ldo);
+        return fsn_check_launch("section_gather_kernel");
+    }
+    hipLaunchKernelGGL(section_rowsum_kernel<false>, sum_grid, dim3(256), 0, s, noisy, fb, S, rows, T, F, nullptr);
     FSN_TRY_LAUNCH("section_rowsum_kernel");
-    hipLaunchKernelGGL(section_mean_kernel, dim3((unsigned)B), dim3(256), 0, s, a, S, den);
+    hipLaunchKernelGGL(section_mean_kernel<false>, dim3((unsigned)B), dim3(256), 0, s, a, S, den);
     FSN_TRY_LAUNCH("section_mean_kernel");
-    const size_t lds = (size_t)64 * (ldo + 1) * sizeof(float);
-    hipLaunchKernelGGL(section_gather_kernel, dim3((unsigned)((T + 63) / 64), (unsigned)Np), dim3(256), lds, s, a, den, out, Np, ldo);
+    hipLaunchKernelGGL(section_gather_kernel<false>, gather_grid, dim3(256), lds, s, a, den, out, Np, ldo);
     return fsn_check_launch("section_gather_kernel");
 }
 

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 from torch.nn import functional
 
-from .acoustics.feature import istft, stft
+from .acoustics.feature import istft, istft_ragged, stft, stft_ragged
 from .base_model import _hip_norm
 from .sequence_model import SequenceModel as _SequenceModel
 
@@ -172,11 +172,13 @@ class SubbandModel(BaseModel):
             sb_model_input = sb_model_input[:, lo:hi].contiguous()
         return sb_model_input
 
-    def _section_prepared(self, noisy_input, fb_output, sb_idx, units=None):
+    def _section_prepared(self, noisy_input, fb_output, sb_idx, units=None, frames=None):
         """The same input as ``_section_input``, written by fsn_improved_section_input straight into the layout the LSTM
         entries take - (h [T, Np, Ip] time-major, zero-padded, rows) - without forming the unfolded tensor: three launches
         instead of nine per section.  Inference on the GPU with the offline Laplace norm (the model's default); None when
-        that does not apply (the caller then takes ``_section_input``) or when this rank owns no unit of the section."""
+        that does not apply (the caller then takes ``_section_input``) or when this rank owns no unit of the section.
+        ``frames`` (device int32 [B]): a ragged batch through fsn_improved_section_input_ragged - row b's statistic over
+        its own frames, zeros from there on."""
         from . import _lib
         from .sequence_model import _round_up
         if (self.norm_type != "offline_laplace_norm" or torch.is_grad_enabled() or not noisy_input.is_cuda
@@ -202,10 +204,22 @@ class SubbandModel(BaseModel):
         h = torch.empty((T, Np, Ip), dtype=torch.float32, device=x.device)
         L = _lib.lib()
         ws = _lib.workspace(L.fsn_improved_section_input_workspace_bytes(B, F), x.device)
-        _lib.check(L.fsn_improved_section_input(
-            _lib.dev_ptr(x, "noisy"), _lib.dev_ptr(f, "fb_output"), B, F, T, lower, upper, sc, sn, fc, fn, lo, hi, EPSILON,
-            _lib.dev_ptr(h), Np, Ip, ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device)))
+        tail = (B, F, T, lower, upper, sc, sn, fc, fn, lo, hi, EPSILON, _lib.dev_ptr(h), Np, Ip, ws.data_ptr(), ws.numel(),
+                _lib.stream_ptr(x.device))
+        if frames is None:
+            _lib.check(L.fsn_improved_section_input(_lib.dev_ptr(x, "noisy"), _lib.dev_ptr(f, "fb_output"), *tail))
+        else:
+            _lib.check(L.fsn_improved_section_input_ragged(_lib.dev_ptr(x, "noisy"), _lib.dev_ptr(f, "fb_output"),
+                                                           frames.data_ptr(), *tail))
         return h, rows
+
+    def _prepared_or_raise(self, noisy_input, fb_output, sb_idx, units, frames):
+        """``_section_prepared`` of a ragged batch: there is no ragged form of the unfolded tensor to fall back to."""
+        p = self._section_prepared(noisy_input, fb_output, sb_idx, units, frames)
+        if p is None:
+            raise RuntimeError(f"section {sb_idx}: a ragged batch needs fsn_improved_section_input_ragged (offline Laplace norm, "
+                               "a window of at most 240 columns); Model.forward runs such configurations row by row")
+        return p
 
     @staticmethod
     def _wrap_output(o, B, n_units):
@@ -221,13 +235,14 @@ class SubbandModel(BaseModel):
             return noisy_input.new_zeros((noisy_input.size(0), 2, 0, noisy_input.size(-1)))
         return self.sb_models[sb_idx](sb_model_input)
 
-    def _run_sections(self, noisy_input, fb_output, units, rows_out=False):
+    def _run_sections(self, noisy_input, fb_output, units, rows_out=False, frames=None):
         """All sections, ``units[i]`` = None or the unit range of section i -> list of [B, 2, n_i c_i, T]; ``rows_out``
         (inference on prepared inputs only): the sections' outputs as their output layers wrote them, [T, Np_i, 2 c_i]
-        time-major - what fsn_improved_mask_apply takes."""
+        time-major - what fsn_improved_mask_apply takes.  ``frames`` (device int32 [B], inference on the GPU only): a ragged
+        batch - both plans below prepare their inputs with it; the recurrences are causal and run every row to T."""
         num = len(self.sb_models)
         if torch.is_grad_enabled() or not noisy_input.is_cuda:
-            assert not rows_out
+            assert not rows_out and frames is None
             return [self._section(noisy_input, fb_output, i, units[i]) for i in range(num)]
         # inference: the sections are independent two-layer stacks over the same frames.  When together they fill the
         # chip's workgroup sets (batches around 32 at 48 kHz) they run as ONE persistent launch of the group kernel with
@@ -242,6 +257,9 @@ class SubbandModel(BaseModel):
         if live and multi_plan([self.sb_models[i] for i in live], [(B * span[i], widths[i], T) for i in live]):
             prepared = []
             for i in live:
+                if frames is not None:
+                    prepared.append(self._prepared_or_raise(noisy_input, fb_output, i, units[i], frames))
+                    continue
                 p = self._section_prepared(noisy_input, fb_output, i, units[i])
                 if p is None:  # another norm: through the unfolded tensor
                     x = self._section_input(noisy_input, fb_output, i, units[i]).reshape(B * span[i], widths[i], T)
@@ -280,6 +298,9 @@ class SubbandModel(BaseModel):
             with torch.cuda.stream(stream_of[i]):
                 if span[i] <= 0:
                     inputs[i] = None
+                    continue
+                if frames is not None:
+                    inputs[i] = self._prepared_or_raise(noisy_input, fb_output, i, units[i], frames)
                     continue
                 inputs[i] = self._section_prepared(noisy_input, fb_output, i, units[i])
                 if inputs[i] is None:  # wider than fsn_improved_section_input's tile / another norm: through the unfolded tensor
@@ -403,11 +424,17 @@ class Model(BaseModel):
                 and all(m.cell == "LSTM" and m.output_size for m in sb.sb_models)
                 and max(2 * c for c in sb.sb_num_center_freqs) <= 480)
 
-    def _forward_kernels(self, y, mag, real, imag):
+    def _forward_kernels(self, y, mag, real, imag, lens=None):
         """model.py:541-591 with every step between the transforms and the LSTM / Linear entries on kernels of the library:
         fsn_improved_front (mag ** fdrc, last bin left out), fsn_norm, fsn_bft_to_rows / fsn_rows_to_bft around the
         full-band model, fsn_improved_section_input per section, fsn_improved_mask_apply (the sections' outputs into the
-        two masked planes, last bin zero).  Bit-identical to the tensor-algebra forward (tests/test_gpu_family.py)."""
+        two masked planes, last bin zero).  Bit-identical to the tensor-algebra forward (tests/test_gpu_family.py).
+
+        ``lens`` = (samples, frames) of every row, device int32 [B] each, with mag / real / imag from ``stft_ragged``: a
+        ragged batch.  The front and the norm
+        become fsn_improved_front_norm_ragged, the sections' inputs fsn_improved_section_input_ragged and the way back
+        fsn_istft_ragged; every block's input is zero past a row's end (never the caller's padding), the blocks run every
+        row to T, and what they produce past a row's end is finite and never read by the iSTFT."""
         import ctypes
         from . import _lib
         from .sequence_model import from_rows, to_rows
@@ -417,12 +444,21 @@ class Model(BaseModel):
         B, F, T = mag.shape
         Fm = F - 1
         noisy_mag = torch.empty((B, 1, Fm, T), dtype=torch.float32, device=dev)
-        _lib.check(L.fsn_improved_front(_lib.dev_ptr(mag, "mag"), B, F, T, 1 if self.fdrc == 0.5 else 0, _lib.dev_ptr(noisy_mag), st))
-        fb_in = self.norm(noisy_mag).reshape(B, Fm, T)                                  # fsn_norm (contiguous: no copy)
+        frames = None
+        if lens is None:
+            _lib.check(L.fsn_improved_front(_lib.dev_ptr(mag, "mag"), B, F, T, 1 if self.fdrc == 0.5 else 0, _lib.dev_ptr(noisy_mag), st))
+            fb_in = self.norm(noisy_mag).reshape(B, Fm, T)                              # fsn_norm (contiguous: no copy)
+        else:
+            lens, frames = lens
+            fb_in = torch.empty((B, Fm, T), dtype=torch.float32, device=dev)
+            ws = _lib.workspace(L.fsn_improved_front_norm_ragged_workspace_bytes(B, F, T), dev)
+            _lib.check(L.fsn_improved_front_norm_ragged(_lib.dev_ptr(mag, "mag"), frames.data_ptr(), B, F, T,
+                                                        1 if self.fdrc == 0.5 else 0, EPSILON, _lib.dev_ptr(noisy_mag),
+                                                        _lib.dev_ptr(fb_in), ws.data_ptr(), ws.numel(), st))
         fb_rows = self.fb_model.forward_time_major(to_rows(fb_in), B, rows_out=True)     # [T, Np, Fm]
         fb_output = from_rows(fb_rows, B).reshape(B, 1, Fm, T)
         sb = self.sb_model
-        outs = sb._run_sections(noisy_mag, fb_output, [None] * len(sb.sb_models), rows_out=True)
+        outs = sb._run_sections(noisy_mag, fb_output, [None] * len(sb.sb_models), rows_out=True, frames=frames)
         secs = (_lib.MaskSection * len(outs))()
         keep, n = [], 0
         n_units = sb.num_units(Fm)
@@ -440,18 +476,62 @@ class Model(BaseModel):
         er, ei = torch.empty_like(real), torch.empty_like(imag)
         _lib.check(L.fsn_improved_mask_apply(n, ctypes.byref(secs), _lib.dev_ptr(real, "real"), _lib.dev_ptr(imag, "imag"), B, F, T,
                                              _lib.dev_ptr(er), _lib.dev_ptr(ei), st))
-        enhanced = istft((er, ei), self.n_fft, self.hop_length, self.win_length, length=y.size(-1), input_type="real_imag")
+        if lens is None:
+            enhanced = istft((er, ei), self.n_fft, self.hop_length, self.win_length, length=y.size(-1), input_type="real_imag")
+        else:
+            enhanced = istft_ragged((er, ei), lens, self.n_fft, self.hop_length, self.win_length, length=y.size(-1))
         return enhanced.unsqueeze(1)
 
-    def forward(self, y, unit_group=None):
+    def _ragged_on_kernels(self, y, unit_group):
+        """Whether a ragged batch takes ONE pass through the library's ragged entries: the configuration of
+        ``_glue_on_kernels`` with every section's window inside fsn_improved_section_input's tile (240 columns, 65535 rows)."""
+        from .sequence_model import _round_up
+        sb = self.sb_model
+        widths = [(sc + 2 * sn) + (fc + 2 * fn) for sc, sn, fc, fn in
+                  zip(sb.sb_num_center_freqs, sb.sb_num_neighbor_freqs, sb.fb_num_center_freqs, sb.fb_num_neighbor_freqs)]
+        n_units = sb.num_units(self.fb_model.input_size)
+        bands = [sb._band(i, self.fb_model.input_size) for i in range(len(sb.sb_models))]
+        return (self._glue_on_kernels(y, unit_group) and self.hop_length < self.n_fft and self.win_length == self.n_fft
+                and max(_round_up(w, 16) for w in widths) <= 240 and _round_up(y.size(0) * max(n_units), 16) <= 65535
+                and all((hi - lo) % sc == 0 and (hi - lo) % fc == 0 and (hi - lo) // sc == (hi - lo) // fc
+                        for (lo, hi), sc, fc in zip(bands, sb.sb_num_center_freqs, sb.fb_num_center_freqs)))
+
+    def _forward_ragged(self, y, lens, unit_group):
+        """``forward(y, lengths=...)`` after validation: y [B, L], ``lens`` a list of B ints."""
+        B, L = y.shape
+        if y.is_cuda and not torch.is_grad_enabled() and self._ragged_on_kernels(y, unit_group):
+            c = self._persistent_chunk(B, 1 + L // self.hop_length)  # as forward: chunks that fit one persistent launch
+            if c and B > c:
+                return torch.cat([self._forward_ragged(y[i:i + c], lens[i:i + c], None) for i in range(0, B, c)], dim=0)
+            from .ragged import frames as n_frames
+            y = y.contiguous()
+            # samples and frames of every row in one upload: the kernels read them on the device
+            both = torch.tensor([lens, [n_frames(n, self.hop_length) for n in lens]], dtype=torch.int32, device=y.device)
+            mag, real, imag = stft_ragged(y, both[0], self.n_fft, self.hop_length, self.win_length)
+            return self._forward_kernels(y, mag, real, imag, (both[0], both[1]))
+        # no single-call form (another norm, GRU, another fdrc, a section beyond the kernel's tile, unit_group, autograd,
+        # the CPU): each row alone, padded back with zeros - correct, not faster
+        rows = [functional.pad(self.forward(y[b:b + 1, :n], unit_group=unit_group), (0, L - n)) for b, n in enumerate(lens)]
+        return torch.cat(rows, dim=0)
+
+    def forward(self, y, unit_group=None, lengths=None):
         """model.py:541-591: y [B, L] or [B, 1, L] -> enhanced [B, 1, L].  ``unit_group``: shard the sub-band units
         over that process group (every rank gets the same ``y`` and returns the same result; for fewer utterances
-        than GPUs - otherwise shard the utterances, ``parallel.enhance_sharded``)."""
+        than GPUs - otherwise shard the utterances, ``parallel.enhance_sharded``).
+
+        ``lengths`` (a sequence of ints or a 1-D integer tensor, one per row, each in ``(n_fft // 2, L]``): a ragged
+        batch - row b holds an utterance of ``lengths[b]`` samples, the rest of the row is never read.  Row b of the result
+        is what ``forward(y[b:b + 1, :lengths[b]])`` gives (within fp32 rounding), zero from ``lengths[b]`` on: its own
+        reflection in the STFT, its own offline norms, its own iSTFT length.  On the configuration ``_glue_on_kernels``
+        accepts this is one pass through the library's ragged entries; anything else runs row by row."""
         ndim = y.dim()
         assert ndim in (2, 3), "Input must be 2D (B, T) or 3D tensor (B, 1, T)"
         if ndim == 3:
             assert y.size(1) == 1, "Input must be 2D (B, T) or 3D tensor (B, 1, T)"
             y = y.squeeze(1)
+        if lengths is not None:
+            from .ragged import check_lengths
+            return self._forward_ragged(y, check_lengths(lengths, y.size(0), y.size(-1), n_fft=self.n_fft), unit_group)
         if unit_group is None and y.is_cuda and not torch.is_grad_enabled():
             # the model has no cross-utterance term: a batch beyond what ONE persistent launch of the band sections holds
             # (32 utterances at 48 kHz) runs as chunks that do fit - 64 utterances: 55 ms as wavefronts, 2 x 21.5 as chunks

@@ -95,6 +95,24 @@ int fsn_istft(const float* real, const float* imag, int B, int T, int n_fft, int
 int fsn_stft_ragged(const float* y, const int* lengths, int B, int L_max, int n_fft, int hop, int win_length,
                     const float* window, float* real, float* imag, float* mag, void* stream);
 
+/* fsn_stft_ragged at every shape fsn_stft takes (improved_fullsubnet/model.py:550-557 runs 512 / 128 and 960 / 480; feature.py:9-50):
+ * same arguments and result - row b is the STFT of y[b][0 .. lengths[b]) alone, reflected at its own end, in its first
+ * T_b = 1 + lengths[b] / hop frames; frames past T_b are exact zeros and cost a store, not a transform; samples past
+ * lengths[b] are never read (values are clamped to [n_fft/2 + 1, L_max]).  512 / 256 runs on the radix-8 kernels' lengths path
+ * (fsn_stft_ragged), any other shape on the ragged forms of the direct-DFT kernels - two-level where n_fft splits, the plain
+ * direct form where it is twice a prime - with fsn_stft's own arithmetic: a row equals fsn_stft of that row alone bit for bit. */
+int fsn_stft_ragged_generic(const float* y, const int* lengths, int B, int L_max, int n_fft, int hop, int win_length,
+                            const float* window, float* real, float* imag, float* mag, void* stream);
+
+/* fsn_istft on a RAGGED batch (feature.py:53-91; improved_fullsubnet/model.py:582-589): real/imag [B, F, T] -> y [B, length],
+ * lengths (device, [B]).  Row b is the iSTFT of its own first T_b = 1 + lengths[b] / hop frames at its own length - the same
+ * envelope and trim arithmetic as fsn_istft - and zeros from lengths[b] on; frames t >= T_b of real / imag are never read.
+ * length is the longest row and T = 1 + length / hop.  Equal lengths give fsn_istft's bits.  Every shape fsn_istft takes;
+ * workspace >= fsn_istft_ragged_workspace_bytes(B, T, n_fft) (0: unsupported). */
+size_t fsn_istft_ragged_workspace_bytes(int B, int T, int n_fft);
+int fsn_istft_ragged(const float* real, const float* imag, const int* lengths, int B, int T, int n_fft, int hop, int win_length,
+                     const float* window, int length, float* y, void* workspace, size_t workspace_bytes, void* stream);
+
 /* inferencer.py:134-141 as one call on a model's COMPRESSED cIRM: decompress_cIRM (K = 10, limit = 9.9), the complex
  * mask on the noisy spectrum and the iSTFT, with the fp32 products of the reference's tensor algebra.
  * crm [B, 2, F, T] as a model's forward returns it (read in place); real/imag [B, F, T] as fsn_stft writes them;
@@ -350,6 +368,16 @@ int fsn_improved_section_input(const float* noisy, const float* fb_out, int B, i
                                float eps, float* out, int Np, int ldo, void* workspace, size_t workspace_bytes,
                                void* stream);
 
+/* fsn_improved_section_input on a RAGGED batch: frames (device, [B]) holds utterance b's frame count T_b in [1, T].  The
+ * section's statistic (model.py:124-150 on the unfolded input of model.py:402-440) comes from the frames t < T_b only - past a
+ * row's end the full-band output is an LSTM's response to zero input, not zero - with the count units x columns x T_b; the
+ * gathered output is zero for t >= T_b, and neither input is read there.  Same tile limits and workspace as the rectangular
+ * entry; frames[b] = T for every b gives its bits. */
+int fsn_improved_section_input_ragged(const float* noisy, const float* fb_out, const int* frames, int B, int F, int T, int lower,
+                                      int upper, int sb_center, int sb_neighbor, int fb_center, int fb_neighbor, int unit_lo,
+                                      int unit_hi, float eps, float* out, int Np, int ldo, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+
 /* The tensor glue AROUND the models of the composed families (round 5; section_kernels.hip), all bit-identical to the tensor
  * algebra it replaces:
  * fsn_improved_front      improved_fullsubnet/model.py:565-566: mag [B][F][T] -> out [B][F - 1][T] = mag ** fdrc without the
@@ -371,6 +399,15 @@ int fsn_bft_to_rows(const float* x, int B, int F, int T, float* h, int Np, int I
 int fsn_rows_to_bft(const float* o, int T, int Np, int ld, int B, int O, float* y, void* stream);
 int fsn_improved_mask_apply(int n, const fsn_mask_section* sections, const float* real, const float* imag, int B, int F, int T,
                             float* er, float* ei, void* stream);
+/* fsn_improved_front and the offline Laplace norm of the full-band input (improved_fullsubnet/model.py:565-567, norm :124-150)
+ * on a RAGGED batch, as ONE fused entry: out [B][F - 1][T] = mag ** fdrc without the last bin for t < frames[b] and zero from
+ * there on (mag is not read past a row's end); normed = out / (mean over the (F - 1) x frames[b] entries of the row + eps), zero
+ * past the end as well.  frames: device, [B], values in [1, T].  The sums are fp64, rounded once, then the reference's fp32
+ * division, as fsn_norm does: frames[b] = T for every b gives the bits of fsn_improved_front followed by fsn_norm.
+ * workspace >= fsn_improved_front_norm_ragged_workspace_bytes(B, F, T). */
+size_t fsn_improved_front_norm_ragged_workspace_bytes(int B, int F, int T);
+int fsn_improved_front_norm_ragged(const float* mag, const int* frames, int B, int F, int T, int sqrt_mode, float eps, float* out,
+                                   float* normed, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Two stacked GRU layers of equal width (nn.GRU(num_layers = 2) of a SequenceModel, sequence_model.py:59-66; weights in nn.GRU's
  * layout: w_ih [3H][I], w_hh [3H][H], biases [3H], gate rows r, z, n) with few rows - the full-band model of a GRU FullSubNet -
