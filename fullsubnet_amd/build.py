@@ -3,6 +3,7 @@
 Every translation unit is compiled to its own object under csrc/_obj/ (only the stale ones, in parallel), then linked.
 """
 import concurrent.futures
+import glob
 import os
 import subprocess
 import sys
@@ -11,8 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libfsn_hip.so")
-HEADERS = [os.path.join(CSRC, "fsn_common.h"), os.path.join(CSRC, "fsn_api_internal.h"), os.path.join(CSRC, "lstm_cell.h"),
-           os.path.join(HERE, "..", "include", "fsn_hip.h")]
+# every header a translation unit may include: a forgotten one means stale objects
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "fsn_hip.h")]
 EXPORTS = os.path.join(CSRC, "fsn_exports.map")  # the library exports the fsn_* entries of fsn_hip.h and nothing else
 SOURCES = ["fft_kernels.hip", "dft_kernels.hip", "elementwise_kernels.hip", "gemm_kernels.hip",
            "gemm_f16x3_kernels.hip", "lstm_rec_kernels.hip", "lstm_rec_in_kernels.hip", "lstm_rec_x_kernels.hip",
@@ -66,7 +67,7 @@ def build(force=False, verbose=True):
             print(" ".join(cmd), file=sys.stderr)
         subprocess.run(cmd, check=True)
 
-    with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(len(todo), os.cpu_count() or 1))) as pool:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(len(todo), os.cpu_count() or 1, 16))) as pool:
         list(pool.map(compile_one, todo))
     cmd = [hipcc] + LINK_FLAGS + [_obj(s) for s in _sources()] + ["-o", LIB]
     if verbose:

@@ -15,7 +15,8 @@
 //     (the next step's flags arrived while it was still multiplying) - 9.3 us per step; as a stage of its own X follows
 //     L1 by one step and L0 follows X, and a step is one product long;
 //   - the gate-gradient buffers dgates[t] ([16][2048] per step; the weight-gradient GEMMs read them afterwards) are the
-//     exchange buffers: write-through stores, drain, flag copies; one wave polls; sc1 loads; nothing is reused;
+//     exchange buffers: write-through stores, drain, flag copies; one wave polls; sc1 loads (the chain family of
+//     persist_sync.h: fsn_chain_wait_words, fsn_publish_copies); nothing is reused;
 //   - the saved activations of a step are requested AFTER the A fragments (loads return in order: requested first they
 //     would hold the MFMAs up for an HBM latency);
 //   - several row tiles (round 6): the rows are independent sequences sharing the weights.  A workgroup forms its product
@@ -24,7 +25,7 @@
 //     derivative, write-through stores), and the step is handed on ONCE: one drain, one flag, one poll per step whatever
 //     the tile count (walking the tiles as separate chains inside a step - one hand-off each - was measured first: 11.4 ms
 //     for a 72-row two-layer stack's forward + backward against 9.4 ms step by step).
-#include "fsn_common.h"
+#include "persist_sync.h"
 
 namespace {
 
@@ -50,20 +51,6 @@ struct ChainBpttArgs {
     int N;                // rows of the buffers: 16 per tile
 };
 
-// wave 0: all 32 flags of a stage copy >= epoch and (optionally) one more flag >= its epoch; bounded
-__device__ __forceinline__ bool qwait(const unsigned* flags, unsigned epoch, const unsigned* one, unsigned one_epoch,
-                                      unsigned* status, unsigned long long ticks) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long t0 = 0;
-    for (unsigned spins = 0;; ++spins) {
-        unsigned v = ~0u, w = ~0u;
-        if (epoch > 0 && lane < QNW) v = __hip_atomic_load(flags + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (one && lane == 0) w = __hip_atomic_load(one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__all((int)(v >= epoch && w >= one_epoch))) return true;
-        if ((spins & 255u) == 255u && fsn_wait_give_up(status, spins, t0, ticks, 1u + epoch)) return false;
-    }
-}
-
 __global__ __launch_bounds__(256, 1) void fb_chain_bptt_kernel(const ChainBpttArgs a) {
     extern __shared__ f32x4 red[];           // partial sums of (wave, tile): [4][nt][64] (4 KB per row tile: the launch beside the
                                              // weight-gradient products' 144 KB workgroups needs the CU's last 16 KB)
@@ -88,8 +75,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_bptt_kernel(const ChainBpttAr
     };
     // rows [16 tile, 16 tile + 16) of step t of a [Tp][N][...] buffer as a buffer resource
     auto slab = [&](const float* p, int t, int width, int tile) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p) + ((size_t)t * nrows + (size_t)16 * tile) * width, 0,
-                                                 16 * width * 4, 0x00020000);
+        return fsn_buffer_rsrc(p + ((size_t)t * nrows + (size_t)16 * tile) * width, 16 * width * 4);
     };
     // this wave's A fragments of a tile of dgates[t] (row lr, k = 16 kc + 4 lq ..) by HALVES of its K quarter (QCW / 2 chunks =
     // 16 KB per wave in flight): sc1 loads; half s + 1 travels under half s' MFMAs (two register sets of 64)
@@ -100,20 +86,15 @@ __global__ __launch_bounds__(256, 1) void fb_chain_bptt_kernel(const ChainBpttAr
         const int q0 = wave * QCW + (stage & 1) * QHC;
 #pragma unroll
         for (int q = 0; q < QHC; ++q)
-            ar[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, a_off, (unsigned)((q0 + q) * 64), 16));
+            ar[q] = fsn_buffer_load<f32x4, FSN_CP_SC1>(r, a_off, (unsigned)((q0 + q) * 64));
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto publish = [&](unsigned* flags, unsigned epoch) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if ((int)threadIdx.x < QREP)
-            __hip_atomic_store(flags + (size_t)threadIdx.x * QNW + j, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    auto publish = [&](unsigned* flags, unsigned epoch) { fsn_publish_copies<QREP, QNW>(flags, j, epoch); };
     // element (row 4 lq + i, unit 16 j + lr) of a step's slabs: one lane offset, compile-time scalar offsets
     const unsigned voff_g = (unsigned)(((4 * lq) * QG + j * 16 + lr) * 4);
     const unsigned voff_h = (unsigned)(((4 * lq) * QH + j * 16 + lr) * 4);
     auto ldf = [&](const __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
+        return fsn_buffer_load<float>(r, voff, soff);
     };
     const float* gates = l1 ? a.gates1 : a.gates0;
     const float* cseq = l1 ? a.cseq1 : a.cseq0;
@@ -121,7 +102,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_bptt_kernel(const ChainBpttAr
     const unsigned dx_wave = (unsigned)(((size_t)j * 4 + wave) * 1024);  // this wave's partial tile inside a step of dx
     const unsigned dx_step = (unsigned)QNW * 4096u;
     auto rdx = [&](int tile) {  // dx of row tile `tile`: [Tp][QNW][4 waves][64][4]
-        return __builtin_amdgcn_make_buffer_rsrc(a.dx + (size_t)tile * Tp * QNW * 1024, 0, 0x7fffffff, 0x00020000);
+        return fsn_buffer_rsrc(a.dx + (size_t)tile * Tp * QNW * 1024);
     };
     float dc[QOWN][4];  // cell-state gradient of the tiles this wave finishes
 #pragma unroll
@@ -157,10 +138,10 @@ __global__ __launch_bounds__(256, 1) void fb_chain_bptt_kernel(const ChainBpttAr
             const float d_o = dh[i] * tc;
             const float dct = dcs[i] + dh[i] * og * (1.f - tc * tc);
             const unsigned so = (unsigned)(i * QG * 4);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dct * gg * ig * (1.f - ig)), ro, voff_g, so, 16);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dct * e_cp[i] * fg * (1.f - fg)), ro, voff_g, so + QH * 4, 16);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dct * ig * (1.f - gg * gg)), ro, voff_g, so + 2 * QH * 4, 16);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, d_o * og * (1.f - og)), ro, voff_g, so + 3 * QH * 4, 16);
+            fsn_buffer_store<FSN_CP_SC1>(ro, voff_g, so, dct * gg * ig * (1.f - ig));
+            fsn_buffer_store<FSN_CP_SC1>(ro, voff_g, so + QH * 4, dct * e_cp[i] * fg * (1.f - fg));
+            fsn_buffer_store<FSN_CP_SC1>(ro, voff_g, so + 2 * QH * 4, dct * ig * (1.f - gg * gg));
+            fsn_buffer_store<FSN_CP_SC1>(ro, voff_g, so + 3 * QH * 4, d_o * og * (1.f - og));
             dcs[i] = dct * fg;
         }
     };
@@ -212,7 +193,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_bptt_kernel(const ChainBpttAr
             for (int k = 0; k < QMAXT; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
             float e_g[4][4], e_ct[4], e_cp[4], e_dh[4];
             if (t < Tp - 1) {
-                if (wave == 0) (void)qwait(fl1 + rep * QNW, done, nullptr, 0, a.status, a.spin_ticks);
+                if (wave == 0) (void)fsn_chain_wait_words<QNW>(fl1 + rep * QNW, done, nullptr, 0, a.status, a.spin_ticks);
                 __syncthreads();
                 load_half(ah0, a.dg1, t + 1, 0);
             }
@@ -228,7 +209,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_bptt_kernel(const ChainBpttAr
         // are drained
         for (int t = Tp - 1; t >= 0; --t) {
             const unsigned epoch = (unsigned)(Tp - t);
-            if (wave == 0) (void)qwait(fl1 + rep * QNW, epoch, nullptr, 0, a.status, a.spin_ticks);
+            if (wave == 0) (void)fsn_chain_wait_words<QNW>(fl1 + rep * QNW, epoch, nullptr, 0, a.status, a.spin_ticks);
             __syncthreads();
             f32x4 accx[QMAXT];
 #pragma unroll
@@ -250,12 +231,12 @@ __global__ __launch_bounds__(256, 1) void fb_chain_bptt_kernel(const ChainBpttAr
     for (int t = Tp - 1; t >= 0; --t) {
         const unsigned done = (unsigned)(Tp - 1 - t);
         // dx_t: stored by X workgroup j, complete at its epoch Tp - t = done + 1
-        if (wave == 0) (void)qwait(fl0 + rep * QNW, done, flx + rep * QNW + j, done + 1, a.status, a.spin_ticks);
+        if (wave == 0) (void)fsn_chain_wait_words<QNW>(fl0 + rep * QNW, done, flx + rep * QNW + j, done + 1, a.status, a.spin_ticks);
         __syncthreads();
         f32x4 acc[QMAXT];
 #pragma unroll
         for (int k = 0; k < QMAXT; ++k)
-            acc[k] = k < nt ? __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rdx(k), lane16, (unsigned)t * dx_step + dx_wave, 16))
+            acc[k] = k < nt ? fsn_buffer_load<f32x4, FSN_CP_SC1>(rdx(k), lane16, (unsigned)t * dx_step + dx_wave)
                             : f32x4{0.f, 0.f, 0.f, 0.f};
         float e_g[4][4], e_ct[4], e_cp[4], e_dh[4];
         if (t < Tp - 1) load_half(ah0, a.dg0, t + 1, 0);

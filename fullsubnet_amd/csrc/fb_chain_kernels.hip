@@ -18,13 +18,14 @@
 //     partial tiles are summed in a fixed order through LDS;
 //   - h_t goes to per-step buffers in A-fragment order (a wave's K chunk is one contiguous 1 KB block) with the
 //     write-through / flag recipe of the CDNA guide (Guideline 16, R1: sc1 stores, every storing wave drains, ONE flag
-//     store per copy; one wave polls the 128 flags of the producing stage, barrier, sc1 loads).  No buffer is ever
+//     store per copy; one wave polls the 128 flags of the producing stage, barrier, sc1 loads: the chain family of
+//     persist_sync.h - fsn_chain_wait, fsn_publish_copies).  No buffer is ever
 //     reused, so there is no back-pressure and the dependence graph is acyclic: with all 256 workgroups resident the
 //     launch cannot deadlock; every spin is bounded anyway (status raised, never a hang; the host then turns the
 //     output into NaN, fsn_launch_poison_if).  The host serialises persistent launches of different streams
 //     (fsn_api.hip) so that two of them never share the CUs.  Up to 4095 steps (the reach of a buffer resource).
 // Measured with tools/probe_chain.hip (190 steps): see DESIGN.md 4.6.
-#include "fsn_common.h"
+#include "persist_sync.h"
 
 namespace {
 
@@ -53,29 +54,6 @@ struct ChainArgs {
     int Tp, RT, Npad;
 };
 
-// wave 0: all 128 flags of a stage >= epoch and (optionally) one more flag >= its epoch, both looked at in the same
-// round trip; bounded
-__device__ __forceinline__ bool chain_wait(const unsigned* flags, int nflags, unsigned epoch, const unsigned* one,
-                                           unsigned one_epoch, unsigned* status, unsigned long long ticks) {
-    const int lane = threadIdx.x & 63;
-    const unsigned long long* f = reinterpret_cast<const unsigned long long*>(flags) + lane;
-    unsigned long long t0 = 0;
-    for (unsigned spins = 0;; ++spins) {
-        unsigned long long v = ~0ull;
-        unsigned w = ~0u;
-        if (epoch > 0 && 2 * lane < nflags) v = __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (one && lane == 0) w = __hip_atomic_load(one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__all((int)((unsigned)v >= epoch && (unsigned)(v >> 32) >= epoch && w >= one_epoch))) return true;
-        if ((spins & 255u) == 255u && fsn_wait_give_up(status, spins, t0, ticks, 1u + epoch)) return false;
-    }
-}
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// 16-byte write-through store (sc1): whole 16-byte groups, never single dwords - a step of the chain publishes ~0.8 MB,
-// and as dword stores that was 200 k partial-line write transactions per step (measured: 2 us of a 9.6 us step)
-__device__ __forceinline__ void chain_store16(const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 16);  // aux 16 = sc1
-}
 // value of quad lane Q (lanes 4 k .. 4 k + 3 form a quad) in every lane of the quad
 template <int Q>
 __device__ __forceinline__ float quad_bcast(float v) {
@@ -114,9 +92,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
     unsigned* fl1 = a.flags + CREP * CFS;  // [CREP][CFS]
     const int rep = j % CREP;
 
-    const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(a.hx0, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(a.hx1, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(a.gx1, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r0 = fsn_buffer_rsrc(a.hx0), r1 = fsn_buffer_rsrc(a.hx1), rx = fsn_buffer_rsrc(a.gx1);
     const unsigned lane16 = (unsigned)lane * 16u;
 
     // weight slice of column tile (gate g, units 4 j .. 4 j + 3), K chunks kp CW .. kp CW + CW - 1, from the packed
@@ -131,7 +107,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
         const unsigned base = (unsigned)((((size_t)ts * RT + rt) * CKC + kp * CW) * 1024);
 #pragma unroll
         for (int q = 0; q < CW; ++q)
-            ar[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, lane16, base + q * 1024u, 16));
+            ar[q] = fsn_buffer_load<f32x4, FSN_CP_SC1>(r, lane16, base + q * 1024u);
         __builtin_amdgcn_sched_barrier(0);  // every request leaves before the first MFMA waits for one of them
     };
     auto mac = [&](f32x4 acc, const f32x4 (&ar)[CW], const f32x4 (&w)[CW]) -> f32x4 {
@@ -157,12 +133,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
         return acc;
     };
     // every wave drains its stores, then one flag store per copy
-    auto publish = [&](unsigned* flags, unsigned epoch) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if ((int)threadIdx.x < CREP)
-            __hip_atomic_store(flags + (size_t)threadIdx.x * CFS + j, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    auto publish = [&](unsigned* flags, unsigned epoch) { fsn_publish_copies<CREP, CFS>(flags, j, epoch); };
     // lane (u', lq) of a quad holds v[i] = x[row 4 lq + i][unit u']: 4 x 4 transpose inside the quad ->
     // x[row 4 lq + ul][units 0..3], one 16-byte group of a row-major (or A-fragment) buffer per lane
     auto quad_transpose = [&](const float (&v)[4]) -> f32x4 {
@@ -241,7 +212,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
             f32x4 acc = gxn;
             if (owner && t + 1 < Tp) gxn = *reinterpret_cast<const f32x4*>(gx0p + (size_t)(t + 1) * gx0_step);
             if (t > 0) {
-                if (wave == 0) (void)chain_wait(fl0 + rep * CFS, CNW, (unsigned)t, nullptr, 0, a.status, a.spin_ticks);
+                if (wave == 0) (void)fsn_chain_wait(fl0 + rep * CFS, CNW, (unsigned)t, nullptr, 0, a.status, a.spin_ticks);
                 __syncthreads();
                 if (active) load_a(ar, r0, t - 1);
             }
@@ -252,7 +223,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
                     const f32x4 hv = cell(acc, c, SAVE ? a.gates0 + (size_t)t * a.Npad * 4 * CH : nullptr,
                                           SAVE ? a.cseq0 + (size_t)t * a.Npad * CH : nullptr);
                     if (g == 0) {
-                        chain_store16(r0, hvoff, hsoff(t), hv);
+                        fsn_buffer_store<FSN_CP_SC1>(r0, hvoff, hsoff(t), hv);  // 16-byte write-through
                         if (SAVE) *reinterpret_cast<f32x4*>(a.hseq0 + ((size_t)t * a.Npad + rt * 16 + hrow) * CH + 4 * j) = hv;
                     }
                 }
@@ -281,11 +252,11 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
     for (int s = 0; s < Tp; ++s) {
         // h1_{s-1} of all workgroups, and the projection tile of step s from L0 workgroup j (complete at flag s + 3)
         if (wave == 0)
-            (void)chain_wait(fl1 + rep * CFS, CNW, (unsigned)s, fl0 + rep * CFS + j, (unsigned)s + 3, a.status, a.spin_ticks);
+            (void)fsn_chain_wait(fl1 + rep * CFS, CNW, (unsigned)s, fl0 + rep * CFS + j, (unsigned)s + 3, a.status, a.spin_ticks);
         __syncthreads();
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
         if (active) {
-            acc = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, lane16, (unsigned)s * gx1_step + gx1_wave, 16));
+            acc = fsn_buffer_load<f32x4, FSN_CP_SC1>(rx, lane16, (unsigned)s * gx1_step + gx1_wave);
             if (s > 0) {
                 load_a(ar, r1, s - 1);
                 acc = mac(acc, ar, whh);
@@ -296,7 +267,7 @@ __global__ __launch_bounds__(256, 1) void fb_chain_kernel(const ChainArgs a) {
             const f32x4 hv = cell(acc, c, SAVE ? a.gates1 + (size_t)s * a.Npad * 4 * CH : nullptr,
                                   SAVE ? a.cseq1 + (size_t)s * a.Npad * CH : nullptr);
             if (g == 0) {
-                chain_store16(r1, hvoff, hsoff(s), hv);
+                fsn_buffer_store<FSN_CP_SC1>(r1, hvoff, hsoff(s), hv);
                 *reinterpret_cast<f32x4*>(a.hseq1 + ((size_t)s * a.Npad + rt * 16 + hrow) * CH + 4 * j) = hv;
             }
         }

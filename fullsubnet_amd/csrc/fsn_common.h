@@ -102,15 +102,6 @@ template <>
 struct FsnWFrag<FSN_ARITH_BF16> {
     typedef fsn_u32x2 type;
 };
-// the lane's fragment at element offset `ofs` of the packed weight buffer behind resource r
-template <int AR>
-__device__ __forceinline__ typename FsnWFrag<AR>::type fsn_load_wfrag(const __amdgpu_buffer_rsrc_t r, unsigned lane,
-                                                                     unsigned ofs) {
-    if constexpr (AR == FSN_ARITH_F32)
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, lane * 16u, ofs * 4u, 0));
-    else
-        return __builtin_bit_cast(fsn_u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, lane * 8u, ofs * 2u, 0));
-}
 template <int AR>
 __device__ __forceinline__ typename FsnOperand<AR>::type fsn_wfrag_operand(const typename FsnWFrag<AR>::type w) {
     if constexpr (AR == FSN_ARITH_F32) return w;
@@ -471,19 +462,6 @@ void fsn_persist_admit(const void* kernel, int block_threads, unsigned grid);
     } while (0)
 unsigned* fsn_ctx_sticky();           // device-visible sticky status record {status, events} of the running call's stream
 
-#ifdef __HIPCC__
-// One 256-poll round of a bounded wait has passed: give up?  The first round only takes the time (t0), so that a wait
-// that succeeds at once never touches the clock.  `code` identifies the wait (1 + step) in the status word.
-__device__ __forceinline__ bool fsn_wait_give_up(unsigned* status, unsigned spins, unsigned long long& t0,
-                                                 unsigned long long ticks, unsigned code) {
-    const unsigned st = __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long now = (unsigned long long)wall_clock64();
-    if (spins < 256u) t0 = now;
-    if (st == 0 && now - t0 <= ticks) return false;
-    if ((threadIdx.x & 63) == 0 && st == 0) __hip_atomic_store(status, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-}
-#endif
 size_t fsn_fb_chain_status_word();
 size_t fsn_lstm2_group_status_word(int clusters);
 size_t fsn_lstm2_group_bptt_status_word(int clusters);

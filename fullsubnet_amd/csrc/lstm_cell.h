@@ -29,3 +29,17 @@ __device__ __forceinline__ f32x4 cat2(f32x2 a, f32x2 b) { return __builtin_shuff
 //   r:  tmp = sig(a)      nh: tmp = tmp a      nx: tmp = tanh(a + tmp) = n      z: h = n + sig(a) (h_{t-1} - n)
 // (= (1 - z) n + z h_{t-1}); `cst` holds h in fp32 where the LSTM holds c.  The products of the two zero blocks are
 // skipped (nx: no recurrent K loop; nh: no input chunks / slices from step 1 on): 3/4 of the LSTM's matrix work.
+
+// One gate pass' update of the accumulator-shaped state, on pairs: VAR[rt][u] = EXPR(a, c, m) for every (row tile, unit group)
+// of the wave, with a / c / m the halves of acc / cst / tmp[rt][u] - names of the kernel's own arrays, as are RT and UG.
+// (The four-pass chain that uses it is written out in both kernels; as one shared template it does not compile to the same
+// instruction stream: profiles/persist_sync_refactor.md.)
+#define FSN_CELL_PASS2(VAR, EXPR)                                                                     \
+    _Pragma("unroll") for (int rt = 0; rt < RT; ++rt)                                                 \
+    _Pragma("unroll") for (int u = 0; u < UG; ++u) {                                                  \
+        const f32x4 A = acc[rt][u], C = cst[rt][u], M = tmp[rt][u];                                   \
+        (void)A, (void)C, (void)M;                                                                    \
+        auto half = [&](f32x2 a, f32x2 c, f32x2 m) { (void)a, (void)c, (void)m; return EXPR; };       \
+        VAR[rt][u] = cat2(half(lo2(A), lo2(C), lo2(M)), half(hi2(A), hi2(C), hi2(M)));                \
+        asm volatile("" : "+v"(VAR[rt][u]));                                                          \
+    }

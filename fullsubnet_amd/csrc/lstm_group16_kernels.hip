@@ -28,12 +28,10 @@
 // Arithmetic: operands rounded to fp16 / bf16 (round to nearest even) exactly where fsn_mma_k16 rounds them - weights
 // once when packed, activations when staged - products and sums in fp32, everything stored in fp32.  Results differ
 // from the fp32-era kernels under the same arithmetic only by the order of the fp32 sums (tests/test_gpu_amp.py holds
-// both to the exact emulation).  Flags / bounded waits / status / poison exactly as in lstm_group_kernels.hip.
-#include "fsn_common.h"
+// both to the exact emulation).  Flags / bounded waits / status / poison: the group family of persist_sync.h, as in lstm_group_kernels.hip.
+#include "persist_sync.h"
 
 namespace {
-
-typedef unsigned q_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int QH = 384;            // hidden units (both layers)
 constexpr int QG = 4 * QH;         // gate columns
@@ -61,13 +59,13 @@ __device__ __forceinline__ fsn_u32x2 q_round4(const f32x4 v) {
     return __builtin_bit_cast(fsn_u32x2, fsn_operand<AR>(v));
 }
 template <int AR>
-__device__ __forceinline__ f32x4 q_mma2(const q_u32x4 a, const q_u32x4 b, f32x4 c) {  // one K block (32 k) of one tile
+__device__ __forceinline__ f32x4 q_mma2(const fsn_u32x4 a, const fsn_u32x4 b, f32x4 c) {  // one K block (32 k) of one tile
     // (round 5: ONE v_mfma_f32_16x16x32_{f16,bf16} - the lane's sixteen bytes ARE that instruction's operand - where
     // rounds 3 - 4 issued two K = 16 instructions, which run at half its rate on gfx950)
     return fsn_mma_k32<AR>(fsn_wfrag_operand<AR>(fsn_u32x2{a[0], a[1]}), fsn_wfrag_operand<AR>(fsn_u32x2{a[2], a[3]}),
                            fsn_wfrag_operand<AR>(fsn_u32x2{b[0], b[1]}), fsn_wfrag_operand<AR>(fsn_u32x2{b[2], b[3]}), c);
 }
-__device__ __forceinline__ q_u32x4 q_lds128(const unsigned char* p) { return *reinterpret_cast<const q_u32x4*>(p); }
+__device__ __forceinline__ fsn_u32x4 q_lds128(const unsigned char* p) { return *reinterpret_cast<const fsn_u32x4*>(p); }
 // four 16-bit values as q_round4 packed them -> fp32 (exact)
 template <int AR>
 __device__ __forceinline__ f32x4 q_unpack4(const unsigned lo, const unsigned hi) {
@@ -86,67 +84,6 @@ __device__ __forceinline__ f32x4 q_unpack4(const unsigned lo, const unsigned hi)
 // r of step t still owns its 4H x 4 bytes and uses the first half as [unit quad 96][gate 4][4 units] 16-bit, so a thread's
 // (row, unit quad) item is 32 contiguous bytes (two 16-byte stores forward, two LDS-DMA pieces backward) and rows that do
 // not fill a cluster (step kernels beside the launch, fp32 layout) are untouched.  The cell sequence stays fp32.
-
-// One wave polls eight member flags until all have reached `epoch` (bounded by the device clock).
-__device__ __forceinline__ void q_poll(unsigned* flags8, unsigned epoch, unsigned* status, unsigned long long ticks) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long t0 = 0;
-    for (unsigned spins = 0;; ++spins) {
-        unsigned v = epoch;
-        if (lane < QM) v = __hip_atomic_load(flags8 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__all((int)(v >= epoch))) return;
-        if ((spins & 255u) == 255u && fsn_wait_give_up(status, spins, t0, ticks, 1u + epoch)) return;
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-__device__ __forceinline__ void q_wait(unsigned* flags8, unsigned epoch, unsigned* status, unsigned long long ticks) {
-    if ((threadIdx.x >> 6) == 0) q_poll(flags8, epoch, status, ticks);
-    __syncthreads();  // one wave looked for all four
-}
-// the workgroup's write-through stores of this step are in flight: every wave drains, then ONE lane bumps the flag
-__device__ __forceinline__ void q_publish(unsigned* flag, unsigned epoch) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// XS: the scope of the exchanged payload.  16 = sc1, device scope: never from this CU's L1, and lines written by a CU of
-// another XCD are fetched through the fabric - valid wherever the workgroups run.  1 = sc0: never from this CU's L1, served
-// by this XCD's L2 - valid only between workgroups of ONE XCD (whose L2 is their point of coherence); the forward kernel
-// takes it when every workgroup of a cluster reports the same XCD at start (HW_REG_XCC_ID), see lstm2_g16_fwd_kernel.
-template <int XS = 16>
-__device__ __forceinline__ f32x4 q_load_sc1(const __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, XS));
-}
-__device__ __forceinline__ f32x4 q_load(const __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-template <int XS = 16>
-__device__ __forceinline__ void q_store_sc1(const __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, const f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(q_u32x4, v), r, voff, soff, XS);  // write-through
-}
-__device__ __forceinline__ void q_store(const __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, const f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(q_u32x4, v), r, voff, soff, 0);
-}
-// One 16-byte-per-lane LDS-DMA fragment (1 KB per wave, no registers): lane l's 16 bytes at `g` land at LDS byte address
-// lds_base + 16 l.  As asm: the compiler neither serialises later LDS reads behind it nor counts it in its own vmcnt
-// bookkeeping (an extra OLDER request in the queue can only make its counted waits longer, never too short); the reader
-// states its own wait (s_waitcnt vmcnt(0)) before it touches the landing zone.
-__device__ __forceinline__ void q_lds_dma(const float* g, unsigned lds_base) {
-    unsigned saved;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, off\n\t"
-        "s_nop 0\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(saved)
-        : "s"(lds_base), "v"(g)
-        : "memory");
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t q_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
 
 // ---- packing ------------------------------------------------------------------------------------------------------
 // forward: product W [4H][K] (nn.LSTM's layout, K = k_pad columns, zeros beyond k) -> [member 8][gate 4][K/32][unit
@@ -172,7 +109,7 @@ __global__ void q_pack_fwd_kernel(const float* __restrict__ w, unsigned short* _
             hi[e] = k0 + 4 + e < k ? w[(long)row * k + k0 + 4 + e] : 0.f;
         }
         const fsn_u32x2 a = q_round4<AR>(lo), b = q_round4<AR>(hi);
-        reinterpret_cast<q_u32x4*>(out)[i] = q_u32x4{a[0], a[1], b[0], b[1]};
+        reinterpret_cast<fsn_u32x4*>(out)[i] = fsn_u32x4{a[0], a[1], b[0], b[1]};
     }
 }
 // BPTT: product W [4H][H] -> [member 8][wave 4][kbl 12][j 3][lane 64][8]: lane (lr, lq) of fragment (m, w, kbl, j) holds
@@ -199,7 +136,7 @@ __global__ void q_pack_bptt_kernel(const float* __restrict__ w, void* __restrict
             v[e] = w[(long)col * QH + unit];
         }
         const fsn_u32x2 a = q_round4<AR>(f32x4{v[0], v[1], v[2], v[3]}), b = q_round4<AR>(f32x4{v[4], v[5], v[6], v[7]});
-        reinterpret_cast<q_u32x4*>(out)[i] = q_u32x4{a[0], a[1], b[0], b[1]};
+        reinterpret_cast<fsn_u32x4*>(out)[i] = fsn_u32x4{a[0], a[1], b[0], b[1]};
     }
 }
 
@@ -222,6 +159,7 @@ struct G16FwdArgs {
     int Tp, Nrows;
 };
 
+// XS: the cache policy (scope) of the exchanged payload, FSN_CP_SC1 or - all workgroups of the cluster on one XCD - FSN_CP_SC0
 template <int LAYER, int AR, int XS, int SV>
 __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, int member, unsigned char* act, unsigned char* xsm) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -230,17 +168,16 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
     const size_t N = (size_t)a.Nrows;
     unsigned* fl0 = a.flags + ((size_t)cluster * 2 + 0) * QFS;
     unsigned* fl1 = a.flags + ((size_t)cluster * 2 + 1) * QFS;
-    const __amdgpu_buffer_rsrc_t wrsrc = q_rsrc(a.w16, 0x7fffffff);
+    const __amdgpu_buffer_rsrc_t wrsrc = fsn_buffer_rsrc(a.w16);
     // this wave's weight stream of a product: fragments (kb, j) at wbase + kb * 3072 + j * 1024 + lane * 16
     auto wbase = [&](unsigned o, int kbn) { return o + (unsigned)((member * 4 + wave) * kbn) * 3072u; };
     const unsigned w_rec = wbase(LAYER ? a.o_hh1 : a.o_hh0, 12), w_in = LAYER ? wbase(a.o_ih1, 12) : wbase(a.o_ih0, 1);
     auto wload = [&](unsigned base, int kb, int j) {
-        return __builtin_bit_cast(q_u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (unsigned)lane * 16u,
-                                                                                 base + (unsigned)kb * 3072u + (unsigned)j * 1024u, 0));
+        return fsn_buffer_load<fsn_u32x4>(wrsrc, (unsigned)lane * 16u, base + (unsigned)kb * 3072u + (unsigned)j * 1024u);
     };
     // the cluster's [64][H] tile of step t of a hidden sequence / cell sequence, its [64][4H] tile of a gate buffer
-    auto tileh = [&](float* p, int t) { return q_rsrc(p + ((size_t)t * N + (size_t)cluster * QROWS) * QH, QROWS * QH * 4); };
-    auto tileg = [&](float* p, int t) { return q_rsrc(p + ((size_t)t * N + (size_t)cluster * QROWS) * QG, QROWS * QG * 4); };
+    auto tileh = [&](float* p, int t) { return fsn_buffer_rsrc(p + ((size_t)t * N + (size_t)cluster * QROWS) * QH, QROWS * QH * 4); };
+    auto tileg = [&](float* p, int t) { return fsn_buffer_rsrc(p + ((size_t)t * N + (size_t)cluster * QROWS) * QG, QROWS * QG * 4); };
 
     // bias of this wave's gate for the member's three unit tiles: accumulator row 4 lq + i of tile j = unit 16 j + 4 lq + i
     f32x4 bias[3];
@@ -258,14 +195,14 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
             for (int i = 0; i < 6; ++i) {
                 const int q = tid + 256 * (half * 6 + i), row = q / 48, k8 = q % 48;
                 const unsigned go = (unsigned)((row * QH + k8 * 8) * 4);
-                v[2 * i] = q_load_sc1<XS>(src, go, 0);
-                v[2 * i + 1] = q_load_sc1<XS>(src, go, 16);
+                v[2 * i] = fsn_buffer_load<f32x4, XS>(src, go, 0);
+                v[2 * i + 1] = fsn_buffer_load<f32x4, XS>(src, go, 16);
             }
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
                 const int q = tid + 256 * (half * 6 + i), row = q / 48, k8 = q % 48;
                 const fsn_u32x2 lo = q_round4<AR>(v[2 * i]), hi = q_round4<AR>(v[2 * i + 1]);
-                *reinterpret_cast<q_u32x4*>(act + row * ACT_STRIDE + k8 * 16) = q_u32x4{lo[0], lo[1], hi[0], hi[1]};
+                *reinterpret_cast<fsn_u32x4*>(act + row * ACT_STRIDE + k8 * 16) = fsn_u32x4{lo[0], lo[1], hi[0], hi[1]};
             }
         }
     };
@@ -273,28 +210,28 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
     // save slots BEFORE its flag; the partners copy [64][H] 16-bit values (half the bytes, no conversion) straight into `act`.
     // `g` = the layer's gate-save buffer, step t.  (Rounded at the producer or at the consumer's matrix input: the same number.)
     auto stage16 = [&](float* g, int t) {
-        const __amdgpu_buffer_rsrc_t src = q_rsrc(g + ((size_t)t * N + (size_t)cluster * QROWS) * QG, QROWS * QG * 4);
-        q_u32x4 v[12];
+        const __amdgpu_buffer_rsrc_t src = fsn_buffer_rsrc(g + ((size_t)t * N + (size_t)cluster * QROWS) * QG, QROWS * QG * 4);
+        fsn_u32x4 v[12];
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
             const int q = tid + 256 * i, row = q / 48, k8 = q % 48;
-            v[i] = __builtin_bit_cast(q_u32x4, __builtin_amdgcn_raw_buffer_load_b128(src, (unsigned)(row * QG * 4 + Q_H16_OFF + k8 * 16), 0, XS));
+            v[i] = fsn_buffer_load<fsn_u32x4, XS>(src, (unsigned)(row * QG * 4 + Q_H16_OFF + k8 * 16), 0);
         }
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
             const int q = tid + 256 * i, row = q / 48, k8 = q % 48;
-            *reinterpret_cast<q_u32x4*>(act + row * ACT_STRIDE + k8 * 16) = v[i];
+            *reinterpret_cast<fsn_u32x4*>(act + row * ACT_STRIDE + k8 * 16) = v[i];
         }
     };
     // acc += W(gate `wave` of the member's 48 units x K) act^T: twelve K blocks, the wave's own weight stream through a
     // ring of QD blocks whose first turn `ring` was requested by the caller (before the hand-off wait)
-    auto kloop12 = [&](f32x4 (&acc)[3][4], q_u32x4 (&ring)[QD][3], unsigned base) {
+    auto kloop12 = [&](f32x4 (&acc)[3][4], fsn_u32x4 (&ring)[QD][3], unsigned base) {
 #pragma unroll
         for (int kb0 = 0; kb0 < 12; kb0 += QD) {
 #pragma unroll
             for (int d = 0; d < QD; ++d) {
                 const int kb = kb0 + d;
-                q_u32x4 wf[3], af[4];
+                fsn_u32x4 wf[3], af[4];
 #pragma unroll
                 for (int j = 0; j < 3; ++j) wf[j] = ring[d][j];
                 if (kb + QD < 12) {
@@ -312,7 +249,7 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
             }
         }
     };
-    auto ring_start = [&](q_u32x4 (&ring)[QD][3], unsigned base) {
+    auto ring_start = [&](fsn_u32x4 (&ring)[QD][3], unsigned base) {
 #pragma unroll
         for (int d = 0; d < QD; ++d)
 #pragma unroll
@@ -334,10 +271,10 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
         for (int j = 0; j < 3; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[j][r] = bias[j];
-        q_u32x4 ring[QD][3];
+        fsn_u32x4 ring[QD][3];
         if (LAYER == 0) {
             // x_t (64 rows x 32 columns, the caller's tensor: plain loads) -> xsm; its three weight fragments
-            q_u32x4 wx[3];
+            fsn_u32x4 wx[3];
 #pragma unroll
             for (int j = 0; j < 3; ++j) wx[j] = wload(w_in, 0, j);
             if (t > 0) ring_start(ring, w_rec);
@@ -346,16 +283,16 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
                 const float* xp = a.x + ((size_t)t * a.x_step + (size_t)cluster * QROWS + row) * 32 + k8 * 8;
                 const fsn_u32x2 lo = q_round4<AR>(*reinterpret_cast<const f32x4*>(xp));
                 const fsn_u32x2 hi = q_round4<AR>(*reinterpret_cast<const f32x4*>(xp + 4));
-                *reinterpret_cast<q_u32x4*>(xsm + row * X_STRIDE + k8 * 16) = q_u32x4{lo[0], lo[1], hi[0], hi[1]};
+                *reinterpret_cast<fsn_u32x4*>(xsm + row * X_STRIDE + k8 * 16) = fsn_u32x4{lo[0], lo[1], hi[0], hi[1]};
             }
             if (t > 0) {
-                q_wait(fl0, (unsigned)t, a.status, a.spin_ticks);  // h0_{t-1} of all members
+                fsn_group_wait<QM>(fl0, (unsigned)t, a.status, a.spin_ticks);  // h0_{t-1} of all members
                 if constexpr (SV != 0) stage16(a.gates0, t - 1);
                 else stage(tileh(a.hseq0, t - 1));
             }
             __syncthreads();
             {
-                q_u32x4 af[4];
+                fsn_u32x4 af[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) af[r] = q_lds128(xsm + (16 * r + lr) * X_STRIDE + lq * 16);
 #pragma unroll
@@ -367,14 +304,14 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
         } else {
             // x_t W_ih1^T first: it needs h0_t, which layer 0 published long ago; then h1_{t-1} W_hh1^T
             ring_start(ring, w_in);
-            q_wait(fl0, (unsigned)t + 1, a.status, a.spin_ticks);
+            fsn_group_wait<QM>(fl0, (unsigned)t + 1, a.status, a.spin_ticks);
             if constexpr (SV != 0) stage16(a.gates0, t);
             else stage(tileh(a.hseq0, t));
             __syncthreads();
             kloop12(acc, ring, w_in);
             if (t > 0) {
                 ring_start(ring, w_rec);
-                q_wait(fl1, (unsigned)t, a.status, a.spin_ticks);  // h1_{t-1} of all members; also: everyone has left `act`
+                fsn_group_wait<QM>(fl1, (unsigned)t, a.status, a.spin_ticks);  // h1_{t-1} of all members; also: everyone has left `act`
                 if constexpr (SV != 0) stage16(a.gates1, t - 1);
                 else stage(tileh(a.hseq1, t - 1));
                 __syncthreads();
@@ -406,10 +343,10 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
                 sg[e][0][i] = ig, sg[e][1][i] = fg, sg[e][2][i] = gg, sg[e][3][i] = og;
             }
             if constexpr (SV != 0)
-                __builtin_amdgcn_raw_buffer_store_b64(q_round4<AR>(hv), rg, (unsigned)(row * QG * 4 + Q_H16_OFF + (QU * member + quad * 4) * 2), 0, XS);
-            else q_store_sc1<XS>(rh, (unsigned)((row * QH + QU * member + quad * 4) * 4), 0, hv);
+                fsn_buffer_store<XS>(rg, (unsigned)(row * QG * 4 + Q_H16_OFF + (QU * member + quad * 4) * 2), 0, q_round4<AR>(hv));
+            else fsn_buffer_store<XS>(rh, (unsigned)((row * QH + QU * member + quad * 4) * 4), 0, hv);
         }
-        q_publish(myflag, (unsigned)t + 1);  // its barrier also closes the reads of the gate exchange
+        fsn_publish(myflag, (unsigned)t + 1);  // its barrier also closes the reads of the gate exchange
         // the saves of the step, AFTER the hand-off (only h belongs to it)
         const __amdgpu_buffer_rsrc_t rc = tileh(cseq, t);
 #pragma unroll
@@ -420,20 +357,20 @@ __device__ __forceinline__ void g16_fwd_body(const G16FwdArgs& a, int cluster, i
                 const unsigned so = (unsigned)(row * QG * 4 + (12 * member + quad) * 32);
                 const fsn_u32x2 pi = q_round4<AR>(sg[e][0]), pf = q_round4<AR>(sg[e][1]);
                 const fsn_u32x2 pg = q_round4<AR>(sg[e][2]), po = q_round4<AR>(sg[e][3]);
-                __builtin_amdgcn_raw_buffer_store_b128(q_u32x4{pi[0], pi[1], pf[0], pf[1]}, rg, so, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b128(q_u32x4{pg[0], pg[1], po[0], po[1]}, rg, so, 16, 0);
+                fsn_buffer_store(rg, so, 0, fsn_u32x4{pi[0], pi[1], pf[0], pf[1]});
+                fsn_buffer_store(rg, so, 16, fsn_u32x4{pg[0], pg[1], po[0], po[1]});
                 // (h_t in 16 bits sits behind them, second half of the row's slot, [H] values: the hand-off above - and the B
                 // operand of two weight-gradient products, which need no conversion pass over the hidden sequence.)  The
                 // fp32 hidden sequence, off the hand-off path: recomputed from o and c, the very value that was rounded
                 f32x4 hv;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) hv[i] = sg[e][3][i] * tanh_fast(c[e][i]);
-                q_store(rh, (unsigned)((row * QH + QU * member + quad * 4) * 4), 0, hv);
+                fsn_buffer_store(rh, (unsigned)((row * QH + QU * member + quad * 4) * 4), 0, hv);
             } else {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) q_store(rg, go, (unsigned)(g * QH * 4), sg[e][g]);
+                for (int g = 0; g < 4; ++g) fsn_buffer_store(rg, go, (unsigned)(g * QH * 4), sg[e][g]);
             }
-            q_store(rc, (unsigned)((row * QH + QU * member + quad * 4) * 4), 0, c[e]);
+            fsn_buffer_store(rc, (unsigned)((row * QH + QU * member + quad * 4) * 4), 0, c[e]);
         }
     }
 }
@@ -459,7 +396,7 @@ __global__ __launch_bounds__(256, 2) void lstm2_g16_fwd_kernel(const G16FwdArgs 
         member = bid % QM;
     }
     // Placement check: every workgroup reports the XCD it runs on (HW_REG_XCC_ID) and reads its cluster's sixteen reports;
-    // only when all agree is the payload exchanged at XCD scope (XS = 1: 9 % of the launch, the partners' tiles come from
+    // only when all agree is the payload exchanged at XCD scope (XS = FSN_CP_SC0: 9 % of the launch, the partners' tiles come from
     // the shared L2 instead of through the fabric).  Any other placement - or a timeout - takes the device-scope path:
     // results never depend on where the workgroups run.
     bool same_xcd = false;
@@ -491,11 +428,11 @@ __global__ __launch_bounds__(256, 2) void lstm2_g16_fwd_kernel(const G16FwdArgs 
         __syncthreads();  // (xsm is the layer-0 input tile afterwards)
     }
     if (same_xcd) {
-        if (layer == 0) g16_fwd_body<0, AR, 1, SV>(a, cluster, member, act, xsm);
-        else g16_fwd_body<1, AR, 1, SV>(a, cluster, member, act, xsm);
+        if (layer == 0) g16_fwd_body<0, AR, FSN_CP_SC0, SV>(a, cluster, member, act, xsm);
+        else g16_fwd_body<1, AR, FSN_CP_SC0, SV>(a, cluster, member, act, xsm);
     } else {
-        if (layer == 0) g16_fwd_body<0, AR, 16, SV>(a, cluster, member, act, xsm);
-        else g16_fwd_body<1, AR, 16, SV>(a, cluster, member, act, xsm);
+        if (layer == 0) g16_fwd_body<0, AR, FSN_CP_SC1, SV>(a, cluster, member, act, xsm);
+        else g16_fwd_body<1, AR, FSN_CP_SC1, SV>(a, cluster, member, act, xsm);
     }
 }
 
@@ -519,7 +456,7 @@ __global__ __launch_bounds__(256, 2) void lstm2_g16_fwd_kernel(const G16FwdArgs 
 constexpr int QAD = 4;                  // operand blocks in flight per wave (4 fragments each)
 constexpr int QWD = 4;                  // weight blocks in flight per wave (3 fragments each)
 template <int AR>
-__device__ __forceinline__ f32x4 q_mma_blk(const q_u32x4 a, const q_u32x4 b, f32x4 c) { return q_mma2<AR>(a, b, c); }
+__device__ __forceinline__ f32x4 q_mma_blk(const fsn_u32x4 a, const fsn_u32x4 b, f32x4 c) { return q_mma2<AR>(a, b, c); }
 
 struct G16BwdArgs {
     const float* dh1;      // [Tp][N][H]  d loss / d hseq1
@@ -547,19 +484,18 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
     const size_t N = (size_t)a.Nrows;
     unsigned* fl1 = a.flags + ((size_t)cluster * 2 + 0) * QFS;
     unsigned* fl0 = a.flags + ((size_t)cluster * 2 + 1) * QFS;
-    const __amdgpu_buffer_rsrc_t wrsrc = q_rsrc(a.w16, 0x7fffffff);
+    const __amdgpu_buffer_rsrc_t wrsrc = fsn_buffer_rsrc(a.w16);
     // this wave's weight stream of a product: fragments (kbl, j) at base + kbl * 3072 + j * 1024 + lane * 16
     constexpr int NBW = q_nbw<AR>(), NBM = q_nbm<AR>(), XSLOT = q_xslot<AR>();
     auto wbase = [&](unsigned o) { return o + (unsigned)((member * 4 + wave) * NBW) * 3072u; };
     auto wload = [&](unsigned base, int kbl, int j) {
-        return __builtin_bit_cast(q_u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (unsigned)lane * 16u,
-                                                                                 base + (unsigned)kbl * 3072u + (unsigned)j * 1024u, 0));
+        return fsn_buffer_load<fsn_u32x4>(wrsrc, (unsigned)lane * 16u, base + (unsigned)kbl * 3072u + (unsigned)j * 1024u);
     };
-    auto wait = [&](unsigned* f8, unsigned epoch) { q_wait(f8, epoch, a.status, a.spin_ticks); };
-    auto tileh = [&](const float* p, int t) { return q_rsrc(p + ((size_t)t * N + (size_t)cluster * QROWS) * QH, QROWS * QH * 4); };
-    auto tileg = [&](const float* p, int t) { return q_rsrc(p + ((size_t)t * N + (size_t)cluster * QROWS) * QG, QROWS * QG * 4); };
-    const __amdgpu_buffer_rsrc_t rx1 = q_rsrc(reinterpret_cast<const unsigned char*>(a.x1) + (size_t)cluster * QDX * XSLOT, (unsigned)QDX * XSLOT);
-    const __amdgpu_buffer_rsrc_t rx0 = q_rsrc(reinterpret_cast<const unsigned char*>(a.x0) + (size_t)cluster * QDX * XSLOT, (unsigned)QDX * XSLOT);
+    auto wait = [&](unsigned* f8, unsigned epoch) { fsn_group_wait<QM>(f8, epoch, a.status, a.spin_ticks); };
+    auto tileh = [&](const float* p, int t) { return fsn_buffer_rsrc(p + ((size_t)t * N + (size_t)cluster * QROWS) * QH, QROWS * QH * 4); };
+    auto tileg = [&](const float* p, int t) { return fsn_buffer_rsrc(p + ((size_t)t * N + (size_t)cluster * QROWS) * QG, QROWS * QG * 4); };
+    const __amdgpu_buffer_rsrc_t rx1 = fsn_buffer_rsrc(reinterpret_cast<const unsigned char*>(a.x1) + (size_t)cluster * QDX * XSLOT, (unsigned)QDX * XSLOT);
+    const __amdgpu_buffer_rsrc_t rx0 = fsn_buffer_rsrc(reinterpret_cast<const unsigned char*>(a.x0) + (size_t)cluster * QDX * XSLOT, (unsigned)QDX * XSLOT);
     const __amdgpu_buffer_rsrc_t rxo = LAYER ? rx1 : rx0;
     // elementwise mapping = accumulator layout of the transposed product after the reduction: wave = row tile, lane (lr, lq)
     // = row 16 w + lr, for unit tile j = 0..2 of this member the four units 48 m + 16 j + 4 lq .. + 3
@@ -569,12 +505,11 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
     // acc += W^T(this member's 48 units x this wave's twelve K blocks) x (the tile behind `rx`, slot offset `xo`)^T.  The
     // first QWD blocks of weight fragments were requested by the caller (before the hand-off wait); the operand ring
     // starts here, after it.
-    auto kloop = [&](f32x4 (&acc)[3][4], q_u32x4 (&wring)[QWD][3], unsigned wb, const __amdgpu_buffer_rsrc_t rx, unsigned xo) {
+    auto kloop = [&](f32x4 (&acc)[3][4], fsn_u32x4 (&wring)[QWD][3], unsigned wb, const __amdgpu_buffer_rsrc_t rx, unsigned xo) {
         auto xload = [&](int kbl, int r) {
-            return __builtin_bit_cast(q_u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                   rx, (unsigned)lane * 16u, xo + (unsigned)(((wave * NBW + kbl) * 4 + r) * 1024), 16));
+            return fsn_buffer_load<fsn_u32x4, FSN_CP_SC1>(rx, (unsigned)lane * 16u, xo + (unsigned)(((wave * NBW + kbl) * 4 + r) * 1024));
         };
-        q_u32x4 aring[QAD][4];
+        fsn_u32x4 aring[QAD][4];
 #pragma unroll
         for (int d = 0; d < QAD; ++d)
 #pragma unroll
@@ -584,7 +519,7 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
 #pragma unroll
             for (int d = 0; d < QAD; ++d) {
                 const int kbl = kb0 + d;
-                q_u32x4 wf[3], af[4];
+                fsn_u32x4 wf[3], af[4];
 #pragma unroll
                 for (int j = 0; j < 3; ++j) wf[j] = wring[d][j];
 #pragma unroll
@@ -605,7 +540,7 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
         }
     };
     static_assert(QAD == QWD && NBW % QAD == 0, "the two rings turn together, in whole turns");
-    auto wring_start = [&](q_u32x4 (&wring)[QWD][3], unsigned wb) {
+    auto wring_start = [&](fsn_u32x4 (&wring)[QWD][3], unsigned wb) {
 #pragma unroll
         for (int d = 0; d < QWD; ++d)
 #pragma unroll
@@ -625,7 +560,7 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
     {
         const __amdgpu_buffer_rsrc_t rc = tileh(cseq, Tp - 1);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) c_t[j] = q_load(rc, eo_h, (unsigned)(j * 64));
+        for (int j = 0; j < 3; ++j) c_t[j] = fsn_buffer_load<f32x4>(rc, eo_h, (unsigned)(j * 64));
     }
 
     for (int t = Tp - 1; t >= 0; --t) {
@@ -649,21 +584,21 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
                 for (int j = 0; j < 3; ++j)
 #pragma unroll
                     for (int p = 0; p < 2; ++p)
-                        q_lds_dma(reinterpret_cast<const float*>(gp16 + j * 128 + p * 16), red_w + (unsigned)((j * 2 + p) * 1024));
+                        fsn_lds_dma(gp16 + j * 128 + p * 16, red_w + (unsigned)((j * 2 + p) * 1024));
             } else {
 #pragma unroll
                 for (int j = 0; j < 3; ++j)
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) q_lds_dma(gp + g * QH + 16 * j, red_w + (unsigned)((j * 4 + g) * 1024));
+                    for (int g = 0; g < 4; ++g) fsn_lds_dma(gp + g * QH + 16 * j, red_w + (unsigned)((j * 4 + g) * 1024));
             }
             const __amdgpu_buffer_rsrc_t rp = tileh(cseq, t > 0 ? t - 1 : 0), rd = tileh(LAYER ? a.dh1 : cseq, t);
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                c_p[j] = t > 0 ? q_load(rp, eo_h, (unsigned)(j * 64)) : f32x4{0.f, 0.f, 0.f, 0.f};
-                dh[j] = LAYER ? q_load(rd, eo_h, (unsigned)(j * 64)) : f32x4{0.f, 0.f, 0.f, 0.f};
+                c_p[j] = t > 0 ? fsn_buffer_load<f32x4>(rp, eo_h, (unsigned)(j * 64)) : f32x4{0.f, 0.f, 0.f, 0.f};
+                dh[j] = LAYER ? fsn_buffer_load<f32x4>(rd, eo_h, (unsigned)(j * 64)) : f32x4{0.f, 0.f, 0.f, 0.f};
             }
         }
-        q_u32x4 wring[QWD][3];
+        fsn_u32x4 wring[QWD][3];
         if (LAYER == 0) {  // dgates1_t W_ih1: layer 1 published step t as its flag value done + 1
             wring_start(wring, w_ih);
             wait(fl1, done + 1);
@@ -679,8 +614,8 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
         if constexpr (SV != 0) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                const q_u32x4 v0 = q_lds128(red + (wave * 12 + j * 2) * 1024 + lane * 16);
-                const q_u32x4 v1 = q_lds128(red + (wave * 12 + j * 2 + 1) * 1024 + lane * 16);
+                const fsn_u32x4 v0 = q_lds128(red + (wave * 12 + j * 2) * 1024 + lane * 16);
+                const fsn_u32x4 v1 = q_lds128(red + (wave * 12 + j * 2 + 1) * 1024 + lane * 16);
                 sg[j][0] = q_unpack4<AR>(v0[0], v0[1]), sg[j][1] = q_unpack4<AR>(v0[2], v0[3]);
                 sg[j][2] = q_unpack4<AR>(v1[0], v1[1]), sg[j][3] = q_unpack4<AR>(v1[2], v1[3]);
             }
@@ -732,23 +667,22 @@ __device__ __forceinline__ void g16_bwd_body(const G16BwdArgs& a, int cluster, i
         if (LAYER && done >= (unsigned)QDX) wait(fl0, done - QDX + 1);
 #pragma unroll
         for (int kbl = 0; kbl < NBM; ++kbl) {
-            const q_u32x4 v = q_lds128(dsh + (wave * 16 + lr) * DSH_STRIDE + kbl * 64 + lq * 16);
-            __builtin_amdgcn_raw_buffer_store_b128(v, rxo, (unsigned)lane * 16u,
-                                                   (unsigned)((t % QDX) * XSLOT + ((NBM * member + kbl) * 4 + wave) * 1024), 16);
+            const fsn_u32x4 v = q_lds128(dsh + (wave * 16 + lr) * DSH_STRIDE + kbl * 64 + lq * 16);
+            fsn_buffer_store<FSN_CP_SC1>(rxo, (unsigned)lane * 16u, (unsigned)((t % QDX) * XSLOT + ((NBM * member + kbl) * 4 + wave) * 1024), v);
         }
-        q_publish(myfl + member, done + 1);  // its barrier also closes this step's use of `red` and `dsh`
+        fsn_publish(myfl + member, done + 1);  // its barrier also closes this step's use of `red` and `dsh`
         // AFTER the hand-off (only the fragment-order tile belongs to it): the gate gradients for the products that follow
         // the launch - 16-bit row-major copies [t][row][4H] (the weight-gradient products' operand: rounding here or at their
         // matrix input is the same number), fp32 for layer 0 (its input gradient is an fp32 product) - and their column sums
         // (the bias gradients, from the fp32 values): the 16 rows of a wave summed by DPP, one lane per unit quad adds to LDS
-        const __amdgpu_buffer_rsrc_t r16 = q_rsrc(dg16 + ((size_t)t * N + (size_t)cluster * QROWS) * QG, QROWS * QG * 2);
+        const __amdgpu_buffer_rsrc_t r16 = fsn_buffer_rsrc(dg16 + ((size_t)t * N + (size_t)cluster * QROWS) * QG, QROWS * QG * 2);
         const unsigned eo_16 = (unsigned)((((wave * 16 + lr) * QG) + QU * member + 4 * lq) * 2);
 #pragma unroll
         for (int j = 0; j < 3; ++j)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                if (LAYER ? a.dg1_f32 : a.dg0_f32) q_store(ro, eo_g, (unsigned)(g * QH * 4 + j * 64), sg[j][g]);
-                __builtin_amdgcn_raw_buffer_store_b64(q_round4<AR>(sg[j][g]), r16, eo_16, (unsigned)((g * QH + j * 16) * 2), 0);
+                if (LAYER ? a.dg1_f32 : a.dg0_f32) fsn_buffer_store(ro, eo_g, (unsigned)(g * QH * 4 + j * 64), sg[j][g]);
+                fsn_buffer_store(r16, eo_16, (unsigned)((g * QH + j * 16) * 2), q_round4<AR>(sg[j][g]));
                 fsn_hold_store_data(sg[j][g]);  // the sums below may be formed in the store's data registers
                 f32x4 v = sg[j][g];
 #pragma unroll

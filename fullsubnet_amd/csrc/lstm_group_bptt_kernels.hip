@@ -17,15 +17,15 @@
 //     cadence of the forward kernel); A fragments come through an eight-deep register ring;
 //   - the saved activations of a step (gates, c_t, c_{t-1}, dH: 7 values per element) are requested before the flag
 //     wait;
-//   - flags / bounded spins / status exactly as in lstm_group_kernels.hip.
-#include "fsn_common.h"
+//   - flags / bounded spins / status: the group family of persist_sync.h, as in lstm_group_kernels.hip.
+#include "persist_sync.h"
 
 namespace {
 
 // sc1 loads of the A operand (never cached: 0.3 GB per step through the fabric).  Ordinary loads after an agent-scope
 // acquire (buffer_inv sc1), shared through the XCD's L2, measured slower (48.5 against 47.1 ms per training step: the
 // invalidates of 64 workgroups per XCD and step take the weights out of the L2 as well)
-constexpr int BPTT_A_AUX = 16;
+constexpr int BPTT_A_AUX = FSN_CP_SC1;
 constexpr int BPTT_TURN = 2;    // x 4 chunks = A fragments in flight (must divide 24 stages); measured: 2 -> 12.5 ms, 3 -> 12.9, 4 -> 13.2
 constexpr int BPTT_TURN16 = 2;  // the same under the 16-bit arithmetic (the K loop is 8x shorter: the A operand's latency shows)
 
@@ -51,22 +51,6 @@ struct BpttArgs {
     int Tp, Nrows;
 };
 
-__device__ __forceinline__ void bptt_store_sc1(float* p, float v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through
-}
-
-__device__ __forceinline__ bool bptt_poll(unsigned* flags8, unsigned epoch, unsigned* status, unsigned long long ticks) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long t0 = 0;
-    for (unsigned spins = 0;; ++spins) {
-        unsigned v = epoch;
-        if (lane < BM) v = __hip_atomic_load(flags8 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__all((int)(v >= epoch))) return true;
-        if ((spins & 255u) == 255u && fsn_wait_give_up(status, spins, t0, ticks, 1u + epoch)) return false;
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-
 // AR: arithmetic of the products (fsn_mma_k16); everything stored stays fp32
 template <int LAYER, int AR>
 __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int member,
@@ -82,23 +66,20 @@ __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int me
     // the cluster's [64][4H] tile of step t of a gate-gradient buffer as a buffer resource (one per step: the whole
     // buffer - 2.5 GB at config 3's shape - is beyond the 2 GB a resource's offsets reach)
     auto tile = [&](float* dg, int t) {
-        return __builtin_amdgcn_make_buffer_rsrc(dg + ((size_t)t * N + (size_t)cluster * BROWS) * BG, 0, BROWS * BG * 4,
-                                                 0x00020000);
+        return fsn_buffer_rsrc(dg + ((size_t)t * N + (size_t)cluster * BROWS) * BG, BROWS * BG * 4);
     };
     // likewise the cluster's [64][H] tile of a [Tp][N][H] buffer (cell states, dH, dx)
     auto tileh = [&](const float* p, int t) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p) + ((size_t)t * N + (size_t)cluster * BROWS) * BH, 0,
-                                                 BROWS * BH * 4, 0x00020000);
+        return fsn_buffer_rsrc(p + ((size_t)t * N + (size_t)cluster * BROWS) * BH, BROWS * BH * 4);
     };
     // Element (row 4 lq + i of this wave's tile, unit 16 u + lr of this member) of such tiles: ONE lane offset each and
     // compile-time scalar offsets for (i, u, gate) - no per-element address registers (84 loads and 60 stores per step)
     const unsigned voff_g = (unsigned)(((wave * 16 + 4 * lq) * BG + member * BU * 16 + lr) * 4);
     const unsigned voff_h = (unsigned)(((wave * 16 + 4 * lq) * BH + member * BU * 16 + lr) * 4);
     auto ldf = [&](const __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
+        return fsn_buffer_load<float>(r, voff, soff);
     };
-    const __amdgpu_buffer_rsrc_t wrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wbase), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = fsn_buffer_rsrc(a.wbase);
 
     // acc[u] += A(16 rows x K) W^T(K x 16 units of group u): n chunks (a multiple of 2 BCH) of the tile behind `xr`
     // (sc1 loads: the partners wrote through) against the packed matrix at element offset b of the weight buffer.
@@ -118,7 +99,7 @@ __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int me
         typename FsnWFrag<AR>::type bn[NB];
         auto fetch_a = [&](int k) -> f32x4 {
             const int kc = k < n ? k : n - 1;
-            return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, a_off, (unsigned)kc * 64u, BPTT_A_AUX));
+            return fsn_buffer_load<f32x4, BPTT_A_AUX>(xr, a_off, (unsigned)kc * 64u);
         };
         // Stage s holds chunks BCH s .. BCH s + BCH - 1, fragment (c, u) at index c NT + u.  The BCH NT fragments of a
         // stage are fetched in batches of NB (the registers a wave spends on them): batch id = fragments NB id ..;
@@ -186,23 +167,9 @@ __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int me
         }
     };
 
-    auto peek = [&](unsigned* flags8) -> unsigned {
-        unsigned v = 0xffffffffu;
-        if (wave == 0 && lane < BM) v = __hip_atomic_load(flags8 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return v;
-    };
+    const FsnGroupPeek<BM> peek{wave, lane};
     auto wait_peeked = [&](unsigned v, unsigned* flags8, unsigned epoch) {
-        if (wave == 0 && !__all((int)(v >= epoch))) (void)bptt_poll(flags8, epoch, a.status, a.spin_ticks);
-        __syncthreads();
-    };
-    auto publish = [&](unsigned* flag, unsigned epoch) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-
-    auto gstore = [&](const __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float v) {
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 16);  // sc1: write-through
+        fsn_group_wait_peeked<BM>(wave, v, flags8, epoch, a.status, a.spin_ticks);
     };
     const float* gates = LAYER ? a.gates1 : a.gates0;
     const float* cseq = LAYER ? a.cseq1 : a.cseq0;
@@ -255,8 +222,8 @@ __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int me
                 for (int u = 0; u < BU; ++u) {
                     acc[u] = acc6[u];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)  // dx_{t+1}: layer 0's dH of step t + 1
-                        gstore(rx, voff_h, (unsigned)((i * BH + u * 16) * 4), acc6[BU + u][i]);
+                    for (int i = 0; i < 4; ++i)  // dx_{t+1}: layer 0's dH of step t + 1 (sc1: write-through)
+                        fsn_buffer_store<FSN_CP_SC1>(rx, voff_h, (unsigned)((i * BH + u * 16) * 4), acc6[BU + u][i]);
                 }
             } else {
                 load_saved();
@@ -270,8 +237,7 @@ __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int me
                 for (int u = 0; u < BU; ++u)
 #pragma unroll
                     for (int i = 0; i < 4; ++i)  // sc1: written through by layer 1's workgroup
-                        acc[u][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                                  rx, voff_h, (unsigned)((i * BH + u * 16) * 4), 16));
+                        acc[u][i] = fsn_buffer_load<float, FSN_CP_SC1>(rx, voff_h, (unsigned)((i * BH + u * 16) * 4));
             }
             if (t < Tp - 1) {
                 wait_peeked(peek(fl0), fl0, done);  // dgates0_{t+1} of all members
@@ -294,14 +260,14 @@ __device__ __forceinline__ void bptt_body(const BpttArgs& a, int cluster, int me
                     const float d_o = dh * tc;
                     const float dct = dc[u][i] + dh * og * (1.f - tc * tc);
                     const unsigned so = (unsigned)((i * BG + u * 16) * 4);
-                    gstore(ro, voff_g, so, dct * gg * ig * (1.f - ig));
-                    gstore(ro, voff_g, so + BH * 4, dct * e_cp[u][i] * fg * (1.f - fg));
-                    gstore(ro, voff_g, so + 2 * BH * 4, dct * ig * (1.f - gg * gg));
-                    gstore(ro, voff_g, so + 3 * BH * 4, d_o * og * (1.f - og));
+                    fsn_buffer_store<FSN_CP_SC1>(ro, voff_g, so, dct * gg * ig * (1.f - ig));
+                    fsn_buffer_store<FSN_CP_SC1>(ro, voff_g, so + BH * 4, dct * e_cp[u][i] * fg * (1.f - fg));
+                    fsn_buffer_store<FSN_CP_SC1>(ro, voff_g, so + 2 * BH * 4, dct * ig * (1.f - gg * gg));
+                    fsn_buffer_store<FSN_CP_SC1>(ro, voff_g, so + 3 * BH * 4, d_o * og * (1.f - og));
                     dc[u][i] = dct * fg;
                 }
         }
-        publish((LAYER ? fl1 : fl0) + member, done + 1);
+        fsn_publish((LAYER ? fl1 : fl0) + member, done + 1);
     }
 }
 

@@ -14,8 +14,8 @@
 //   - each layer's K loop contains its input projection (K = 32 + 384 and 384 + 384: no projection GEMMs, no gx);
 //     layer 1 follows layer 0 at a distance of up to two steps (the depth of layer 0's exchange buffer);
 //   - members exchange h slices through a small global buffer per cluster (48 columns written, 384 read) with the
-//     write-through / flag / acquire recipe of the CDNA guide (Guideline 16, R1: sc1 stores, drained, ONE flag store;
-//     relaxed poll by one wave, ONE agent-scope acquire, barrier, plain loads);
+//     write-through / flag recipe of the CDNA guide (Guideline 16, R1: sc1 stores, drained, ONE flag store; relaxed
+//     poll by one wave, barrier, sc1 loads) - the handshake itself is persist_sync.h's group family;
 //   - weight fragments are fetched once per workgroup and shared by its four waves through a two-stage LDS buffer
 //     (the K loop of lstm_step_cu_kernel), 0.9 MB per CU and step instead of 2.4 - 4.7 MB; the A fragments (other
 //     CUs' write-through data: first touch comes from the Infinity Cache / HBM) are requested four chunks ahead.
@@ -25,7 +25,7 @@
 // (Round 6: both layers of a member as ONE instruction stream per CU - lstm2_duo_kernel, commit 1df4f24 - was built, is
 // bit-identical and SLOWER: 73 us per step against 57; its floor with every load, poll and non-linearity removed is 53 us, one
 // wave per SIMD hides none of its own latencies.  profiles/r06_duo_probe.md.)
-#include "fsn_common.h"
+#include "persist_sync.h"
 
 namespace {
 
@@ -92,25 +92,6 @@ struct GrpSets {
     int n;
 };
 
-__device__ __forceinline__ void store_sc1(float* p, float v) {
-    // write-through store (sc1): the line leaves this XCD's L2, any CU of the chip reads it after an agent-scope acquire
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// One wave polls the eight member flags of a layer (relaxed agent-scope loads, never served by this CU's L1) until all
-// have reached `epoch`; bounded.  Returns false after a timeout (status raised).
-__device__ __forceinline__ bool grp_poll(unsigned* flags8, unsigned epoch, unsigned* status, unsigned long long ticks) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long t0 = 0;
-    for (unsigned spins = 0;; ++spins) {
-        unsigned v = epoch;
-        if (lane < GM) v = __hip_atomic_load(flags8 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__all((int)(v >= epoch))) return true;
-        if ((spins & 255u) == 255u && fsn_wait_give_up(status, spins, t0, ticks, 1u + epoch)) return false;
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-
 // What a workgroup keeps per cluster.  A workgroup serves one cluster, or TWO alternately (batches of 9 - 16 utterances:
 // more clusters than the chip holds at once): step t of cluster A, step t of cluster B, step t + 1 of A ... - while it
 // works on one cluster the partners' flags and write-through data of the other are on their way.
@@ -150,8 +131,8 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
         k.hx1 = a.hx1 + (TRAIN ? (size_t)cluster * GROWS * GH : (size_t)cluster * 2 * GROWS * GH);
         k.fl0 = a.flags + ((size_t)cluster * 2 + 0) * GFS;
         k.fl1 = a.flags + ((size_t)cluster * 2 + 1) * GFS;
-        k.xrsrc0 = __builtin_amdgcn_make_buffer_rsrc(k.hx0, 0, 0x7fffffff, 0x00020000);
-        k.xrsrc1 = __builtin_amdgcn_make_buffer_rsrc(k.hx1, 0, 0x7fffffff, 0x00020000);
+        k.xrsrc0 = fsn_buffer_rsrc(k.hx0);
+        k.xrsrc1 = fsn_buffer_rsrc(k.hx1);
         k.row_ok = k.row_l < x.N;
         k.tile_ok = !GX || cluster * GROWS + wave * 16 < a.Nrows;
         k.ng = k.row_l + x.row0;
@@ -170,7 +151,7 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
     const bool my_tile = !GX || cluster_a * GROWS + wave * 16 < a.Nrows;
     const unsigned a_off = (unsigned)((((my_tile ? wave * 16 : 0) + lr) * GH + 4 * lq) * 4);
     auto xload = [&](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 16));  // aux 16 = sc1
+        return fsn_buffer_load<f32x4, FSN_CP_SC1>(r, voff, soff);
     };
 
     // biases of this member's 12 column tiles: in LDS (12 registers decide between fitting and spilling when the
@@ -191,8 +172,7 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
     // = (unit group f >> 2, gate f & 3); wave w fetches fragments 3 w .. 3 w + 2 and parks them in LDS.
     // weight fragments by buffer load: resource descriptor + scalar byte offset + this lane's 16 l (no per-fragment
     // pointers in vector registers)
-    const __amdgpu_buffer_rsrc_t wrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wbase), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = fsn_buffer_rsrc(a.wbase);
     // A operand: xa (registers, layer-0 input) or tile `at1` / `at2` (byte offset) of exchange buffer ab1 / ab2 (0 / 1)
     // (descriptors by value: a reference to one of two descriptors puts both on the stack)
     auto kloop = [&](f32x4 (&acc)[GU][4], const f32x4* xa, const __amdgpu_buffer_rsrc_t r1, unsigned at1, unsigned b1,
@@ -209,9 +189,9 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
             const int kc = k < n ? k : n - 1;
             if (kc < n1) {
                 if (xa) return kc == 0 ? xa[0] : xa[1];
-                return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r1, a_off, at1 + (unsigned)kc * 64u, 16));
+                return xload(r1, a_off, at1 + (unsigned)kc * 64u);
             }
-            return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r2, a_off, at2 + (unsigned)(kc - n1) * 64u, 16));
+            return xload(r2, a_off, at2 + (unsigned)(kc - n1) * 64u);
         };
         auto fetch_b = [&](int k) {
             const int kc = k < n ? k : n - 1;
@@ -275,23 +255,11 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
         if (n % CPS) __syncthreads();  // a last, partial stage (layer 0's 2 + 24 chunks at four per stage): close it as well
     };
 
-    // Flags are looked at EARLY (before a K loop) and checked after it: in the steady state the early look already
-    // shows the awaited epoch and the check costs nothing; only otherwise does wave 0 poll.  No acquire fence: every
-    // load of exchanged data is an sc1 load (see xload).
-    auto peek = [&](unsigned* flags8) -> unsigned {
-        unsigned v = 0xffffffffu;
-        if (wave == 0 && lane < GM) v = __hip_atomic_load(flags8 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return v;
-    };
+    // The handshake (persist_sync.h, group family): flags are looked at EARLY (before a K loop) and checked after it.  No
+    // acquire fence: every load of exchanged data is an sc1 load (see xload).
+    const FsnGroupPeek<GM> peek{wave, lane};
     auto wait_peeked = [&](unsigned v, unsigned* flags8, unsigned epoch) {
-        if (wave == 0 && !__all((int)(v >= epoch))) (void)grp_poll(flags8, epoch, a.status, a.spin_ticks);
-        __syncthreads();  // one wave looked for all four
-    };
-    // h slice of this step is in flight (write-through): every wave drains, then one lane bumps the flag
-    auto publish = [&](unsigned* flag, unsigned epoch) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        fsn_group_wait_peeked<GM>(wave, v, flags8, epoch, a.status, a.spin_ticks);
     };
     // cell update of this wave's 16 rows x 48 units; h_t slice -> exchange buffer
     auto cell = [&](GrpCl& k, f32x4 (&acc)[GU][4], float* hdst, float* gates_t, float* cseq_t) {
@@ -306,13 +274,13 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
                 float* hp = hdst + (size_t)(wave * 16 + 4 * lq + i) * GH + (member * GU + u) * 16 + lr;
                 const float hv = og * tanh_fast(cn);
                 if (GX && !k.tile_ok) continue;
-                store_sc1(hp, hv);
+                fsn_store_sc1(hp, hv);
                 if (TRAIN && SAVE) {  // kept in place of the pre-activations for save_cell (after the hand-off)
                     acc[u][0][i] = ig, acc[u][1][i] = fg, acc[u][2][i] = gg, acc[u][3][i] = og;
                 }
             }
     };
-    // Training: the activated gates and the cell state of the step, stored AFTER the hand-off - publish() drains the
+    // Training: the activated gates and the cell state of the step, stored AFTER the hand-off - fsn_publish() drains the
     // wave's stores before the flag goes out, and only the 12 h values belong to the hand-off: with the 60 saved values
     // issued first every step's flag waited for their trip to HBM as well (same values, same addresses: bit-equal)
     auto save_cell = [&](GrpCl& k, f32x4 (&acc)[GU][4], float* gates_t, float* cseq_t) {
@@ -390,7 +358,7 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
             if (t >= GD0) wait_peeked(ring, k.fl1, (unsigned)(t - GD0 + 1));
             cell(k, acc, reinterpret_cast<float*>(reinterpret_cast<char*>(k.hx0) + slot0(t)),
                  TRAIN ? a.gates0 + (size_t)t * a.Nrows * 4 * GH : nullptr, TRAIN ? a.cseq0 + (size_t)t * a.Nrows * GH : nullptr);
-            publish(k.fl0 + member, (unsigned)t + 1);
+            fsn_publish(k.fl0 + member, (unsigned)t + 1);  // the h slice is in flight (write-through)
             if (TRAIN && SAVE) save_cell(k, acc, a.gates0 + (size_t)t * a.Nrows * 4 * GH, a.cseq0 + (size_t)t * a.Nrows * GH);
         };
         GrpCl ka, kb;
@@ -464,7 +432,7 @@ __device__ __forceinline__ void group_body(const GrpArgs& a, int cluster_a, int 
                 // slot s & 1 held h1_{s-2}: read by every member in step s - 1, which they have left (flag1 >= s above)
                 cell(k, acc, reinterpret_cast<float*>(reinterpret_cast<char*>(k.hx1) + slot1(s)),
                      TRAIN ? a.gates1 + (size_t)s * a.Nrows * 4 * GH : nullptr, TRAIN ? a.cseq1 + (size_t)s * a.Nrows * GH : nullptr);
-                publish(k.fl1 + member, (unsigned)s + 1);
+                fsn_publish(k.fl1 + member, (unsigned)s + 1);
                 if (TRAIN && SAVE) save_cell(k, acc, a.gates1 + (size_t)s * a.Nrows * 4 * GH, a.cseq1 + (size_t)s * a.Nrows * GH);
             }
         };

@@ -11,8 +11,8 @@
 //       first sub-band layer), with or without left-over tiles beside it
 //   lstm_rec_in_kernel<384, RT, 2, GRU = true, KX = 1 | 2, ROWSIN = true>  the same for nn.GRU (fsn_gru_layer_forward,
 //       fsn_api_gru.hip), weights expanded to the four-gate cell of lstm_cell.h
-#include "fsn_common.h"
 #include "lstm_cell.h"
+#include "persist_sync.h"
 
 namespace {
 
@@ -132,12 +132,9 @@ __global__ __launch_bounds__((H / (16 * UG)) * 64) __attribute__((amdgpu_num_vgp
     stage.commit(xin, xl, XS, n0);
     __syncthreads();
 
-    const __amdgpu_buffer_rsrc_t wrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w_p), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = fsn_buffer_rsrc(w_p);
     const unsigned lane16 = (unsigned)lane * 16u;
-    auto wload = [&](unsigned ofs) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane16, ofs * 4u, 0));
-    };
+    auto wload = [&](unsigned ofs) { return fsn_buffer_load<f32x4>(wrsrc, lane16, ofs * 4u); };
     auto wxofs = [&](int g, int u) { return (unsigned)((g * KC + wave * UG + u) * KX) * 256u; };
     auto whofs = [&](int g, int u) { return whh_off + (unsigned)((g * KC + wave * UG + u) * KC) * 256u; };
     f32x4 b0[UG], b1[UG];
@@ -272,37 +269,27 @@ __global__ __launch_bounds__((H / (16 * UG)) * 64) __attribute__((amdgpu_num_vgp
                     ha23 += 6 * 16;
                 }
             }
-#define FSN_REC_EPILOGUE2(VAR, EXPR)                                                                  \
-    _Pragma("unroll") for (int rt = 0; rt < RT; ++rt)                                                 \
-    _Pragma("unroll") for (int u = 0; u < UG; ++u) {                                                  \
-        const f32x4 A = acc[rt][u], C = cst[rt][u], M = tmp[rt][u];                                   \
-        (void)A, (void)C, (void)M;                                                                    \
-        auto half = [&](f32x2 a, f32x2 c, f32x2 m) { (void)a, (void)c, (void)m; return EXPR; };       \
-        VAR[rt][u] = cat2(half(lo2(A), lo2(C), lo2(M)), half(hi2(A), hi2(C), hi2(M)));                \
-        asm volatile("" : "+v"(VAR[rt][u]));                                                          \
-    }
             if constexpr (GRU) {  // cst = h_{t-1} (and h_t after the z pass); tmp: r, r * (W_hn h + b_hn), n
                 if (pass == 0) {
-                    FSN_REC_EPILOGUE2(tmp, sigmoid_fast2(a))
+                    FSN_CELL_PASS2(tmp, sigmoid_fast2(a))
                     if (more) stage.commit(xin, xl + ((t + 1) & 1) * ROWS * XS, XS, n0);
                 } else if (pass == 1) {
-                    FSN_REC_EPILOGUE2(tmp, m * a)
+                    FSN_CELL_PASS2(tmp, m * a)
                 } else if (pass == 2) {
-                    FSN_REC_EPILOGUE2(tmp, tanh_fast2(a + m))
+                    FSN_CELL_PASS2(tmp, tanh_fast2(a + m))
                 } else {
-                    FSN_REC_EPILOGUE2(cst, m + sigmoid_fast2(a) * (c - m))
+                    FSN_CELL_PASS2(cst, m + sigmoid_fast2(a) * (c - m))
                 }
             } else if (pass == 0) {
-                FSN_REC_EPILOGUE2(cst, sigmoid_fast2(a) * c)
+                FSN_CELL_PASS2(cst, sigmoid_fast2(a) * c)
                 if (more) stage.commit(xin, xl + ((t + 1) & 1) * ROWS * XS, XS, n0);  // tmp's registers are free here
             } else if (pass == 1) {
-                FSN_REC_EPILOGUE2(tmp, sigmoid_fast2(a))
+                FSN_CELL_PASS2(tmp, sigmoid_fast2(a))
             } else if (pass == 2) {
-                FSN_REC_EPILOGUE2(cst, c + m * tanh_fast2(a))
+                FSN_CELL_PASS2(cst, c + m * tanh_fast2(a))
             } else {
-                FSN_REC_EPILOGUE2(tmp, sigmoid_fast2(a) * tanh_fast2(c))
+                FSN_CELL_PASS2(tmp, sigmoid_fast2(a) * tanh_fast2(c))
             }
-#undef FSN_REC_EPILOGUE2
             __builtin_amdgcn_sched_barrier(0);
         }
         // every wave has finished reading h_{t-1}

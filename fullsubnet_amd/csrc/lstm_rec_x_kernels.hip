@@ -10,8 +10,8 @@
 //       I == H, with or without left-over tiles beside it)
 //   lstm_rec_x_kernel<384, RT, 2, GRU = true, HSEQ = true>    the same for nn.GRU (fsn_gru_layer_forward, fsn_api_gru.hip);
 //       the GRU's output layer is a separate launch, so there is no fused GRU form
-#include "fsn_common.h"
 #include "lstm_cell.h"
+#include "persist_sync.h"
 
 namespace {
 
@@ -31,41 +31,8 @@ namespace {
 // landed: it is older than a dozen weight fragments the wave has consumed since, and loads return in order).
 // Output layer fused exactly as in lstm_rec_kernel (the hidden sequence of this layer is never stored).
 // ---------------------------------------------------------------------------------------------
-// One 16-byte-per-lane LDS-DMA fragment (1 KB per wave): lane l's 16 bytes at `g` land at LDS byte address
-// lds_base + 16 l.  Written as asm so that the compiler neither serialises later LDS reads behind it (it cannot tell
-// the ring stages apart and would wait for vmcnt(0) before every ds_read) nor counts it in its own vmcnt bookkeeping
-// (an extra, OLDER request in the queue can only make its counted waits longer, never too short).
+// The fragment is persist_sync.h's fsn_lds_dma (vector address) / fsn_lds_dma_s (wave-uniform base + lane offset).
 // (Non-temporal / sc0 sc1 fills were measured in round 5: +0.4 .. +0.8 ms - the slices are re-read from L2 / Infinity Cache.)
-__device__ __forceinline__ void lds_dma_fragment(const float* g, unsigned lds_base) {
-    unsigned saved;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, off\n\t"
-        "s_nop 0\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(saved)
-        : "s"(lds_base), "v"(g)
-        : "memory");
-}
-
-// The same with the source address as a wave-uniform base (scalar registers) + this lane's byte offset: no per-fragment
-// vector arithmetic at all.
-__device__ __forceinline__ void lds_dma_fragment_s(const float* sbase, unsigned lane_bytes, unsigned lds_base) {
-    unsigned saved;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, %3\n\t"
-        "s_nop 0\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(saved)
-        : "s"(lds_base), "v"(lane_bytes), "s"(sbase)
-        : "memory");
-}
-
 #ifndef FSN_REC_VCAP
 #define FSN_REC_VCAP 76  // x 2 on gfx950's unified register file = 152: three waves per SIMD + room for a step workgroup
 #endif
@@ -143,8 +110,8 @@ __global__ __launch_bounds__((H / (16 * UG)) * 64) __attribute__((amdgpu_num_vgp
         const float* src = xseq + ((long)t * Npad + n0) * H + sl * (SK * 16);  // wave-uniform
         for (int f = wave; f < NF; f += NW) {
             const int rt = f / SK, kcl = f - rt * SK;
-            lds_dma_fragment(src + (rt * 16 * H + kcl * 16) + xlane,
-                             __builtin_amdgcn_readfirstlane(xs_lds + (unsigned)((buf * NF + f) * 1024)));
+            fsn_lds_dma(src + (rt * 16 * H + kcl * 16) + xlane,
+                        __builtin_amdgcn_readfirstlane(xs_lds + (unsigned)((buf * NF + f) * 1024)));
         }
     };
     // FSA: the fills' addresses from scalar registers - a wave's fragments of a stage are the same (row
@@ -164,7 +131,7 @@ __global__ __launch_bounds__((H / (16 * UG)) * 64) __attribute__((amdgpu_num_vgp
 #pragma unroll
         for (int i = 0; i < FPW; ++i)
             if (NF % NW == 0 || wave + i * NW < NF)
-                lds_dma_fragment_s(src + fsa_src[i], xlane_bytes, (unsigned)(fsa_lds[i] + buf * (NF * 1024)));
+                fsn_lds_dma_s(src + fsa_src[i], xlane_bytes, (unsigned)(fsa_lds[i] + buf * (NF * 1024)));
     };
     fill(0, 0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -178,13 +145,10 @@ __global__ __launch_bounds__((H / (16 * UG)) * 64) __attribute__((amdgpu_num_vgp
     // elements behind it) = a wave-uniform part (scalar registers) + 256 kc, + this lane's 16 bytes
     // buffer loads (T8): resource descriptor + scalar byte offset + this lane's constant 16 l - no per-load VGPR
     // address arithmetic at all
-    const __amdgpu_buffer_rsrc_t wrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w_p), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = fsn_buffer_rsrc(w_p);
     const unsigned lane16 = (unsigned)lane * 16u;
     auto wofs = [&](int g, int u) { return (unsigned)((g * KC + wave * UG + u) * KC) * 256u; };
-    auto wload = [&](unsigned ofs) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane16, ofs * 4u, 0));
-    };
+    auto wload = [&](unsigned ofs) { return fsn_buffer_load<f32x4>(wrsrc, lane16, ofs * 4u); };
     float bias_n[UG];  // the bias of the coming pass, requested a pass ahead
     {
         int g0 = 1;
@@ -344,35 +308,25 @@ __global__ __launch_bounds__((H / (16 * UG)) * 64) __attribute__((amdgpu_num_vgp
                     ha23 += SK * 16;
                 }
             }
-#define FSN_REC_EPILOGUE2(VAR, EXPR)                                                                  \
-    _Pragma("unroll") for (int rt = 0; rt < RT; ++rt)                                                 \
-    _Pragma("unroll") for (int u = 0; u < UG; ++u) {                                                  \
-        const f32x4 A = acc[rt][u], C = cst[rt][u], M = tmp[rt][u];                                   \
-        (void)A, (void)C, (void)M;                                                                    \
-        auto half = [&](f32x2 a, f32x2 c, f32x2 m) { (void)a, (void)c, (void)m; return EXPR; };       \
-        VAR[rt][u] = cat2(half(lo2(A), lo2(C), lo2(M)), half(hi2(A), hi2(C), hi2(M)));                \
-        asm volatile("" : "+v"(VAR[rt][u]));                                                          \
-    }
             if constexpr (GRU) {  // cst = h_{t-1} (h_t after the z pass); tmp: r, r * (W_hn h + b_hn), n
                 if (pass == 0) {
-                    FSN_REC_EPILOGUE2(tmp, sigmoid_fast2(a))
+                    FSN_CELL_PASS2(tmp, sigmoid_fast2(a))
                 } else if (pass == 1) {
-                    FSN_REC_EPILOGUE2(tmp, m * a)
+                    FSN_CELL_PASS2(tmp, m * a)
                 } else if (pass == 2) {
-                    FSN_REC_EPILOGUE2(tmp, tanh_fast2(a + m))
+                    FSN_CELL_PASS2(tmp, tanh_fast2(a + m))
                 } else {
-                    FSN_REC_EPILOGUE2(cst, m + sigmoid_fast2(a) * (c - m))
+                    FSN_CELL_PASS2(cst, m + sigmoid_fast2(a) * (c - m))
                 }
             } else if (pass == 0) {
-                FSN_REC_EPILOGUE2(cst, sigmoid_fast2(a) * c)
+                FSN_CELL_PASS2(cst, sigmoid_fast2(a) * c)
             } else if (pass == 1) {
-                FSN_REC_EPILOGUE2(tmp, sigmoid_fast2(a))
+                FSN_CELL_PASS2(tmp, sigmoid_fast2(a))
             } else if (pass == 2) {
-                FSN_REC_EPILOGUE2(cst, c + m * tanh_fast2(a))
+                FSN_CELL_PASS2(cst, c + m * tanh_fast2(a))
             } else {
-                FSN_REC_EPILOGUE2(tmp, sigmoid_fast2(a) * tanh_fast2(c))
+                FSN_CELL_PASS2(tmp, sigmoid_fast2(a) * tanh_fast2(c))
             }
-#undef FSN_REC_EPILOGUE2
             __builtin_amdgcn_sched_barrier(0);
         }
         // every wave has finished reading h_{t-1}; the fill of the next step's first slice stays in flight

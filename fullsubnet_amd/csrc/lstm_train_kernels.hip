@@ -13,7 +13,7 @@
 // First, correctness-first version: one elementwise launch + one small GEMM per step.
 #include <stdlib.h>
 
-#include "fsn_common.h"
+#include "persist_sync.h"
 
 namespace {
 
@@ -432,19 +432,6 @@ constexpr int TH_STAGES = 4;             // (6 stages = 5 chunks in flight measu
 // against 2 x 24 KB)
 template <int WN>
 constexpr int th_stage_bytes() { return 2 * (12 + 6 * WN) * 512; }  // (A 12 + B 6 WN column tiles) x 2 k steps x 512 B
-__device__ __forceinline__ void th_lds_dma(const unsigned short* g, unsigned lds_base) {
-    unsigned saved;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, off\n\t"
-        "s_nop 0\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(saved)
-        : "s"(lds_base), "v"(g)
-        : "memory");
-}
 template <int AR, int WN>
 __global__ __launch_bounds__(WN * 128) void gemm_tn16h_kernel(const unsigned short* __restrict__ A, long lda,
                                                               const unsigned short* __restrict__ B, long ldb,
@@ -480,7 +467,7 @@ __global__ __launch_bounds__(WN * 128) void gemm_tn16h_kernel(const unsigned sho
         if (!loader) return;
         const unsigned dst = lds0 + (unsigned)((c % TH_STAGES) * TH_STAGE) + s_dst;
 #pragma unroll
-        for (int p = 0; p < 6; ++p) th_lds_dma(sp + (long)c * 32 * s_ld + 32 * p, dst + (unsigned)(p * 1024));
+        for (int p = 0; p < 6; ++p) fsn_lds_dma(sp + (long)c * 32 * s_ld + 32 * p, dst + (unsigned)(p * 1024));
     };
     f32x4 acc[6][6];
 #pragma unroll
@@ -713,8 +700,8 @@ __global__ __launch_bounds__(256) void gemm_tn16n_kernel(const unsigned short* _
     auto issue = [&](int c) {
         const unsigned st = lds0 + (unsigned)((c % TH_STAGES) * TNN_STAGE);
 #pragma unroll
-        for (int p = 0; p < 6; ++p) th_lds_dma(spa + (long)c * 32 * lda + 32 * p, st + dst_a + (unsigned)(p * 1024));
-        if (wave < 2) th_lds_dma(spb + (long)c * 32 * ldb, st + dst_b);
+        for (int p = 0; p < 6; ++p) fsn_lds_dma(spa + (long)c * 32 * lda + 32 * p, st + dst_a + (unsigned)(p * 1024));
+        if (wave < 2) fsn_lds_dma(spb + (long)c * 32 * ldb, st + dst_b);
     };
     f32x4 acc[6][2];
 #pragma unroll
