@@ -19,7 +19,8 @@ SOURCES = ["fft_kernels.hip", "dft_kernels.hip", "elementwise_kernels.hip", "gem
            "gemm_f16x3_kernels.hip", "lstm_rec_kernels.hip", "lstm_rec_in_kernels.hip", "lstm_rec_x_kernels.hip",
            "lstm_step_kernels.hip", "lstm_group_kernels.hip",
            "lstm_group_bptt_kernels.hip", "lstm_group16_kernels.hip", "fb_chain_kernels.hip", "fb_chain_bptt_kernels.hip",
-           "lstm_f16x3_kernels.hip", "lstm_train_kernels.hip", "gru_kernels.hip", "optim_kernels.hip",
+           "lstm_f16x3_kernels.hip", "bptt_step_kernels.hip", "gemm_tn_kernels.hip", "gemm_tn16_kernels.hip",
+           "gru_kernels.hip", "optim_kernels.hip",
            "norm_kernels.hip", "section_kernels.hip", "train_glue_kernels.hip", "fast_glue_kernels.hip",
            "stream_pool_kernels.hip",
            "fsn_api.hip", "fsn_api_fullsubnet.hip", "fsn_api_layers.hip", "fsn_api_gru.hip", "fsn_api_train.hip"]

@@ -307,16 +307,14 @@ static int launch_dft_stft(const float* y, int B, int L, const float* window, fl
         const long frames = (long)B * T;
         const unsigned grid = (unsigned)(frames < 1024 ? frames : 1024);
         if (5 * N * sizeof(double) > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft2_stft_kernel<kRagged>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(5 * N * sizeof(double)));
+            (void)fsn_request_lds(dft2_stft_kernel<kRagged>, 5 * N * sizeof(double));
         hipLaunchKernelGGL(dft2_stft_kernel<kRagged>, dim3(grid), dim3(256), 5 * N * sizeof(double), s, y, window, re, im, mag,
                            L, T, N, hop, F, P, N / P, frames, lengths);
         return fsn_check_launch("dft2_stft_kernel");
     }
     const size_t lds = 3 * N * sizeof(double);  // 96 KB at N = 4096: above 64 KB a launch needs the attribute raised
     if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft_stft_kernel<kRagged>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)fsn_request_lds(dft_stft_kernel<kRagged>, lds);
     hipLaunchKernelGGL(dft_stft_kernel<kRagged>, dim3((unsigned)(B * T), (F + 255) / 256), dim3(256), lds, s, y, window, re, im,
                        mag, L, T, N, hop, F, lengths);
     return fsn_check_launch("dft_stft_kernel");
@@ -331,16 +329,14 @@ static int launch_dft_istft(const float* re, const float* im, const float* windo
         const long frames = (long)B * T;
         const unsigned grid = (unsigned)(frames < 1024 ? frames : 1024);
         if (6 * N * sizeof(double) > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft2_irfft_kernel<kRagged>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(6 * N * sizeof(double)));
+            (void)fsn_request_lds(dft2_irfft_kernel<kRagged>, 6 * N * sizeof(double));
         hipLaunchKernelGGL(dft2_irfft_kernel<kRagged>, dim3(grid), dim3(256), 6 * N * sizeof(double), s, re, im, window, wframes,
                            T, N, F, P, N / P, frames, lengths, length, hop);
         FSN_TRY_LAUNCH("dft2_irfft_kernel");
     } else {
         const size_t lds = (2 * F + 2 * N) * sizeof(double);
         if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft_irfft_kernel<kRagged>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            (void)fsn_request_lds(dft_irfft_kernel<kRagged>, lds);
         hipLaunchKernelGGL(dft_irfft_kernel<kRagged>, dim3((unsigned)(B * T), (N + 255) / 256), dim3(256), lds, s, re, im, window,
                            wframes, T, N, F, lengths, length, hop);
         FSN_TRY_LAUNCH("dft_irfft_kernel");

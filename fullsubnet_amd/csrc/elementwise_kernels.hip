@@ -350,8 +350,7 @@ __global__ __launch_bounds__(256) void hog_kernel(unsigned long long ticks, floa
 }
 int fsn_launch_hog(int workgroups, int lds_bytes, int heavy, unsigned long long ticks, float* sink, hipStream_t s) {
     if (lds_bytes > 64 * 1024) {  // above 64 KB of dynamic LDS a kernel opts in
-        (void)hipFuncSetAttribute(heavy ? (const void*)hog_kernel<true> : (const void*)hog_kernel<false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        (void)fsn_request_lds(heavy ? hog_kernel<true> : hog_kernel<false>, (size_t)lds_bytes);
         (void)hipGetLastError();
     }
     if (heavy) hipLaunchKernelGGL((hog_kernel<true>), dim3(workgroups), dim3(256), (size_t)lds_bytes, s, ticks, sink);

@@ -3,6 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <map>
+#include <mutex>
+#include <utility>
+
 #include "../../include/fsn_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -43,6 +47,41 @@ struct FsnCallScope {
     ~FsnCallScope();
 };
 int fsn_check_launch(const char* what);
+
+// Raise `kernel`'s dynamic-LDS limit to at least `bytes` on the current device, before a launch that asks for more than
+// the 64 KB every kernel may have.  Called at every such launch; the runtime is asked once per (device, kernel) and size
+// that grows - the limit belongs to that pair, so the record is keyed by it, and it is kept under a mutex (the per-launcher
+// `static bool` flags this replaces skipped a process's second device and raced between threads; with no record at all
+// the training figures were not reliably inside the parent's range: profiles/gemm_tn_split.md).
+// fsn_request_lds: false on failure, nothing refused and nothing recorded - for the launches the runtime was measured to
+// accept anyway; fsn_reserve_lds: the launcher's return value, the failure on record as "<what>: cannot reserve ..".
+inline bool fsn_request_lds_of(const void* kernel, size_t bytes) {
+    static std::mutex mu;
+    static std::map<std::pair<int, const void*>, size_t> raised;  // (device, kernel) -> the limit it has been given
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return false;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& have = raised[{dev, kernel}];
+    if (have >= bytes) return true;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
+    have = bytes;
+    return true;
+}
+template <class Kernel>
+inline bool fsn_request_lds(Kernel kernel, size_t bytes) {
+    return fsn_request_lds_of(reinterpret_cast<const void*>(kernel), bytes);
+}
+template <class Kernel>
+inline int fsn_reserve_lds(const char* what, Kernel kernel, size_t bytes) {
+    if (fsn_request_lds(kernel, bytes)) return FSN_OK;
+    fsn_set_error("%s: cannot reserve %zu bytes of LDS", what, bytes);
+    return FSN_ERR_LAUNCH;
+}
+#define FSN_TRY_RESERVE_LDS(what, kernel, bytes)                   \
+    do {                                                           \
+        const int _rc = fsn_reserve_lds(what, kernel, bytes);      \
+        if (_rc != FSN_OK) return _rc;                             \
+    } while (0)
 
 #define FSN_TRY_LAUNCH(what)                        \
     do {                                            \
@@ -383,7 +422,7 @@ size_t fsn_section_input_workspace_floats(int B, int F);
 int fsn_launch_section_input(const float* noisy, const float* fb, int B, int F, int T, int lower, int units, int sc, int sn,
                              int fc, int fn, int u_lo, int u_hi, float eps, float* out, int Np, int ldo, void* workspace,
                              hipStream_t s, const int* frames = nullptr);  // frames (device, [B]): a ragged batch
-void fsn_tn_plan_splits(int M, int Nc, long K, int arith, int* splits, long* bound);  // lstm_train_kernels.hip (test hook)
+void fsn_tn_plan_splits(int M, int Nc, long K, int arith, int* splits, long* bound);  // gemm_tn_kernels.hip (test hook)
 // nn.Linear with O <= 4 outputs and I % 64 == 0 inputs as row dot products / outer products (gemm_kernels.hip)
 bool fsn_linear_small_out_ok(int I, int O, long ldx);
 int fsn_launch_linear_small_out(const float* x, long ldx, const float* w, const float* b, float* y, long R, int I, int O,
@@ -495,13 +534,24 @@ int fsn_launch_fb_chain(const float* gx0, const float* whh0_p, const float* wih1
 int fsn_launch_gru_expand4(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* w_ih4, float* w_hh4,
                            float* b4, int I, int H, hipStream_t s, int order = 0);
 
-// lstm_train_kernels.hip (training step: BPTT pieces)
+// gemm_tn_kernels.hip (training step: weight gradients)
 // C [M][Nc] = sum_k A[k][M]^T B[k][Nc]   (both operands row-major over k; split-K, deterministic 2-pass)
 size_t fsn_gemm_tn_workspace_bytes(int M, int Nc, long K);
 int fsn_launch_gemm_tn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int Nc, long K,
                        void* workspace, hipStream_t s, float* colsum_out = nullptr, int arith = FSN_ARITH_F32);
 int fsn_launch_colsum(const float* A, long lda, float* out, int cols, long rows, void* workspace, hipStream_t s);
-// the same product with both operands 16-bit in memory (LDS-DMA staging, transposing LDS reads); workspace as above
+size_t fsn_colsum_workspace_bytes(int cols, long rows);
+// its split-K plan (host code), shared with the 16-bit-operand forms
+struct FsnTnPlan {
+    int m_blocks, n_blocks, splits, narrow;
+    int square;  // 192 x 192 tiles, every K split's tiles on one XCD (bandwidth-bound under the 16-bit arithmetic)
+    long k_per_split;
+};
+FsnTnPlan fsn_tn_plan(int M, int Nc, long K, int arith = FSN_ARITH_F32, bool allow_square = true);
+long fsn_tn_max_splits(int M, int Nc);
+constexpr size_t kFsnTnOnePerCu = 96 * 1024;  // LDS reservation (never touched): one workgroup per CU
+// gemm_tn16_kernels.hip: the same product with both operands 16-bit in memory (LDS-DMA staging, transposing LDS reads);
+// workspace as above
 bool fsn_gemm_tn16h_supported(int M, int Nc, long K);
 bool fsn_gemm_tn16n_supported(int M, int Nc, long K);  // the narrow form (Nc <= 32) and dx from the 16-bit gate gradients
 int fsn_launch_gemm_tn16n(const void* A16, long lda, const void* B16, long ldb, float* C, long ldc, int M, int Nc, long K,
@@ -511,7 +561,7 @@ int fsn_launch_gemm_dx16(const void* dg16, long ld16, const float* w, void* wfra
                          hipStream_t s, int arith);
 int fsn_launch_gemm_tn16h(const void* A16, long lda, const void* B16, long ldb, float* C, long ldc, int M, int Nc, long K,
                           void* workspace, hipStream_t s, int arith);
-size_t fsn_colsum_workspace_bytes(int cols, long rows);
+// bptt_step_kernels.hip (training step: BPTT one step at a time)
 int fsn_launch_bptt_step(const float* dh_out, const float* dgates_next, const float* whhT_p, float* dc,
                          const float* gates, const float* c_t, const float* c_prev, float* dgates, int row_tiles, int H,
                          int last, int first, hipStream_t s);

@@ -230,15 +230,7 @@ int fsn_launch_pack_f16x3(const float* w, void* packed, int n_out, int k, hipStr
 int fsn_launch_gemm_f16x3(const float* A, long lda, const void* packed, const float* bias, float* C, long row_tiles,
                           int n_out, int k, hipStream_t s) {
     const size_t lds = (size_t)2 * kLdsStageHalves * sizeof(_Float16);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16x3_lds_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            fsn_set_error("gemm_f16x3: cannot reserve %zu bytes of LDS", lds);
-            return FSN_ERR_LAUNCH;
-        }
-        attr_set = true;
-    }
+    FSN_TRY_RESERVE_LDS("gemm_f16x3", gemm_f16x3_lds_kernel, lds);
     const int cus = plan_cus();
     const f16x8* whi = static_cast<const f16x8*>(packed);
     const f16x8* wlo = whi + (size_t)n_out * k / 8;

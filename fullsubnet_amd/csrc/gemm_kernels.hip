@@ -299,15 +299,10 @@ int launch(const FsnGemmA& a, const float* wp, const FsnGemmC& c, int row_tiles,
     const long nrb = ((long)row_tiles + WR * RTW - 1) / (WR * RTW);
     const long ncb = (col_tiles + WC * CTW - 1) / (WC * CTW);
     auto kern = gemm_kernel<AKIND, CKIND, RTW, CTW, WR, WC, PF>;
+    if (lds_reserve > 64 * 1024) FSN_TRY_RESERVE_LDS("gemm", kern, lds_reserve);
     static int occ = 0;  // per instantiation
     if (occ == 0) {
         int n = 0;
-        if (lds_reserve > 64 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_reserve) != hipSuccess) {
-            fsn_set_error("gemm: cannot reserve %zu bytes of LDS", lds_reserve);
-            return FSN_ERR_LAUNCH;
-        }
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, WR * WC * 64, lds_reserve) != hipSuccess || n < 1)
             n = 1;
         occ = n;

@@ -2,7 +2,7 @@
 // unidirectional, h0 = 0.  PyTorch's cell (gate rows r, z, n of weight_ih / weight_hh):
 //   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr)        z = sigmoid(W_iz x + b_iz + W_hz h + b_hz)
 //   n = tanh(W_in x + b_in + r * (W_hn h + b_hn))     h' = n + z * (h - n)
-// Same execution shape as the LSTM step kernels (lstm_step_kernels.hip / lstm_train_kernels.hip): the input
+// Same execution shape as the LSTM step kernels (lstm_step_kernels.hip / bptt_step_kernels.hip): the input
 // projection of all steps is one GEMM (fragment-ordered gx, bias = b_ih + [b_hr, b_hz, 0]); each step is
 // one launch whose workgroups own RTS 16-row tiles x one 16-unit group x the three gates, 4 waves =
 // 4-way split-K reduced through LDS in a fixed order.  Training keeps r, z, n and hn = W_hn h + b_hn.

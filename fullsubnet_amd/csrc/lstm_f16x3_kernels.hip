@@ -244,11 +244,7 @@ int launch(const float* gx, const FsnSbInput& xin, const void* wih_packed, const
     const size_t lds = (size_t)2 * RT * 16 * (H + 8) * sizeof(_Float16) +
                        (XIN ? (size_t)4 * RT * 16 * kXSH * sizeof(_Float16) : (size_t)2 * H * sizeof(float));
     auto kern = lstm_rec_f16x3_kernel<H, RT, UG, XIN>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess) {
-        fsn_set_error("lstm_rec_f16x3: cannot reserve %zu bytes of LDS", lds);
-        return FSN_ERR_LAUNCH;
-    }
+    FSN_TRY_RESERVE_LDS("lstm_rec_f16x3", kern, lds);
     const f16x8* whi = static_cast<const f16x8*>(packed);
     const f16x8* wlo = whi + (size_t)4 * H * H / 8;
     const f16x8* wxh = static_cast<const f16x8*>(wih_packed);

@@ -437,7 +437,7 @@ __global__ __launch_bounds__(256, 2) void lstm2_g16_fwd_kernel(const G16FwdArgs 
 }
 
 // ---- back-propagation through time --------------------------------------------------------------------------------
-// Per step t = T-1 .. 0 (formulas: lstm_train_kernels.hip):
+// Per step t = T-1 .. 0 (formulas: bptt_step_kernels.hip):
 //   layer 1: dh1_t = dH1_t + dgates1_{t+1} W_hh1;   layer 0: dh0_t = dgates1_t W_ih1 + dgates0_{t+1} W_hh0
 // Member m owns the 48 units [48 m, 48 m + 48) of dh for the cluster's 64 rows, transposed: D^T[unit][row] = sum over ALL
 // 1536 gate columns.  The gate gradients travel between members as a 16-BIT copy in matrix-operand FRAGMENT order -

@@ -1,7 +1,7 @@
 // Back-propagation through time of the sub-band model's two LSTM layers (training step, fullsubnet/trainer.py:56-63
 // through sequence_model.py:52-58) as ONE persistent launch: the mirror image of lstm_group_kernels.hip.
 //
-// Per step t = T-1 .. 0 (formulas: lstm_train_kernels.hip):
+// Per step t = T-1 .. 0 (formulas: bptt_step_kernels.hip):
 //   layer 1: dh1_t = dH1_t (from the output layer) + dgates1_{t+1} W_hh1          -> cell derivative -> dgates1_t
 //   layer 0: dh0_t = dgates1_t W_ih1 (the layer-to-layer dX, no GEMM) + dgates0_{t+1} W_hh0 -> ... -> dgates0_t
 // As 2 x 193 launches of bptt_step_kernel plus a dX GEMM this cost 14.6 + 1.9 ms of a 50.5 ms training step (one step:

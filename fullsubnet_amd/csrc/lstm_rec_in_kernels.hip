@@ -328,12 +328,11 @@ int launch_rec_in(const FsnSbInput* xin, const float* whh_p, float* hseq, int Tp
     constexpr int NW = H / (16 * UG);
     const size_t lds = ((size_t)RT * 16 * (H + 4) + (size_t)2 * RT * 16 * (16 * KX + 4)) * sizeof(float);
     auto kern = lstm_rec_in_kernel<H, RT, UG, CELL != 0, KX, ROWSIN>;
-    if (lds > 160 * 1024 ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess) {
+    if (lds > 160 * 1024) {
         fsn_set_error("lstm_rec_in: cannot reserve %zu bytes of LDS", lds);
         return FSN_ERR_LAUNCH;
     }
+    FSN_TRY_RESERVE_LDS("lstm_rec_in", kern, lds);
     hipLaunchKernelGGL(kern, dim3((unsigned)main_wgs), dim3(NW * 64), lds, s, *xin, xin->wih_p,
                        (unsigned)(whh_p - xin->wih_p), hseq, Tp, Npad);
     return fsn_check_launch("lstm_rec_in_kernel");

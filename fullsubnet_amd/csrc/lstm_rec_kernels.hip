@@ -402,12 +402,11 @@ int launch_rec(const float* gx, const FsnSbInput* xin, const float* whh_p, float
     void (*kern)(const float*, const FsnSbInput, const float*, float*, int, int, const FsnRecFc) =
         lstm_rec_kernel<H, RT, UG, XIN>;
     if constexpr (RT <= 1) kern = lstm_rec_small_kernel<H, RT, UG, XIN>;
-    if (lds > 160 * 1024 ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess) {
+    if (lds > 160 * 1024) {
         fsn_set_error("lstm_rec: cannot reserve %zu bytes of LDS", lds);
         return FSN_ERR_LAUNCH;
     }
+    FSN_TRY_RESERVE_LDS("lstm_rec", kern, lds);
     hipLaunchKernelGGL(kern, dim3((unsigned)main_wgs), dim3(NW * 64), lds, s, gx, XIN ? *xin : FsnSbInput{}, whh_p,
                        hseq, Tp, Npad, fuse ? *fc : FsnRecFc{});
     return fsn_check_launch("lstm_rec_kernel");

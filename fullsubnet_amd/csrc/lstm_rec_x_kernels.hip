@@ -402,12 +402,11 @@ int launch_rec_x(const float* xseq, const float* wih_p, const float* whh_p, cons
     constexpr int NW = H / (16 * UG);
     const size_t lds = ((size_t)RT * 16 * (H + 4) + 2 * H + (size_t)2 * RT * 6 * 256) * sizeof(float);
     auto kern = lstm_rec_x_kernel<H, RT, UG, CELL != 0, HSEQ>;
-    if (lds > 160 * 1024 ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess) {
+    if (lds > 160 * 1024) {
         fsn_set_error("lstm_rec_x: cannot reserve %zu bytes of LDS", lds);
         return FSN_ERR_LAUNCH;
     }
+    FSN_TRY_RESERVE_LDS("lstm_rec_x", kern, lds);
     if (whh_p < wih_p || whh_p - wih_p > 0x3fffffffL) {
         fsn_set_error("lstm_rec_x: W_hh must follow W_ih in one packed buffer");
         return FSN_ERR_ARG;

@@ -272,8 +272,7 @@ extern "C" int fsn_norm(const float* x, float* y, int norm_type, int B, int C, i
     FSN_REQUIRE(d.R <= 0x7fffffffL && scan_lds <= 144 * 1024, "norm: too many statistic rows or frames (T <= %d)",
                 FSN_NORM_MAX_FRAMES);
     if (scan_lds > 64 * 1024) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(norm_scan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)scan_lds);
+        (void)fsn_request_lds(norm_scan_kernel, scan_lds);
         (void)hipGetLastError();
     }
     double* s1 = static_cast<double*>(workspace);

@@ -3,7 +3,7 @@ python -m pytest tests/test_gpu_linear_sweep.py -m gpu -s
 
 Every nn.Linear and every weight / bias gradient of a training step runs through these two entries: the packed NN GEMM of
 gemm_kernels.hip, the linear_small_out / linear_small_dx row-dot kernels, and the split-K C = A^T B family with its column
-sums in lstm_train_kernels.hip, whose host side picks one of five code paths from the shape alone.  TABLE below has one
+sums in gemm_tn_kernels.hip, whose host side picks one of five code paths from the shape alone.  TABLE below has one
 row per shape, named after the path it is there for; the entries are called through fullsubnet_amd._lib directly so that
 ldx, lddy, lddx and the three call forms of the backward are the test's to choose.
 

@@ -43,7 +43,7 @@ Fixed on the way: train-group-left0 T190 N1536 I20 (fsn_lstm2_forward_train + fs
 relative Frobenius error of dw_hh0 at 2.32e-6 against 4.38e-7 of the yardstick (5.3 x), dw_ih1 2.31e-6 against 3.58e-7 (6.5 x),
 dw_hh1 2.24e-6 against 3.56e-7 (6.3 x).  These are the [4H][H] weight-gradient products over K = T N = 291 840 rows:
 fsn_launch_gemm_tn split K sixteen ways (one workgroup per CU), one fp32 chain of 18 240 rows per split.  It now forms a
-product whose splits would exceed 4096 rows in K segments of 2048 rows per split, summed in a fixed order (lstm_train_kernels.hip);
+product whose splits would exceed 4096 rows in K segments of 2048 rows per split, summed in a fixed order (gemm_tn_kernels.hip);
 after: dw_hh0 1.01e-6 (2.6 x torch's fp32), dw_ih1 7.8e-7 (2.2 x), dw_hh1 7.7e-7 (2.2 x); the row's y 3.5 x, dx 2.5 x unchanged.
 
 Seen on an MI355X, all 88 rows, 154 s, every plan assertion holding (also under FSN_WS_CANARY=1 before the K-segment fix):

@@ -5,7 +5,7 @@
 // experiment switch.
 #include <cstdio>
 #include <cstdlib>
-#include "../fullsubnet_amd/csrc/lstm_train_kernels.hip"
+#include "../fullsubnet_amd/csrc/gemm_tn_kernels.hip"
 void fsn_set_error(const char*, ...) {}
 int fsn_check_launch(const char*) { return hipGetLastError() == hipSuccess ? 0 : -3; }
 __global__ void fill_kernel(float* p, size_t n, unsigned seed, float scale) {
