@@ -138,6 +138,18 @@ SIGNATURES = {
     "fsn_fullsubnet_stream_workspace_bytes": (_c.c_size_t, [_c.POINTER(Cfg), _c.c_int, _c.c_int]),
     "fsn_fullsubnet_stream_step": (_c.c_int, [_c.POINTER(Cfg), _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _f32p,
                                               _c.c_int, _c.c_int, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_fullsubnet_segment_state_bytes": (_c.c_size_t, [_c.POINTER(Cfg), _c.c_int]),
+    "fsn_fullsubnet_segment_workspace_bytes": (_c.c_size_t, [_c.POINTER(Cfg), _c.c_int, _c.c_int]),
+    "fsn_fullsubnet_segment_stats": (_c.c_int, [_c.POINTER(Cfg), _c.c_void_p, _c.c_size_t, _f32p, _c.c_int, _c.c_int,
+                                                _c.c_void_p]),
+    "fsn_fullsubnet_segment_fullband": (_c.c_int, [_c.POINTER(Cfg), _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int,
+                                                   _c.c_void_p, _f32p, _c.c_int, _c.c_int, _f32p, _c.c_void_p, _c.c_size_t,
+                                                   _c.c_void_p]),
+    "fsn_fullsubnet_segment_subband": (_c.c_int, [_c.POINTER(Cfg), _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int,
+                                                  _c.c_void_p, _f32p, _f32p, _c.c_int, _c.c_int, _f32p, _c.c_void_p,
+                                                  _c.c_size_t, _c.c_void_p]),
+    "fsn_fullsubnet_segment_divisors": (_c.c_int, [_c.POINTER(Cfg), _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_int, _f32p,
+                                                   _f32p, _c.c_void_p]),
     "fsn_fullsubnet_stream_pool_state_bytes": (_c.c_size_t, [_c.POINTER(Cfg), _c.c_int]),
     "fsn_fullsubnet_stream_pool_workspace_bytes": (_c.c_size_t, [_c.POINTER(Cfg), _c.c_int, _c.c_int]),
     "fsn_fullsubnet_stream_pool_reset": (_c.c_int, [_c.POINTER(Cfg), _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p,

@@ -98,6 +98,16 @@ __global__ __launch_bounds__(64 * kBinsumTG) void binsum_kernel(const float* __r
     }
 }
 
+// m[f] of the sub-band divisor below in closed form: pairs (u, k), u in [0, F), k in [-nb, nb], whose source bin is f -
+// directly (u + k = f), mirrored at the low edge (u + k = -f) or at the high edge (u + k = 2 (F - 1) - f); checked
+// against the brute-force count in tests/test_host_cpu.py
+__device__ __forceinline__ int unfold_multiplicity(int f, int F, int nb) {
+    const int direct = min(nb, f) - max(-nb, f - (F - 1)) + 1;
+    const int low = f >= 1 ? max(0, min(F - 1, nb - f) + 1) : 0;
+    const int high = f <= F - 2 ? max(0, F - max(0, 2 * (F - 1) - f - nb)) : 0;
+    return direct + low + high;
+}
+
 // offline_laplace_norm (base_model.py:204-218): one mean per utterance, eps 1e-5.
 //   which == 0: den_fb[b] = mean_{f,t}(mag) + 1e-5                        (fullsubnet/model.py:92)
 //   which == 1: den_sb[b] = mean over the concatenated [F, 2nb+2, Tp] sub-band tensor + 1e-5
@@ -121,13 +131,7 @@ __global__ __launch_bounds__(256) void offline_den_kernel(const double* __restri
         if (threadIdx.x == 0) den_fb[b] = (float)(tot / ((double)F * Tpb)) + 1e-5f;
     } else {
         for (int f = threadIdx.x; f < F; f += blockDim.x) {
-            // m[f] in closed form: pairs (u, k), u in [0, F), k in [-nb, nb], whose source bin is f -
-            // directly (u + k = f), mirrored at the low edge (u + k = -f) or at the high edge
-            // (u + k = 2 (F - 1) - f); checked against the brute-force count in tests/test_host_cpu.py
-            const int direct = min(nb, f) - max(-nb, f - (F - 1)) + 1;
-            const int low = f >= 1 ? max(0, min(F - 1, nb - f) + 1) : 0;
-            const int high = f <= F - 2 ? max(0, F - max(0, 2 * (F - 1) - f - nb)) : 0;
-            acc += (double)(direct + low + high) * binsum[(long)b * FP + f];
+            acc += (double)unfold_multiplicity(f, F, nb) * binsum[(long)b * FP + f];
         }
         // columns F..FP-1 of fb_out are written as zeros by the output layer: whole rows can be summed
         const f32x4* p = reinterpret_cast<const f32x4*>(fb_out + (long)b * Tp * FP);
@@ -137,6 +141,73 @@ __global__ __launch_bounds__(256) void offline_den_kernel(const double* __restri
         }
         const double tot = fsn_block_sum(acc, scratch);
         if (threadIdx.x == 0) den_sb[b] = (float)(tot / ((double)F * (2 * nb + 2) * Tpb)) + 1e-5f;
+    }
+}
+
+// ---- the offline norm of a recording that arrives in segments (fsn_fullsubnet_segment_*) ---------------------------------
+// Its two divisors are sums over the whole recording; the segment entries keep them as fp64 accumulators in the caller's
+// state and add one segment at a time.  Each kernel below sums its segment in a fixed order and then adds ONE value per
+// accumulator, so a run is deterministic for a given segmentation (two segmentations differ by fp64 rounding only).
+//
+// binsum[b][f] += sum_t mag[b][f][t], mag in the CALLER's layout [B][F][k] (frames contiguous): a wave per bin, the lanes
+// walk the frames 64 apart with two loads in flight, a fixed butterfly joins them.
+__global__ __launch_bounds__(256) void binsum_accumulate_kernel(const float* __restrict__ mag, double* __restrict__ binsum,
+                                                                int F, int FP, int k) {
+    const int b = blockIdx.y, f = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (f >= F) return;  // whole waves leave; no barrier below
+    const float* p = mag + ((long)b * F + f) * k;
+    double a0 = 0.0, a1 = 0.0;
+    int t = lane;
+    for (; t + 64 < k; t += 128) {
+        const float v0 = p[t], v1 = p[t + 64];
+        a0 += (double)v0;
+        a1 += (double)v1;
+    }
+    if (t < k) a0 += (double)p[t];
+    double acc = a0 + a1;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    if (lane == 0) binsum[(long)b * FP + f] += acc;
+}
+
+// acc[b] += sum of x[b][t][0 .. FP) over the frames t of this segment with frames_done + t < total_frames[b]
+// (x = the full-band output, frame-major [B][k][FP], columns F .. FP - 1 zero: whole rows are summed, as offline_den_kernel does)
+__global__ __launch_bounds__(256) void masked_sum_accumulate_kernel(const float* __restrict__ x, double* __restrict__ acc_out,
+                                                                    const int* __restrict__ total_frames, int frames_done,
+                                                                    int k, int FP) {
+    __shared__ double scratch[4];
+    const int b = blockIdx.x;
+    long n = (long)total_frames[b] - frames_done;  // this row's frames inside the segment
+    n = n < 0 ? 0 : (n > k ? k : n);
+    const f32x4* p = reinterpret_cast<const f32x4*>(x + (long)b * k * FP);
+    double acc = 0.0;
+    for (long i = threadIdx.x; i < n * FP / 4; i += blockDim.x) {
+        const f32x4 v = p[i];
+        acc += ((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3]);
+    }
+    const double tot = fsn_block_sum(acc, scratch);
+    if (threadIdx.x == 0) acc_out[b] += tot;
+}
+
+// The two divisors of offline_den_kernel from the finished accumulators: the sums exactly in fp64, then the reference's
+// fp32 operations.  Utterance b is total_frames[b] = T_b + look_ahead frames long.  den_fb / den_sb: either may be NULL.
+__global__ __launch_bounds__(256) void segment_den_kernel(const double* __restrict__ binsum, const double* __restrict__ fbsum,
+                                                          const int* __restrict__ total_frames, float* __restrict__ den_fb,
+                                                          float* __restrict__ den_sb, int F, int FP, int nb) {
+    __shared__ double scratch[4];
+    const int b = blockIdx.x;
+    const int Tpb = total_frames[b] < 1 ? 1 : total_frames[b];
+    double plain = 0.0, weighted = 0.0;
+    for (int f = threadIdx.x; f < F; f += blockDim.x) {
+        const double v = binsum[(long)b * FP + f];
+        plain += v;
+        weighted += (double)unfold_multiplicity(f, F, nb) * v;
+    }
+    const double tot_fb = fsn_block_sum(plain, scratch);
+    const double tot_sb = fsn_block_sum(weighted, scratch) + fbsum[b];
+    if (threadIdx.x == 0) {
+        if (den_fb) den_fb[b] = (float)(tot_fb / ((double)F * Tpb)) + 1e-5f;
+        if (den_sb) den_sb[b] = (float)(tot_sb / ((double)F * (2 * nb + 2) * Tpb)) + 1e-5f;
     }
 }
 
@@ -252,6 +323,20 @@ int fsn_launch_offline_den(const double* binsum, const float* fb_out, float* den
     hipLaunchKernelGGL(offline_den_kernel, dim3(B), dim3(256), 0, s, binsum, fb_out, den_fb, den_sb, Tp, F, FP, nb,
                        which, lengths, T);
     return fsn_check_launch("offline_den_kernel");
+}
+int fsn_launch_binsum_accumulate(const float* mag, double* binsum, int B, int F, int FP, int k, hipStream_t s) {
+    hipLaunchKernelGGL(binsum_accumulate_kernel, dim3((F + 3) / 4, B), dim3(256), 0, s, mag, binsum, F, FP, k);
+    return fsn_check_launch("binsum_accumulate_kernel");
+}
+int fsn_launch_masked_sum_accumulate(const float* x, double* acc, const int* total_frames, int frames_done, int B, int k,
+                                     int FP, hipStream_t s) {
+    hipLaunchKernelGGL(masked_sum_accumulate_kernel, dim3(B), dim3(256), 0, s, x, acc, total_frames, frames_done, k, FP);
+    return fsn_check_launch("masked_sum_accumulate_kernel");
+}
+int fsn_launch_segment_den(const double* binsum, const double* fbsum, const int* total_frames, float* den_fb, float* den_sb,
+                           int B, int F, int FP, int nb, hipStream_t s) {
+    hipLaunchKernelGGL(segment_den_kernel, dim3(B), dim3(256), 0, s, binsum, fbsum, total_frames, den_fb, den_sb, F, FP, nb);
+    return fsn_check_launch("segment_den_kernel");
 }
 int fsn_launch_cumulative_den_fb(const float* mag, float* den, int B, int Tp, int F, int FP, hipStream_t s,
                                  double* carry, int t0) {

@@ -883,29 +883,33 @@ extern "C" size_t fsn_fullsubnet_stream_workspace_bytes(const fsn_fullsubnet_cfg
     return fsn_round_up_sz(cv.off, 256);
 }
 
-// The model step on n rows for k frames with carried state: w.magT [n][k][FP] -> w.crm_r / w.crm_i -> crm_out [n, 2, F, k].
-// fb / sb: the (h0, h1, c0, c1) rows of the full-band / sub-band layers, updated in place; den_fb() / den_sb() launch the
-// cumulative norm's divisors (w.den_fb from w.magT; w.den_sb from w.magT and w.fb_out) from wherever the carries live.
-template <class DenFb, class DenSb>
-static int stream_sequence(const fsn_fullsubnet_cfg* cfg, const float* pk, const StreamWs& w, float* const fb[4],
-                           float* const sb[4], int n, int k, float* crm_out, const DenFb& den_fb, const DenSb& den_sb,
-                           hipStream_t s) {
+// The two halves of the model step on n rows for k frames with carried state.  den_mode: how the half's divisors are laid out (0: one per row of the batch, the offline
+// norm of the segment entries; 1: one per frame - w.den_fb [n][k], w.den_sb [k][Npad] - the cumulative norm).
+// Full-band half: w.magT / w.den_fb -> w.fb_out [n][k][FP]; fb = the (h0, h1, c0, c1) rows of its two layers.
+static int stream_fullband(const fsn_fullsubnet_cfg* cfg, const float* pk, const StreamWs& w, float* const fb[4], int n, int k,
+                           int den_mode, hipStream_t s) {
     const Packed p = packed_layout(cfg);
-    const int F = cfg->num_freqs, FP = fsn_fpad(F), Hf = cfg->fb_hidden, Hs = cfg->sb_hidden;
-    const int Npad_fb = fsn_round_up(n, 16), N = n * F, Npad = fsn_round_up(N, 16);
+    const int F = cfg->num_freqs, FP = fsn_fpad(F), Hf = cfg->fb_hidden;
+    const int Npad_fb = fsn_round_up(n, 16);
     // la = 0: every model step is handed back; the caller matches step s to output frame s - look_ahead
     const ModelGeom g{n, k, k, F, FP, cfg->sb_num_neighbors, 0};
-    FSN_TRY(den_fb());
     const int fb_rt = k * Npad_fb / 16;
-    FSN_TRY(fsn_launch_gemm(gemm_a_fullband(g, w.magT, w.den_fb, 1, Npad_fb), pk + p.fb_wih0, gemm_c_frag(w.gx_fb, pk + p.fb_b0),
-                            fb_rt, 4 * Hf / 16, FP / 16, s));
+    FSN_TRY(fsn_launch_gemm(gemm_a_fullband(g, w.magT, w.den_fb, den_mode, Npad_fb), pk + p.fb_wih0,
+                            gemm_c_frag(w.gx_fb, pk + p.fb_b0), fb_rt, 4 * Hf / 16, FP / 16, s));
     FSN_TRY(fsn_launch_lstm_wavefront2(w.gx_fb, Npad_fb / 16, 0, pk + p.fb_whh0, pk + p.fb_wih1, pk + p.fb_b1_frag,
                                        pk + p.fb_whh1, w.hseq_fb0, w.hseq_fb1, Npad_fb, 0, fb[2], fb[3], k, Npad_fb / 16, Hf,
                                        s, fb[0], fb[1]));
-    FSN_TRY(fsn_launch_gemm(gemm_a_rows(w.hseq_fb1, Hf), pk + p.fb_fc, gemm_c_fb_out(g, w.fb_out, pk + p.fb_fcb, Npad_fb), fb_rt,
-                            FP / 16, Hf / 16, s));
-    FSN_TRY(den_sb());
-    const FsnSbInput xin = sb_input_model(g, w.magT, w.fb_out, w.den_sb, 1, Npad, pk + p.sb_wih0, pk + p.sb_b0,
+    return fsn_launch_gemm(gemm_a_rows(w.hseq_fb1, Hf), pk + p.fb_fc, gemm_c_fb_out(g, w.fb_out, pk + p.fb_fcb, Npad_fb), fb_rt,
+                           FP / 16, Hf / 16, s);
+}
+// Sub-band half: w.magT / w.fb_out / w.den_sb -> w.crm_r / w.crm_i -> crm_out [n, 2, F, k]; sb = its layers' state rows.
+static int stream_subband(const fsn_fullsubnet_cfg* cfg, const float* pk, const StreamWs& w, float* const sb[4], int n, int k,
+                          int den_mode, float* crm_out, hipStream_t s) {
+    const Packed p = packed_layout(cfg);
+    const int F = cfg->num_freqs, FP = fsn_fpad(F), Hs = cfg->sb_hidden;
+    const int N = n * F, Npad = fsn_round_up(N, 16);
+    const ModelGeom g{n, k, k, F, FP, cfg->sb_num_neighbors, 0};
+    const FsnSbInput xin = sb_input_model(g, w.magT, w.fb_out, w.den_sb, den_mode, Npad, pk + p.sb_wih0, pk + p.sb_b0,
                                           p.sb_kin_pad / 16, N, 0);
     const int sb_rt = (int)((long)k * Npad / 16);
     FSN_TRY(fsn_launch_gemm(gemm_a_subband(xin, 0, Npad), pk + p.sb_wih0, gemm_c_frag(w.gx_sb, pk + p.sb_b0), sb_rt,
@@ -917,6 +921,18 @@ static int stream_sequence(const fsn_fullsubnet_cfg* cfg, const float* pk, const
                             gemm_c_masks(g, w.crm_r, w.crm_i, pk + p.sb_fcb, Npad, 0, N), sb_rt, 1, Hs / 16, s));
     FSN_TRY(fsn_launch_transpose(w.crm_r, crm_out, n, k, F, FP, (long)k * FP, k, 2L * F * k, k, F, s));
     return fsn_launch_transpose(w.crm_i, crm_out + (size_t)F * k, n, k, F, FP, (long)k * FP, k, 2L * F * k, k, F, s);
+}
+// The model step on n rows for k frames with carried state: w.magT [n][k][FP] -> w.crm_r / w.crm_i -> crm_out [n, 2, F, k].
+// fb / sb: the (h0, h1, c0, c1) rows of the full-band / sub-band layers, updated in place; den_fb() / den_sb() launch the
+// cumulative norm's divisors (w.den_fb from w.magT; w.den_sb from w.magT and w.fb_out) from wherever the carries live.
+template <class DenFb, class DenSb>
+static int stream_sequence(const fsn_fullsubnet_cfg* cfg, const float* pk, const StreamWs& w, float* const fb[4],
+                           float* const sb[4], int n, int k, float* crm_out, const DenFb& den_fb, const DenSb& den_sb,
+                           hipStream_t s) {
+    FSN_TRY(den_fb());
+    FSN_TRY(stream_fullband(cfg, pk, w, fb, n, k, 1, s));
+    FSN_TRY(den_sb());
+    return stream_subband(cfg, pk, w, sb, n, k, 1, crm_out, s);
 }
 
 extern "C" int fsn_fullsubnet_stream_step(const fsn_fullsubnet_cfg* cfg, const void* packed, void* state,
@@ -1032,6 +1048,133 @@ extern "C" int fsn_fullsubnet_stream_pool_step(const fsn_fullsubnet_cfg* cfg, co
     FSN_TRY(fsn_launch_pool_scatter(state, L, capacity, slots, n, 0, t.fb[0], t.fb[1], t.fb[2], t.fb[3], Npad_fb, k, s));
     // last: it advances the listed slots' step counts
     return fsn_launch_pool_scatter(state, L, capacity, slots, n, 1, t.sb[0], t.sb[1], t.sb[2], t.sb[3], Npad, k, s);
+}
+
+// ---- recordings of any length: the model in segments of k frames, both norms --------------------------------------------
+// The stream step's two halves as entries of their own, so that the offline norm - whose divisors are means over the whole
+// recording - can run in three passes over the segments: (1) per-bin magnitude sums, (2) the full-band model, which needs
+// the first divisor and yields the sum of its own output, (3) the sub-band model, which needs the second.  State: the
+// stream step's blob (same layout, so a cumulative-norm cfg does here exactly what the stream step does) followed by the
+// fp64 accumulators of the offline norm.
+struct SegmentState {
+    StreamState st;
+    double *binsum, *fbsum;  // [B][FP] per-bin magnitude sums; [B] sums of the full-band output
+};
+static SegmentState segment_carve(Carver& cv, const fsn_fullsubnet_cfg* cfg, int B) {
+    SegmentState g;
+    g.st = stream_carve(cv, cfg, B);
+    g.binsum = cv.take<double>((size_t)B * fsn_fpad(cfg->num_freqs));
+    g.fbsum = cv.take<double>((size_t)B);
+    return g;
+}
+static int check_segment(const fsn_fullsubnet_cfg* cfg, int B, int k) {
+    FSN_TRY(check_cfg(cfg));
+    FSN_REQUIRE(cfg->arith == FSN_ARITH_F32, "segments: only the fp32 arithmetic is built (arith %d)", cfg->arith);
+    FSN_REQUIRE(B >= 1 && B <= 4096, "segments: batch %d out of range [1, 4096]", B);
+    FSN_REQUIRE(k >= 1 && k <= 4096, "segments: frames %d out of range [1, 4096]", k);
+    return FSN_OK;
+}
+extern "C" size_t fsn_fullsubnet_segment_state_bytes(const fsn_fullsubnet_cfg* cfg, int B) {
+    if (check_segment(cfg, B, 1) != FSN_OK) return 0;
+    Carver cv(nullptr);
+    segment_carve(cv, cfg, B);
+    return fsn_round_up_sz(cv.off, 256);
+}
+extern "C" size_t fsn_fullsubnet_segment_workspace_bytes(const fsn_fullsubnet_cfg* cfg, int B, int k) {
+    if (check_segment(cfg, B, k) != FSN_OK) return 0;
+    Carver cv(nullptr);
+    stream_ws_carve(cv, cfg, B, k);  // one layout for both model passes: each uses its half of it
+    return fsn_round_up_sz(cv.off, 256);
+}
+// what every segment entry checks about its state (and workspace, when it has one: workspace_bytes = 0 with ws = NULL)
+static int check_segment_call(const fsn_fullsubnet_cfg* cfg, const void* state, size_t state_bytes, int B, int k,
+                              const void* workspace, size_t workspace_bytes) {
+    FSN_TRY(check_segment(cfg, B, k));
+    FSN_REQUIRE(state, "segments: state is NULL");
+    if (state_bytes < fsn_fullsubnet_segment_state_bytes(cfg, B) ||
+        (workspace && workspace_bytes < fsn_fullsubnet_segment_workspace_bytes(cfg, B, k))) {
+        fsn_set_error("segments: state / workspace buffer too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    return FSN_OK;
+}
+
+extern "C" int fsn_fullsubnet_segment_stats(const fsn_fullsubnet_cfg* cfg, void* state, size_t state_bytes, const float* mag,
+                                            int B, int k, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_segment_call(cfg, state, state_bytes, B, k, nullptr, 0));
+    FSN_REQUIRE(mag, "NULL pointer argument");
+    if (cfg->norm_type == FSN_NORM_CUMULATIVE_LAPLACE) return FSN_OK;  // causal: the model passes keep running sums
+    Carver cs(state);
+    const SegmentState g = segment_carve(cs, cfg, B);
+    return fsn_launch_binsum_accumulate(mag, g.binsum, B, cfg->num_freqs, fsn_fpad(cfg->num_freqs), k,
+                                        static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fsn_fullsubnet_segment_divisors(const fsn_fullsubnet_cfg* cfg, const void* state, size_t state_bytes,
+                                               const int* total_frames, int B, float* den_fb, float* den_sb, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_segment_call(cfg, state, state_bytes, B, 1, nullptr, 0));
+    FSN_REQUIRE(cfg->norm_type == FSN_NORM_OFFLINE_LAPLACE, "segments: only the offline norm has per-recording divisors");
+    FSN_REQUIRE(total_frames && den_fb && den_sb, "NULL pointer argument");
+    Carver cs(const_cast<void*>(state));
+    const SegmentState g = segment_carve(cs, cfg, B);
+    return fsn_launch_segment_den(g.binsum, g.fbsum, total_frames, den_fb, den_sb, B, cfg->num_freqs, fsn_fpad(cfg->num_freqs),
+                                  cfg->sb_num_neighbors, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fsn_fullsubnet_segment_fullband(const fsn_fullsubnet_cfg* cfg, const void* packed, void* state,
+                                               size_t state_bytes, int frames_done, const int* total_frames, const float* mag,
+                                               int B, int k, float* fb_out, void* workspace, size_t workspace_bytes,
+                                               void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(workspace, "NULL pointer argument");
+    FSN_TRY(check_segment_call(cfg, state, state_bytes, B, k, workspace, workspace_bytes));
+    const bool cum = cfg->norm_type == FSN_NORM_CUMULATIVE_LAPLACE;
+    FSN_REQUIRE(packed && mag && fb_out && frames_done >= 0 && (cum || total_frames),
+                "NULL pointer argument / negative frame count");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int F = cfg->num_freqs, FP = fsn_fpad(F);
+    Carver cs(state), cw(workspace);
+    const SegmentState g = segment_carve(cs, cfg, B);
+    const StreamWs w = stream_ws_carve(cw, cfg, B, k);
+    float* const fb[4] = {g.st.fb_h0, g.st.fb_h1, g.st.fb_c0, g.st.fb_c1};
+    // [B, 1, F, k] -> frame-major [B][k][FP]
+    FSN_TRY(fsn_launch_transpose(mag, w.magT, B, FP, k, k, (long)F * k, FP, (long)k * FP, F, k, s));
+    if (cum)
+        FSN_TRY(fsn_launch_cumulative_den_fb(w.magT, w.den_fb, B, k, F, FP, s, g.st.fb_sum, frames_done));
+    else
+        FSN_TRY(fsn_launch_segment_den(g.binsum, g.fbsum, total_frames, w.den_fb, nullptr, B, F, FP, cfg->sb_num_neighbors, s));
+    FSN_TRY(stream_fullband(cfg, static_cast<const float*>(packed), w, fb, B, k, cum ? 1 : 0, s));
+    if (!cum) FSN_TRY(fsn_launch_masked_sum_accumulate(w.fb_out, g.fbsum, total_frames, frames_done, B, k, FP, s));
+    // frame-major [B][k][FP] -> [B, F, k]
+    return fsn_launch_transpose(w.fb_out, fb_out, B, k, F, FP, (long)k * FP, k, (long)F * k, k, F, s);
+}
+
+extern "C" int fsn_fullsubnet_segment_subband(const fsn_fullsubnet_cfg* cfg, const void* packed, void* state,
+                                              size_t state_bytes, int frames_done, const int* total_frames, const float* mag,
+                                              const float* fb_out, int B, int k, float* crm_out, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(workspace, "NULL pointer argument");
+    FSN_TRY(check_segment_call(cfg, state, state_bytes, B, k, workspace, workspace_bytes));
+    const bool cum = cfg->norm_type == FSN_NORM_CUMULATIVE_LAPLACE;
+    FSN_REQUIRE(packed && mag && fb_out && crm_out && frames_done >= 0 && (cum || total_frames),
+                "NULL pointer argument / negative frame count");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int F = cfg->num_freqs, FP = fsn_fpad(F), nb = cfg->sb_num_neighbors, Npad = fsn_round_up(B * F, 16);
+    Carver cs(state), cw(workspace);
+    const SegmentState g = segment_carve(cs, cfg, B);
+    const StreamWs w = stream_ws_carve(cw, cfg, B, k);
+    float* const sb[4] = {g.st.sb_h0, g.st.sb_h1, g.st.sb_c0, g.st.sb_c1};
+    // [B, 1, F, k] and [B, F, k] -> frame-major [B][k][FP], padded bins zero
+    FSN_TRY(fsn_launch_transpose(mag, w.magT, B, FP, k, k, (long)F * k, FP, (long)k * FP, F, k, s));
+    FSN_TRY(fsn_launch_transpose(fb_out, w.fb_out, B, FP, k, k, (long)F * k, FP, (long)k * FP, F, k, s));
+    if (cum)
+        FSN_TRY(fsn_launch_cumulative_den_sb(w.magT, w.fb_out, w.den_sb, B, k, F, FP, nb, Npad, s, g.st.sb_sum, frames_done));
+    else
+        FSN_TRY(fsn_launch_segment_den(g.binsum, g.fbsum, total_frames, nullptr, w.den_sb, B, F, FP, nb, s));
+    return stream_subband(cfg, static_cast<const float*>(packed), w, sb, B, k, cum ? 1 : 0, crm_out, s);
 }
 
 // ---- STFT / iSTFT boundary -------------------------------------------------------------------

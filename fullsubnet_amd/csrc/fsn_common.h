@@ -389,6 +389,14 @@ int fsn_launch_binsum(const float* mag, double* binsum, int B, int Tp, int FP, h
 int fsn_launch_offline_den(const double* binsum, const float* fb_out, float* den_fb, float* den_sb, int B,
                            int Tp, int F, int FP, int nb, int which, hipStream_t s, const int* lengths = nullptr,
                            int T = 0);
+// The offline norm over segments (elementwise_kernels.hip): binsum [B][FP] += this segment's per-bin sums of mag [B][F][k];
+// acc [B] += the sum of x [B][k][FP] over the frames frames_done + t < total_frames[b]; the two divisors (either output
+// may be NULL) from the finished accumulators.  total_frames: device memory, [B].
+int fsn_launch_binsum_accumulate(const float* mag, double* binsum, int B, int F, int FP, int k, hipStream_t s);
+int fsn_launch_masked_sum_accumulate(const float* x, double* acc, const int* total_frames, int frames_done, int B, int k,
+                                     int FP, hipStream_t s);
+int fsn_launch_segment_den(const double* binsum, const double* fbsum, const int* total_frames, float* den_fb, float* den_sb,
+                           int B, int F, int FP, int nb, hipStream_t s);
 // carry / t0: streaming continuation (running sums of the t0 frames already seen, updated in place); NULL / 0 offline
 int fsn_launch_cumulative_den_fb(const float* mag, float* den, int B, int Tp, int F, int FP, hipStream_t s,
                                  double* carry = nullptr, int t0 = 0);

@@ -52,6 +52,12 @@ class Inferencer:
         self.torch_stft = partial(stft, n_fft=self.n_fft, hop_length=self.hop_length, win_length=self.win_length)
         self.torch_istft = partial(istft, n_fft=self.n_fft, hop_length=self.hop_length, win_length=self.win_length)
         self.fused_call = True  # one utterance per call on the fused FullSubNet configurations: fsn_enhance (False: stage by stage)
+        # [inferencer] segment_frames (optional): items longer than that many frames run in segments (Model.enhance_long)
+        self.segment_frames = self.inference_config.get("segment_frames")
+        if self.segment_frames is not None:
+            self.segment_frames = int(self.segment_frames)
+            if not 1 <= self.segment_frames <= 4096:
+                raise ValueError(f"[inferencer] segment_frames must be in [1, 4096], got {self.segment_frames}")
 
         epoch = 0
         if model is None:
@@ -80,6 +86,13 @@ class Inferencer:
     @torch.no_grad()
     def full_band_crm_mask(self, noisy, inference_args=None):
         model = self.model
+        if self._is_long(noisy):
+            if not hasattr(model, "enhance_long"):
+                from ._lib import FsnError
+                raise FsnError(f"[inferencer] segment_frames: {type(model).__module__}.Model has no enhance_long (FullSubNet's "
+                               "fused configurations only); remove the key for this model")
+            return model.enhance_long(noisy, segment_frames=self.segment_frames, n_fft=self.n_fft,
+                                      hop_length=self.hop_length).detach().squeeze(0).cpu().numpy()
         if (self.fused_call and noisy.dim() == 2 and noisy.shape[0] == 1 and getattr(model, "_fused", False)
                 and self.n_fft == self.win_length == 512 and self.hop_length == 256 and noisy.shape[1] > self.n_fft // 2):
             # ONE utterance (the reference's loop, base_inferencer.py:78,173): band dropping does not fire (model.py:114), so the
@@ -95,6 +108,12 @@ class Inferencer:
         enhanced_imag = pred_crm[..., 1] * noisy_real + pred_crm[..., 0] * noisy_imag
         enhanced = self.torch_istft((enhanced_real, enhanced_imag), length=noisy.size(-1), input_type="real_imag")
         return enhanced.detach().squeeze(0).cpu().numpy()
+
+    def _is_long(self, noisy):
+        """[inferencer] segment_frames = N: one-utterance items of more than N frames go through ``Model.enhance_long``
+        (segments of N frames with carried state, memory that does not grow with the recording at hidden-state width)."""
+        n = self.__dict__.get("segment_frames")
+        return n is not None and noisy.dim() == 2 and noisy.shape[0] == 1 and 1 + noisy.shape[1] // self.hop_length > n
 
     @torch.no_grad()
     def enhance_batch(self, noisy, lengths=None):
@@ -116,7 +135,7 @@ class Inferencer:
         configurations, Fast FullSubNet's time-major path), long enough for the STFT's reflect padding."""
         ragged_ok = getattr(self.model, "ragged_enhance_ok", None)
         return (self.fused_call and ragged_ok is not None and ragged_ok(self.n_fft, self.hop_length)
-                and self.n_fft == self.win_length
+                and self.n_fft == self.win_length and not any(self._is_long(n) for n, _ in items)
                 and all(n.dim() == 2 and n.shape[0] == 1 and n.shape[1] > self.n_fft // 2 for n, _ in items))
 
     def __getattr__(self, name):

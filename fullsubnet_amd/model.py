@@ -302,6 +302,19 @@ class Model(nn.Module):
                                  ws.numel(), _lib.stream_ptr(y.device)))
         return (out, crm) if return_crm else out
 
+    @torch.no_grad()
+    def enhance_long(self, noisy, lengths=None, segment_frames=None, workspace_limit=4 << 30, return_crm=False, **kw):
+        """``enhance`` for recordings of any length: noisy [B, L] (device or host) -> enhanced [B, L] on the model's device
+        (and the mask [B, 2, F, 1 + L // hop] with ``return_crm``), ``lengths`` as in ``enhance``.  The model runs in
+        segments of ``segment_frames`` frames (1 .. 4096; None: the largest whose workspace stays under
+        ``workspace_limit`` bytes) with carried LSTM state, the transforms in slabs; what grows with the recording are
+        planes of F floats per frame (about 6 KB per frame and row), nothing of hidden-size width.  Same result as
+        ``enhance`` within fp32 rounding (other recurrent kernels: not bit for bit), for both Laplace norms.  Fused
+        configurations at n_fft 512 / hop 256 in fp32 only: anything else raises ``FsnError``.  See ``long_form.py``."""
+        from .long_form import enhance_long
+        return enhance_long(self, noisy, lengths=lengths, segment_frames=segment_frames, workspace_limit=workspace_limit,
+                            return_crm=return_crm, **kw)
+
     def ragged_enhance_ok(self, n_fft, hop_length):
         """Whether ``enhance(noisy, lengths=...)`` is ONE library call (``fsn_enhance_ragged``), not a row-by-row loop."""
         return self._fused and n_fft == 512 and hop_length == 256

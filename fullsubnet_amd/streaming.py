@@ -22,10 +22,10 @@ import ctypes
 import torch
 
 from . import _lib
-from .acoustics.feature import istft, stft
 from .acoustics.mask import decompress_cIRM
 from .base_model import EPSILON, BaseModel
 from .sequence_model import _round_up, linear_infer
+from .slabs import analysis_bounds, analysis_slab, synthesis_slab
 
 
 def _packed_layers(block):
@@ -175,13 +175,8 @@ class StreamingEnhancer:
         t_end = self._n_in // hop if final else (self._n_in - half) // hop
         if t_end < self._t_next:
             return None
-        j0 = max(self._t_next - 2, 0)  # two frames of history keep the segment longer than the reflect pad
-        a = j0 * hop - self._buf0
-        b = (self._n_in if final else max(t_end * hop + half, half + 1)) - self._buf0
-        seg = self._buf[:, a:b].contiguous()
-        mag, _, re, im = stft(seg, self.n_fft, hop, self.n_fft, return_phase=False)
-        lo, hi = self._t_next - j0, t_end - j0 + 1
-        out = tuple(x[:, :, lo:hi].contiguous() for x in (mag, re, im))
+        j0, a, b = analysis_bounds(self._t_next, t_end, self._n_in, final, self.n_fft, hop)
+        out = analysis_slab(self._buf[:, a - self._buf0:b - self._buf0], j0, self._t_next, t_end, self.n_fft, hop)
         self._t_next = t_end + 1
         keep_from = max(self._t_next - 2, 0) * hop
         if keep_from > self._buf0:
@@ -199,20 +194,10 @@ class StreamingEnhancer:
         dm = decompress_cIRM(crm.permute(0, 2, 3, 1).contiguous())
         er = dm[..., 0] * re - dm[..., 1] * im
         ei = dm[..., 1] * re + dm[..., 0] * im
-        first = self._m_next if self._prev is None else self._m_next - 1
-        if self._prev is not None:
-            er = torch.cat([self._prev[0], er], dim=-1)
-            ei = torch.cat([self._prev[1], ei], dim=-1)
+        y, self._prev = synthesis_slab(er, ei, self._prev, self._m_next, self._n_out, self.n_fft, self.hop, total_length)
         self._m_next += k
-        self._prev = (er[..., -1:].contiguous(), ei[..., -1:].contiguous())
-        n_frames = er.shape[-1]
-        length = (n_frames - 1) * self.hop if total_length is None else total_length - first * self.hop
-        if length <= 0:
+        if y is None:
             return torch.zeros((self.B, 0), dtype=torch.float32, device=self.device)
-        y = istft((er.contiguous(), ei.contiguous()), self.n_fft, self.hop, self.n_fft, length=length,
-                  input_type="real_imag")
-        skip = self._n_out - first * self.hop  # samples of this segment already emitted (none in steady state)
-        y = y[:, skip:]
         self._n_out += y.shape[1]
         return y
 

@@ -247,6 +247,54 @@ int fsn_fullsubnet_stream_step(const fsn_fullsubnet_cfg* cfg, const void* packed
                                int steps_done, const float* mag, int B, int k, float* crm_out, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* ---- recordings of any length: the model in segments, state carried, both norms ------------- */
+
+/* fsn_fullsubnet_forward stops at 100 000 frames and its workspace grows with the recording at hidden-state width.  These
+ * entries run the same model on k (1 .. 4096) frames at a time: only planes of F floats per frame (magnitude, full-band
+ * output, mask) live for the whole recording, in the caller's memory; everything of hidden-size width is inside `workspace`
+ * (fsn_fullsubnet_segment_workspace_bytes(cfg, B, k), shared by the passes) and dies with the segment.  fp32 arithmetic only.
+ *
+ * `state` (fsn_fullsubnet_segment_state_bytes(cfg, B), caller-owned): (h, c) of the four LSTM layers, the running sums of
+ * the cumulative norm, and the fp64 accumulators of the offline norm - per-bin magnitude sums [B][FP] and the sum of the
+ * full-band output [B].  All zeros is a fresh recording.  Both size queries answer without a device and return 0
+ * (fsn_last_error) for B outside 1 .. 4096, k outside 1 .. 4096 or a bad cfg; both norm types are accepted.
+ *
+ * offline_laplace_norm (base_model.py:204-218) divides by ONE mean per utterance, so a recording takes three passes over
+ * its segments, each pass in frame order over the T_max + look_ahead model steps (the caller appends the look_ahead zero
+ * frames of model.py:85), each step exactly once:
+ *   1. fsn_fullsubnet_segment_stats on every segment: adds the segment's per-bin sums of mag [B, 1, F, k] to the state
+ *      (fp64, fixed order inside a segment).
+ *   2. fsn_fullsubnet_segment_fullband on every segment: the full-band divisor from the finished sums, both full-band
+ *      layers and the output layer on k more frames from the carried (h, c) -> fb_out [B, F, k] (model.py:95); the sum of
+ *      fb_out over the frames frames_done + t < total_frames[b] of each row is added to the state.
+ *   3. fsn_fullsubnet_segment_subband on every segment: the sub-band divisor (model.py:110-111, the multiplicity-weighted
+ *      per-bin sums plus the full-band sum), both sub-band layers and the output layer from the carried (h, c) ->
+ *      crm_out [B, 2, F, k]; step s is the compressed mask of frame s - look_ahead, as in fsn_fullsubnet_stream_step.
+ * frames_done: model steps passed to THIS pass before the call.  total_frames (device memory, [B]): row b's own
+ * T_b + look_ahead.  In a ragged batch every row runs to the longest row's end; a row's mag must be zero from its frame T_b
+ * on (fsn_stft_ragged writes it so), and only the divisors and the fb_out sum depend on total_frames.  The divisors are
+ * exactly-summed fp64 values, then the reference's fp32 operations (float(sum / count) + 1e-5f), as in the one-call path;
+ * the results agree with fsn_fullsubnet_forward within fp32 rounding, not bit for bit (different recurrent kernels), and
+ * two segmentations of one recording agree within fp32 rounding of the recurrences (the sums differ in fp64 only).
+ * fsn_fullsubnet_segment_divisors writes the two divisors the passes use to den_fb / den_sb (device memory, [B] each); call
+ * it after pass 2 for den_sb.
+ *
+ * cumulative_laplace_norm: the norm is causal, passes 2 and 3 continue its running sums exactly as
+ * fsn_fullsubnet_stream_step does (the state begins with that entry's layout), pass 1 does nothing, total_frames may be
+ * NULL and fsn_fullsubnet_segment_divisors is refused.  One driver serves both norms. */
+size_t fsn_fullsubnet_segment_state_bytes(const fsn_fullsubnet_cfg* cfg, int B);
+size_t fsn_fullsubnet_segment_workspace_bytes(const fsn_fullsubnet_cfg* cfg, int B, int k);
+int fsn_fullsubnet_segment_stats(const fsn_fullsubnet_cfg* cfg, void* state, size_t state_bytes, const float* mag, int B,
+                                 int k, void* stream);
+int fsn_fullsubnet_segment_fullband(const fsn_fullsubnet_cfg* cfg, const void* packed, void* state, size_t state_bytes,
+                                    int frames_done, const int* total_frames, const float* mag, int B, int k,
+                                    float* fb_out, void* workspace, size_t workspace_bytes, void* stream);
+int fsn_fullsubnet_segment_subband(const fsn_fullsubnet_cfg* cfg, const void* packed, void* state, size_t state_bytes,
+                                   int frames_done, const int* total_frames, const float* mag, const float* fb_out, int B,
+                                   int k, float* crm_out, void* workspace, size_t workspace_bytes, void* stream);
+int fsn_fullsubnet_segment_divisors(const fsn_fullsubnet_cfg* cfg, const void* state, size_t state_bytes,
+                                    const int* total_frames, int B, float* den_fb, float* den_sb, void* stream);
+
 /* ---- streaming pool: sessions that open, advance and close on their own --------------------- */
 
 /* fsn_fullsubnet_stream_step for streams that are NOT in lockstep.  `state` is a pool of `capacity` slots (1 .. 4096),
