@@ -275,6 +275,18 @@ SIGNATURES = {
     "fsn_debug_persist_stats": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "fsn_debug_persist_set_fits": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p]),
     "fsn_debug_tn_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_long, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "fsn_debug_lstm2_plan16": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_long, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int]),
+    "fsn_debug_gemm_tn_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_long]),
+    "fsn_debug_tn16_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_long, _c.c_void_p, _c.c_void_p]),
+    "fsn_debug_to16": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p]),
+    "fsn_debug_gemm_tn16h": (_c.c_int, [_c.c_void_p, _c.c_long, _c.c_void_p, _c.c_long, _c.c_void_p, _c.c_long, _c.c_int, _c.c_int,
+                                        _c.c_long, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p]),
+    "fsn_debug_gemm_tn16n": (_c.c_int, [_c.c_void_p, _c.c_long, _c.c_void_p, _c.c_long, _c.c_void_p, _c.c_long, _c.c_int, _c.c_int,
+                                        _c.c_long, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p]),
+    "fsn_debug_gemm_tn": (_c.c_int, [_c.c_void_p, _c.c_long, _c.c_void_p, _c.c_long, _c.c_void_p, _c.c_long, _c.c_int, _c.c_int,
+                                     _c.c_long, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p]),
+    "fsn_debug_gemm_dx16": (_c.c_int, [_c.c_void_p, _c.c_long, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_long,
+                                       _c.c_long, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
     "fsn_debug_core_chunks": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
     "fsn_debug_core_plan": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int]),
     "fsn_improved_front": (_c.c_int, [_f32p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_void_p]),

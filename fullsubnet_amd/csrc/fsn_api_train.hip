@@ -59,6 +59,65 @@ extern "C" int fsn_lstm2_train_is_persistent(int T, int N, int I, int H) {
 static bool lstm2_use_g16(int arith, int clusters, int N) {
     return arith != FSN_ARITH_F32 && clusters > 0 && fsn_lstm2_g16_clusters(N / 16) >= clusters && !g_g16_off.load(std::memory_order_relaxed);
 }
+// ONE plan of the 16-bit training arithmetic for both directions, computed here and nowhere else: which kernels a call of
+// fsn_lstm2_forward_train / fsn_lstm2_backward under `arith` (with or without FSN_ARITH_SAVES16) lands on.  Each direction
+// has its own clusters (Lstm2TrainPlan); a direction without clusters runs layer by layer or on the chain, in fp32.
+struct Lstm2Plan16 {
+    int fwd_clusters, bwd_clusters;  // 64-row clusters of the group launch of each direction (0: none)
+    int fwd_left, bwd_left;          // rows beside that launch, step by step in fp32
+    bool fwd16, bwd16;               // the direction runs in the 16-bit arithmetic at all
+    bool g16_fwd, g16_bptt;          // ... on lstm_group16_kernels.hip (else: the `arith` forms of the fp32-era group kernels)
+    bool tn16h;                      // the three large weight-gradient products from 16-bit operands in memory
+    int tn16h_form;                  // of the K = (T - 1) N products: 0 none, 1 the 192 x 192 form, 2 the 192 x 384 form
+    bool in16;                       // ... and layer 0's input-side products (dx, dW_ih0) too
+    bool h16_saved;                  // the products read the 16-bit h_t the forward launch left in the save slots
+    // FSN_ARITH_SAVES16 in force: only where BOTH directions run on lstm_group16_kernels.hip, the one pair that writes and reads
+    // the 16-bit gate slots.  (The flag used to reach the 16-bit BPTT launch whatever the forward had done: with 1 - 16 or 33+
+    // input columns the forward runs layer by layer and saves fp32 gates, which that launch then decoded as 16-bit ones.)
+    bool saves16;
+};
+static Lstm2Plan16 lstm2_plan16(int T, int N, int I, long ldx, int H, int arith) {
+    const bool saves16_asked = (arith & FSN_ARITH_SAVES16) != 0;
+    arith &= ~FSN_ARITH_SAVES16;
+    const Lstm2TrainPlan tp = lstm2_train_plan(T, N, I, H);
+    const int G = 4 * H;
+    Lstm2Plan16 p{};
+    p.fwd_clusters = tp.fwd_group;
+    p.bwd_clusters = tp.bptt_group;
+    p.fwd_left = tp.fwd_group ? N - 64 * tp.fwd_group : 0;
+    p.bwd_left = tp.bptt_group ? N - 64 * tp.bptt_group : 0;
+    p.fwd16 = arith != FSN_ARITH_F32 && tp.fwd_group > 0;
+    p.bwd16 = arith != FSN_ARITH_F32 && tp.bptt_group > 0;
+    p.g16_fwd = lstm2_use_g16(arith, tp.fwd_group, N);
+    p.g16_bptt = lstm2_use_g16(arith, tp.bptt_group, N);
+    // the weight-gradient products from 16-bit operands in memory (needs the shapes' one-workgroup-per-CU plan - for BOTH K:
+    // dW_hh sums (T - 1) N rows, dW_ih1 T N, and a plan exists only for some K (every split non-empty); asking for the first
+    // alone made fsn_lstm2_backward fail with "gemm_tn16h: no plan" at e.g. T = 2, N = 2064 or T = 3, N = 1728 on 256 CUs)
+    p.tn16h = p.g16_bptt && T > 1 && fsn_gemm_tn16h_supported(G, H, (long)(T - 1) * N) && fsn_gemm_tn16h_supported(G, H, (long)T * N) &&
+              !g_tn16h_off.load(std::memory_order_relaxed);
+    p.tn16h_form = p.tn16h ? fsn_gemm_tn16h_form(G, H, (long)(T - 1) * N, nullptr) : 0;
+    // ... and layer 0's input-side products too (dx, dW_ih0): then the BPTT launch stores no fp32 gate gradients at all
+    p.in16 = p.tn16h && fsn_gemm_tn16n_supported(G, I, (long)T * N) && fsn_gemm_dx16_supported((long)T * N, G, I) && ldx == 32 &&
+             !g_in16_off.load(std::memory_order_relaxed);
+    p.saves16 = saves16_asked && p.g16_fwd && p.g16_bptt;
+    // under FSN_ARITH_SAVES16 the forward launch left h_t in 16 bits inside the save buffers (second half of a row's gate slot)
+    // for every cluster row - with no step-by-step rows beside the launch the hidden sequences need no conversion pass at all
+    p.h16_saved = p.tn16h && p.saves16 && p.bwd_left == 0;
+    return p;
+}
+// Test hook: that plan as integers (include/fsn_hip.h lists the fields)
+extern "C" int fsn_debug_lstm2_plan16(int T, int N, int I, long ldx, int H, int arith, int* out, int n) {
+    const int base = arith & ~FSN_ARITH_SAVES16;
+    if (T < 1 || N < 16 || N % 16 || I < 1 || H < 1 || ldx < I || !out || n < 1 ||
+        (base != FSN_ARITH_F32 && base != FSN_ARITH_F16 && base != FSN_ARITH_BF16))
+        return -1;
+    const Lstm2Plan16 p = lstm2_plan16(T, N, I, ldx, H, arith);
+    const int v[13] = {p.fwd16, p.bwd16, p.g16_fwd, p.g16_bptt, p.tn16h, p.tn16h_form, p.in16, p.h16_saved,
+                       p.bwd_left, p.bwd_clusters, p.fwd_left, p.fwd_clusters, p.saves16};
+    const int m = n < 13 ? n : 13;
+    for (int i = 0; i < m; ++i) out[i] = v[i];
+    return m;
+}
 static size_t lstm2_group_flag_words_any(int clusters) {
     size_t a = fsn_lstm2_group_flag_words(clusters), b = fsn_lstm2_g16_flag_words(clusters), c = fsn_lstm2_group_bptt_flag_words(clusters);
     a = a > b ? a : b;
@@ -129,7 +188,8 @@ extern "C" int fsn_lstm2_forward_train(const float* x, long ldx, const float* w_
         float* gx_left = cv.take<float>((size_t)T * left * 4 * H);
         const size_t wfloats = (size_t)4 * H * Ipad + (size_t)3 * 4 * H * H;
         unsigned short* w16 = arith != FSN_ARITH_F32 ? cv.take<unsigned short>(wfloats) : nullptr;
-        const bool g16 = lstm2_use_g16(arith, clusters, N);
+        const Lstm2Plan16 p16 = lstm2_plan16(T, N, I, ldx, H, arith | saves16);
+        const bool g16 = p16.g16_fwd;
         if (!g16 || left > 0) {  // the fp32-fragment weights: the group kernel's and the step-by-step rows' (the 16-bit kernels pack their own)
             FSN_TRY(fsn_launch_pack(w_ih0, wih0_p, 4 * H, I, 4 * H, Ipad, s));
             FSN_TRY(fsn_launch_pack(w_hh0, whh0_p, 4 * H, H, 4 * H, H, s));
@@ -147,7 +207,7 @@ extern "C" int fsn_lstm2_forward_train(const float* x, long ldx, const float* w_
             FSN_PERSIST_BEGIN(s);
             if (g16) {  // the 16-bit arithmetic's own kernels: they pack the raw weights their way into w16
                 FSN_TRY(fsn_launch_lstm2_g16_train(x, I, N, w_ih0, w_hh0, w_ih1, w_hh1, b0, b1, hseq0, hseq1, sv0, sv1, flags, w16,
-                                                   T, clusters, H, s, arith | saves16));
+                                                   T, clusters, H, s, arith | (p16.saves16 ? FSN_ARITH_SAVES16 : 0)));
                 FSN_TRY(fsn_launch_poison_if(flags + fsn_lstm2_g16_status_word(clusters), hseq1, (size_t)T * N * H, s));
             } else {
                 FSN_TRY(fsn_launch_lstm2_group_train(x, ldx, 32, N, wih0_p, whh0_p, wih1_p, whh1_p, b0, b1, hseq0, hseq1, sv0,
@@ -428,19 +488,13 @@ static int lstm2_backward_phases(const float* dh1, const float* x, long ldx, con
     unsigned short* dg16 = arith != FSN_ARITH_F32 ? cv.take<unsigned short>((size_t)2 * T * N * G) : nullptr;  // layer 0 | layer 1
     unsigned short* h16 = arith != FSN_ARITH_F32 ? cv.take<unsigned short>((size_t)2 * T * N * H) : nullptr;    // hseq0 | hseq1
     float* dbp = arith != FSN_ARITH_F32 ? cv.take<float>((size_t)2 * clusters * G) : nullptr;
-    const bool g16 = lstm2_use_g16(arith, clusters, N);
-    // the weight-gradient products from 16-bit operands in memory (needs the shapes' one-workgroup-per-CU plan)
-    const bool tn16h = g16 && T > 1 && fsn_gemm_tn16h_supported(G, H, (long)(T - 1) * N) && !g_tn16h_off.load(std::memory_order_relaxed);
-    // ... and layer 0's input-side products too (dx, dW_ih0): then the BPTT launch stores no fp32 gate gradients at all
-    const bool in16 = tn16h && fsn_gemm_tn16n_supported(G, I, (long)T * N) && fsn_gemm_dx16_supported((long)T * N, G, I) && ldx == 32 &&
-                      !g_in16_off.load(std::memory_order_relaxed);
+    const Lstm2Plan16 p16 = lstm2_plan16(T, N, I, ldx, H, arith | saves16);
+    const bool g16 = p16.g16_bptt, tn16h = p16.tn16h, in16 = p16.in16;
     unsigned short* x16 = arith != FSN_ARITH_F32 ? cv.take<unsigned short>((size_t)T * N * 32 + (size_t)G * 32) : nullptr;  // x in 16 bits | W_ih0 fragments
     unsigned short* wdx16 = in16 ? x16 + (size_t)T * N * 32 : nullptr;
     const float* sv0 = static_cast<const float*>(save0);
     const float* sv1 = static_cast<const float*>(save1);
-    // FSN_ARITH_SAVES16: the forward launch left h_t in 16 bits inside the save buffers (second half of a row's gate slot) for
-    // every cluster row - with no step-by-step rows beside the launch the hidden sequences need no conversion pass at all
-    const bool h16_saved = tn16h && saves16 && left == 0;
+    const bool h16_saved = p16.h16_saved;  // the 16-bit h_t inside the save buffers: second half of a row's gate slot
     const unsigned short* h16_0 = h16_saved ? reinterpret_cast<const unsigned short*>(sv0) + G : h16;
     const unsigned short* h16_1 = h16_saved ? reinterpret_cast<const unsigned short*>(sv1) + G : (h16 ? h16 + (size_t)T * N * H : nullptr);
     const long ldh16 = h16_saved ? 2L * G : H;  // 16-bit elements between rows
@@ -468,7 +522,8 @@ static int lstm2_backward_phases(const float* dh1, const float* x, long ldx, con
         if (g16) {  // the 16-bit arithmetic's own kernel (K-split; packs the raw weights its way into w16)
             // (layer 1's fp32 gate gradients of the cluster rows are not stored: the products below take the 16-bit copies)
             FSN_TRY(fsn_launch_lstm2_g16_bptt(dh1, w_hh1, w_ih1, w_hh0, sv0, sv1, dg0, dg1, partials, flags, g16_w, T, N, clusters,
-                                              H, s, arith | saves16, dg16, dg16 + (size_t)T * N * G, dbp, tn16h ? 0 : 1,
+                                              H, s, arith | (p16.saves16 ? FSN_ARITH_SAVES16 : 0), dg16, dg16 + (size_t)T * N * G, dbp,
+                                              tn16h ? 0 : 1,
                                               in16 ? 0 : 1));  // dg16 = layer 0 | layer 1
             FSN_TRY(fsn_launch_poison_if(flags + fsn_lstm2_g16_status_word(clusters), dg1, (size_t)2 * T * N * G, s));
             // the 16-bit copies and the bias-gradient sums as well (viewed as floats: every second value of a poisoned copy
@@ -652,4 +707,66 @@ extern "C" int fsn_linear_backward(const float* dy, long lddy, const float* x, l
     if (!dw) return FSN_OK;  // the input gradient alone (the parameter gradients by a second call, possibly on another stream)
     FSN_TRY(fsn_launch_gemm_tn(dy, lddy, x, ldx, dw, I, O, I, R, scratch, s));
     return fsn_launch_colsum(dy, lddy, db, O, R, scratch, s);
+}
+
+// ---- test hooks: the 16-bit arithmetic's conversion and product launchers on caller data ---------------------------
+// Thin entries: shape, pointer and workspace-size checks here, then the launcher unchanged (its own checks stay in force).
+// The workspace of the three weight-gradient forms is that of the fp32 product, fsn_debug_gemm_tn_workspace_bytes.
+extern "C" size_t fsn_debug_gemm_tn_workspace_bytes(int M, int Nc, long K) {
+    if (M < 1 || Nc < 1 || K < 1) return 0;
+    return fsn_gemm_tn_workspace_bytes(M, Nc, K);
+}
+extern "C" int fsn_debug_tn16_plan(int narrow, int M, int Nc, long K, int* splits, int* form) {
+    if (M < 1 || Nc < 1 || K < 1) return -1;
+    int s = 0;
+    const int f = narrow ? ((s = fsn_gemm_tn16n_splits(M, Nc, K)) > 0 ? 1 : 0) : fsn_gemm_tn16h_form(M, Nc, K, &s);
+    if (splits) *splits = s;
+    if (form) *form = f;
+    return 0;
+}
+extern "C" int fsn_debug_to16(const float* src, void* dst, size_t n, int arith, void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(src && dst && n > 0, "to16: NULL pointer argument or no elements");
+    FSN_REQUIRE(((size_t)src & 15) == 0 && ((size_t)dst & 7) == 0, "to16: source rows of 16 bytes, destination of 8");
+    return fsn_launch_to16(src, dst, n, arith, static_cast<hipStream_t>(stream));
+}
+static int debug_tn_args(const void* A, long lda, const void* B, long ldb, const float* C, long ldc, int M, int Nc, long K,
+                         const void* workspace, size_t workspace_bytes) {
+    FSN_REQUIRE(A && B && C && workspace, "NULL pointer argument");
+    FSN_REQUIRE(M >= 1 && Nc >= 1 && K >= 1 && lda >= M && ldb >= Nc && ldc >= Nc, "gemm_tn: bad shape");
+    if (workspace_bytes < fsn_gemm_tn_workspace_bytes(M, Nc, K)) {
+        fsn_set_error("gemm_tn: workspace too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    return FSN_OK;
+}
+extern "C" int fsn_debug_gemm_tn16h(const void* A16, long lda, const void* B16, long ldb, float* C, long ldc, int M, int Nc, long K,
+                                    void* workspace, size_t workspace_bytes, int arith, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(debug_tn_args(A16, lda, B16, ldb, C, ldc, M, Nc, K, workspace, workspace_bytes));
+    return fsn_launch_gemm_tn16h(A16, lda, B16, ldb, C, ldc, M, Nc, K, workspace, static_cast<hipStream_t>(stream), arith);
+}
+extern "C" int fsn_debug_gemm_tn16n(const void* A16, long lda, const void* B16, long ldb, float* C, long ldc, int M, int Nc, long K,
+                                    void* workspace, size_t workspace_bytes, int arith, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(debug_tn_args(A16, lda, B16, ldb, C, ldc, M, Nc, K, workspace, workspace_bytes));
+    return fsn_launch_gemm_tn16n(A16, lda, B16, ldb, C, ldc, M, Nc, K, workspace, static_cast<hipStream_t>(stream), arith);
+}
+extern "C" int fsn_debug_gemm_tn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int Nc, long K,
+                                 void* workspace, size_t workspace_bytes, int arith, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(debug_tn_args(A, lda, B, ldb, C, ldc, M, Nc, K, workspace, workspace_bytes));
+    return fsn_launch_gemm_tn(A, lda, B, ldb, C, ldc, M, Nc, K, workspace, static_cast<hipStream_t>(stream), nullptr, arith);
+}
+// wfrag: G x 32 16-bit words (written here: the packed weight)
+extern "C" int fsn_debug_gemm_dx16(const void* dg16, long ld16, const float* w, void* wfrag, size_t wfrag_bytes, float* dx, long lddx,
+                                   long rows, int G, int I, int arith, void* stream) {
+    CallScope scope(stream);
+    FSN_REQUIRE(dg16 && w && wfrag && dx, "NULL pointer argument");
+    FSN_REQUIRE(rows >= 1 && G >= 1 && I >= 1 && ld16 >= G && lddx >= I, "gemm_dx16: bad shape");
+    if (wfrag_bytes < (size_t)G * 32 * sizeof(unsigned short)) {
+        fsn_set_error("gemm_dx16: weight-fragment scratch too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    return fsn_launch_gemm_dx16(dg16, ld16, w, wfrag, dx, lddx, rows, G, I, static_cast<hipStream_t>(stream), arith);
 }

@@ -561,7 +561,9 @@ constexpr size_t kFsnTnOnePerCu = 96 * 1024;  // LDS reservation (never touched)
 // gemm_tn16_kernels.hip: the same product with both operands 16-bit in memory (LDS-DMA staging, transposing LDS reads);
 // workspace as above
 bool fsn_gemm_tn16h_supported(int M, int Nc, long K);
+int fsn_gemm_tn16h_form(int M, int Nc, long K, int* splits);  // 0 no plan, 1 the 192 x 192 form, 2 the 192 x 384 form; its K splits
 bool fsn_gemm_tn16n_supported(int M, int Nc, long K);  // the narrow form (Nc <= 32) and dx from the 16-bit gate gradients
+int fsn_gemm_tn16n_splits(int M, int Nc, long K);      // its K splits (0: unsupported)
 int fsn_launch_gemm_tn16n(const void* A16, long lda, const void* B16, long ldb, float* C, long ldc, int M, int Nc, long K,
                           void* workspace, hipStream_t s, int arith);
 bool fsn_gemm_dx16_supported(long rows, int G, int I);

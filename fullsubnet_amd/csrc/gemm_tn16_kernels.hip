@@ -326,10 +326,28 @@ static bool tn16h_wide_plan(int M, int Nc, long K32, FsnTnPlan* out) {
     }
     return true;
 }
-bool fsn_gemm_tn16h_supported(int M, int Nc, long K) {
+// which form a product takes and its K splits: 0 none, 1 the 192 x 192 form, 2 the 192 x 384 form.  ONE rule for the
+// launcher, for fsn_gemm_tn16h_supported and for the test query: the square form splits K in whole chunks of 32 rows where
+// fsn_tn_plan counts in 16, and a plan whose splits come out fewer that way is no plan (fsn_gemm_tn16h_supported used to say
+// yes from fsn_tn_plan alone; fsn_lstm2_backward then failed with "gemm_tn16h: no plan", e.g. at T = 4, N = 1552 on 256 CUs)
+static int tn16h_pick(int M, int Nc, long K, FsnTnPlan* p) {
     const long K32 = K & ~31L;
-    if (K32 <= 0) return false;
-    return tn16h_wide_plan(M, Nc, K32, nullptr) || fsn_tn_plan(M, Nc, K32, FSN_ARITH_F16).square != 0;
+    if (K32 <= 0) return 0;
+    if (tn16h_wide_plan(M, Nc, K32, p)) return 2;
+    *p = fsn_tn_plan(M, Nc, K32, FSN_ARITH_F16);
+    if (!p->square) return 0;
+    p->k_per_split = (p->k_per_split + 31) / 32 * 32;  // whole chunks; the last split takes what is left (K32 is a multiple of 32)
+    return (K32 + p->k_per_split - 1) / p->k_per_split == p->splits && p->splits <= fsn_tn_max_splits(M, Nc) ? 1 : 0;
+}
+bool fsn_gemm_tn16h_supported(int M, int Nc, long K) {
+    FsnTnPlan p{};
+    return tn16h_pick(M, Nc, K, &p) != 0;
+}
+int fsn_gemm_tn16h_form(int M, int Nc, long K, int* splits) {
+    FsnTnPlan p{};
+    const int form = tn16h_pick(M, Nc, K, &p);
+    if (splits) *splits = form ? p.splits : 0;
+    return form;
 }
 // the two launches of a planned product under arithmetic AR: the split partials, then their sum + the K % 32 tail rows
 template <int AR>
@@ -357,22 +375,18 @@ static int tn16h_run(const unsigned short* a, long lda, const unsigned short* b,
 }
 int fsn_launch_gemm_tn16h(const void* A16, long lda, const void* B16, long ldb, float* C, long ldc, int M, int Nc, long K,
                           void* workspace, hipStream_t s, int arith) {
-    const long K32 = K & ~31L;
     if ((arith != FSN_ARITH_F16 && arith != FSN_ARITH_BF16) || !fsn_gemm_tn16h_supported(M, Nc, K) || lda % 8 || ldb % 8 ||
         ((size_t)A16 & 15) || ((size_t)B16 & 15)) {
         fsn_set_error("gemm_tn16h: 16-bit arithmetic, M and Nc multiples of 192 with a one-workgroup-per-CU plan, 16-byte aligned rows");
         return FSN_ERR_ARG;
     }
     FsnTnPlan p{};
-    const bool wide = tn16h_wide_plan(M, Nc, K32, &p);
-    if (!wide) {
-        p = fsn_tn_plan(M, Nc, K32, arith);
-        p.k_per_split = (p.k_per_split + 31) / 32 * 32;  // whole chunks; the last split takes what is left (K32 is a multiple of 32)
-        if ((K32 + p.k_per_split - 1) / p.k_per_split != p.splits || p.splits > fsn_tn_max_splits(M, Nc)) {
-            fsn_set_error("gemm_tn16h: no plan for %d x %d, K = %ld", M, Nc, K);
-            return FSN_ERR_ARG;
-        }
+    const int form = tn16h_pick(M, Nc, K, &p);
+    if (!form) {
+        fsn_set_error("gemm_tn16h: no plan for %d x %d, K = %ld", M, Nc, K);
+        return FSN_ERR_ARG;
     }
+    const bool wide = form == 2;
     float* part = static_cast<float*>(workspace);
     const unsigned short *a = static_cast<const unsigned short*>(A16), *b = static_cast<const unsigned short*>(B16);
     return arith == FSN_ARITH_F16 ? tn16h_run<FSN_ARITH_F16>(a, lda, b, ldb, C, ldc, M, Nc, K, part, s, p, wide)
@@ -397,13 +411,8 @@ static int tn16n_run(const unsigned short* a, long lda, const unsigned short* b,
                        lda, b, ldb, K32, K);
     return fsn_check_launch("tn16n_reduce_kernel");
 }
-int fsn_launch_gemm_tn16n(const void* A16, long lda, const void* B16, long ldb, float* C, long ldc, int M, int Nc, long K,
-                          void* workspace, hipStream_t s, int arith) {
-    if ((arith != FSN_ARITH_F16 && arith != FSN_ARITH_BF16) || !fsn_gemm_tn16n_supported(M, Nc, K) || lda % 8 || ldb % 8 || ldb < 32 ||
-        ((size_t)A16 & 15) || ((size_t)B16 & 15)) {
-        fsn_set_error("gemm_tn16n: 16-bit arithmetic, M a multiple of 384, Nc <= 32 in rows of >= 32 16-bit columns, 16-byte aligned rows");
-        return FSN_ERR_ARG;
-    }
+// its K splits (one workgroup per CU, as many as the workspace holds) and the rows of each; 0: not even one partial fits
+static long tn16n_splits(int M, int Nc, long K, long* kps_out) {
     const int cus = plan_cus();
     const long K32 = K & ~31L;
     const int m_blocks = M / 384;
@@ -411,13 +420,27 @@ int fsn_launch_gemm_tn16n(const void* A16, long lda, const void* B16, long ldb, 
     // the partials take 32 columns per split whatever Nc is, while the workspace query counts Nc + 1: with a small Nc on a
     // device of few CUs not even one partial fits
     const long bound = (long)(fsn_gemm_tn_workspace_bytes(M, Nc, K) / ((size_t)M * 32 * sizeof(float)));
-    if (bound < 1) {
+    if (bound < 1) return 0;
+    splits = splits < bound ? splits : bound;
+    const long kps = ((K32 + splits - 1) / splits + 31) / 32 * 32;
+    if (kps_out) *kps_out = kps;
+    return (K32 + kps - 1) / kps;
+}
+int fsn_gemm_tn16n_splits(int M, int Nc, long K) { return fsn_gemm_tn16n_supported(M, Nc, K) ? (int)tn16n_splits(M, Nc, K, nullptr) : 0; }
+int fsn_launch_gemm_tn16n(const void* A16, long lda, const void* B16, long ldb, float* C, long ldc, int M, int Nc, long K,
+                          void* workspace, hipStream_t s, int arith) {
+    if ((arith != FSN_ARITH_F16 && arith != FSN_ARITH_BF16) || !fsn_gemm_tn16n_supported(M, Nc, K) || lda % 8 || ldb % 8 || ldb < 32 ||
+        ((size_t)A16 & 15) || ((size_t)B16 & 15)) {
+        fsn_set_error("gemm_tn16n: 16-bit arithmetic, M a multiple of 384, Nc <= 32 in rows of >= 32 16-bit columns, 16-byte aligned rows");
+        return FSN_ERR_ARG;
+    }
+    const int m_blocks = M / 384;
+    long kps = 0;
+    const long splits = tn16n_splits(M, Nc, K, &kps);
+    if (splits < 1) {
         fsn_set_error("gemm_tn16n: the workspace of a %d x %d product holds no %d x 32 partial", M, Nc, M);
         return FSN_ERR_WORKSPACE;
     }
-    splits = splits < bound ? splits : bound;
-    const long kps = ((K32 + splits - 1) / splits + 31) / 32 * 32;
-    splits = (K32 + kps - 1) / kps;
     float* part = static_cast<float*>(workspace);
     const unsigned short *a = static_cast<const unsigned short*>(A16), *b = static_cast<const unsigned short*>(B16);
     return arith == FSN_ARITH_F16 ? tn16n_run<FSN_ARITH_F16>(a, lda, b, ldb, C, ldc, M, Nc, K, part, s, m_blocks, (int)splits, kps)

@@ -295,16 +295,34 @@ __global__ void reduce_splits_kernel(const float* __restrict__ part, float* __re
 
 // gemm_tn epilogue: sum of the split partials (fixed order) + the K % 16 tail rows the MFMA kernel
 // does not cover; `transposed`: the partials hold C^T ([Nc][M], operands were swapped).
+// Under a 16-bit arithmetic the tail rows' operands are rounded like those of the matrix instructions (they used to enter
+// in fp32: at K = 2069 the product stood at 8.4 u rms against 0.14 u of the fp32 product of the rounded operands,
+// tests/test_gpu_amp_sweep.py; the training step's K = T N are multiples of 16 and have no tail).
+template <int AR>
+__device__ __forceinline__ float tn_tail_term(float a, float b) {
+    if constexpr (AR == FSN_ARITH_F16) {
+        const fsn_f16x4 v = fsn_operand<AR>(f32x4{a, b, 0.f, 0.f});
+        return (float)v[0] * (float)v[1];
+    } else {
+        const fsn_u32x2 v = __builtin_bit_cast(fsn_u32x2, fsn_operand<AR>(f32x4{a, b, 0.f, 0.f}));
+        return __builtin_bit_cast(float, v[0] << 16) * __builtin_bit_cast(float, v[0] & 0xffff0000u);
+    }
+}
 __global__ void tn_reduce_kernel(const float* __restrict__ part, float* __restrict__ C, long ldc, int M, int Nc,
                                  int splits, int transposed, const float* __restrict__ A, long lda,
-                                 const float* __restrict__ B, long ldb, long k_tail0, long K, int accumulate) {
+                                 const float* __restrict__ B, long ldb, long k_tail0, long K, int accumulate, int arith) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)M * Nc) return;
     const int m = (int)(i / Nc), n = (int)(i % Nc);
     const long pi = transposed ? (long)n * M + m : i;
     float acc = 0.f;
     for (int s = 0; s < splits; ++s) acc += part[(long)s * M * Nc + pi];
-    for (long k = k_tail0; k < K; ++k) acc += A[k * lda + m] * B[k * ldb + n];
+    if (arith == FSN_ARITH_F16)
+        for (long k = k_tail0; k < K; ++k) acc += tn_tail_term<FSN_ARITH_F16>(A[k * lda + m], B[k * ldb + n]);
+    else if (arith == FSN_ARITH_BF16)
+        for (long k = k_tail0; k < K; ++k) acc += tn_tail_term<FSN_ARITH_BF16>(A[k * lda + m], B[k * ldb + n]);
+    else
+        for (long k = k_tail0; k < K; ++k) acc += A[k * lda + m] * B[k * ldb + n];
     C[(long)m * ldc + n] = accumulate ? C[(long)m * ldc + n] + acc : acc;  // a later K segment (fsn_launch_gemm_tn)
 }
 
@@ -490,7 +508,7 @@ static int gemm_tn_segment(const float* A, long lda, const float* B, long ldb, f
     }
     const long n = (long)M * Nc;
     hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, C, ldc, M, Nc, splits,
-                       swap ? 1 : 0, A_all, lda, B_all, ldb, k_tail0, K_all, accumulate ? 1 : 0);
+                       swap ? 1 : 0, A_all, lda, B_all, ldb, k_tail0, K_all, accumulate ? 1 : 0, arith);
     FSN_TRY_LAUNCH("tn_reduce_kernel");
     if (colsum_out) {
         hipLaunchKernelGGL(tn_colsum_reduce_kernel, dim3((M + 255) / 256), dim3(256), 0, s, asum_part, colsum_out, M,

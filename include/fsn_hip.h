@@ -53,7 +53,8 @@ extern "C" {
  * backward pass re-reads are saved in the arithmetic's 16-bit type instead of fp32 - what the vendor LSTM the reference
  * trains on keeps in its reserve space under autocast (fullsubnet/trainer.py:56) - inside the same save buffers; the cell
  * sequence, the hidden sequences and every gradient stay fp32.  Takes effect where the 16-bit arithmetic's own kernels run
- * (lstm_group16_kernels.hip); ignored elsewhere.  Half the save traffic of the two persistent launches. */
+ * BOTH directions (lstm_group16_kernels.hip; field 12 of fsn_debug_lstm2_plan16); ignored elsewhere, where the saves and
+ * every result are those of the call without the flag.  Half the save traffic of the two persistent launches. */
 #define FSN_ARITH_SAVES16 0x100
 
 const char* fsn_last_error(void);
@@ -805,6 +806,37 @@ int fsn_debug_g16_kernels(int on);
 /* 0: the 16-bit-operand weight-gradient products on 192 x 192 tiles also where the 192 x 384 eight-wave form applies (both
  * give bit-identical partial products; the split count differs).  A/B measurements and tests. */
 int fsn_debug_tn16h_wide(int on);
+/* Test hook that needs no device: the plan of the two-layer training entries under `arith` (FSN_ARITH_F32 / _F16 / _BF16
+ * [| FSN_ARITH_SAVES16]) for x rows of ldx columns, decided from the shape alone (and the two switches above).
+ * out[0..n) of: 0 the forward runs in the 16-bit arithmetic at all, 1 the backward does, 2 the forward on the 16-bit
+ * arithmetic's own kernel, 3 the BPTT on it, 4 the three large weight-gradient products from 16-bit operands in memory
+ * (tn16h), 5 their form at K = (T - 1) N (0 none, 1 192 x 192 tiles, 2 192 x 384), 6 dx and dW_ih0 from the 16-bit gate
+ * gradients too (in16), 7 the products read the 16-bit h_t of the save slots (h16_saved), 8 rows beside the backward
+ * launch (step by step, fp32), 9 its clusters, 10 rows beside the forward launch, 11 its clusters, 12 FSN_ARITH_SAVES16
+ * in force (asked for, and both directions on the 16-bit arithmetic's own kernels: otherwise the gates are saved and read in
+ * fp32 whatever the flag).  Returns the number of fields written (at most 13), -1 on bad arguments. */
+int fsn_debug_lstm2_plan16(int T, int N, int I, long ldx, int H, int arith, int* out, int n);
+/* Test hooks: the 16-bit training arithmetic's conversion and weight-gradient / dx products on caller data, each the
+ * internal launcher unchanged behind shape, pointer and size checks (the launcher's own refusals - no plan for the shape,
+ * alignment, arithmetic - come back as FSN_ERR_ARG with nothing written).  arith: FSN_ARITH_F16 / _BF16 (gemm_tn: _F32 too).
+ * to16: dst[0..n) = src rounded to nearest even, n % 4 == 0.
+ * gemm_tn16h / gemm_tn16n / gemm_tn: C [M][ldc >= Nc] = A^T B over K rows, A [K][lda], B [K][ldb] 16-bit (gemm_tn: fp32,
+ *   rounded on load under a 16-bit arith); tn16n reads 32 columns of B (those beyond Nc zero).  Workspace:
+ *   fsn_debug_gemm_tn_workspace_bytes(M, Nc, K).  fsn_debug_tn16_plan: *form = 0 when the 16-bit-operand product has no
+ *   plan at this shape (narrow != 0: tn16n, form 0 / 1; else tn16h, 1 = 192 x 192 tiles, 2 = 192 x 384), *splits its K splits.
+ * gemm_dx16: dx [rows][lddx] columns 0 .. I - 1 = dg16 [rows][ld16] (16-bit) x w [G][I] (fp32, rounded here); wfrag:
+ *   scratch of G x 32 16-bit words. */
+size_t fsn_debug_gemm_tn_workspace_bytes(int M, int Nc, long K);
+int fsn_debug_tn16_plan(int narrow, int M, int Nc, long K, int* splits, int* form);
+int fsn_debug_to16(const float* src, void* dst, size_t n, int arith, void* stream);
+int fsn_debug_gemm_tn16h(const void* A16, long lda, const void* B16, long ldb, float* C, long ldc, int M, int Nc, long K,
+                         void* workspace, size_t workspace_bytes, int arith, void* stream);
+int fsn_debug_gemm_tn16n(const void* A16, long lda, const void* B16, long ldb, float* C, long ldc, int M, int Nc, long K,
+                         void* workspace, size_t workspace_bytes, int arith, void* stream);
+int fsn_debug_gemm_tn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int Nc, long K,
+                      void* workspace, size_t workspace_bytes, int arith, void* stream);
+int fsn_debug_gemm_dx16(const void* dg16, long ld16, const float* w, void* wfrag, size_t wfrag_bytes, float* dx, long lddx,
+                        long rows, int G, int I, int arith, void* stream);
 /* Test hooks that need no device.  fsn_debug_persist_set_fits: 1 when the gate would let n persistent launches with the
  * given chip fractions (grid / (occ x CUs)) and occupancies run side by side, 0 when the newest has to wait.
  * fsn_debug_tn_plan: the K splits a weight-gradient product [M x Nc], K rows, would take (*splits) and the bound the
