@@ -289,6 +289,8 @@ SIGNATURES = {
                                        _c.c_long, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
     "fsn_debug_core_chunks": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
     "fsn_debug_core_plan": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int]),
+    "fsn_debug_core_call_plan": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_long, _c.c_long, _c.c_void_p, _c.c_int]),
+    "fsn_debug_core_last_launches": (_c.c_uint, []),
     "fsn_improved_front": (_c.c_int, [_f32p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_void_p]),
     "fsn_bft_to_rows": (_c.c_int, [_f32p, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_int, _c.c_int, _c.c_void_p]),
     "fsn_rows_to_bft": (_c.c_int, [_f32p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_void_p]),
@@ -440,6 +442,28 @@ def core_plan(cfg, B, T):
     keys = ("rows", "tiles", "row_tiles_per_workgroup", "persistent_workgroups", "left_over_tiles", "group_clusters",
             "fullband_chain", "chunks", "persistent_rows_all_chunks")  # the first seven: the FIRST chunk's plan
     return dict(zip(keys, list(buf)))
+
+
+CORE_CALL_PLAN = ("rows", "tiles", "npad", "rt", "main_wgs", "left_tiles", "grp_clusters", "grp_aux_tiles", "cu_tiles",
+                  "aux_tiles", "fb_chain", "npad_fb", "fc_fused", "l1x", "kin_chunks")
+# bits of fsn_debug_core_last_launches, in the order of FsnTraceBit (csrc/fsn_common.h)
+LAUNCH_BITS = ("lstm_rec", "lstm_rec_in", "lstm_rec_x", "lstm_step", "lstm_step_cu", "lstm_wavefront2", "lstm2_group", "fb_chain",
+               "gemm_sb_proj", "gemm_sb_l1", "gemm_sb_out")
+
+
+def core_call_plan(cfg, B, T, row_begin=0, row_end=-1):
+    """The plan of ONE model-core call (fsn_debug_core_call_plan): the B utterances whole (row_end < 0; what a chunk of
+    fsn_fullsubnet_forward runs) or the rows [row_begin, row_end) as fsn_fullsubnet_forward_rows forms them."""
+    buf = (ctypes.c_int * len(CORE_CALL_PLAN))()
+    if lib().fsn_debug_core_call_plan(ctypes.byref(cfg), B, T, row_begin, row_end, buf, len(buf)) != 0:
+        raise FsnError("fsn_debug_core_call_plan: bad arguments")
+    return dict(zip(CORE_CALL_PLAN, list(buf)))
+
+
+def core_last_launches():
+    """Names of the launchers (and sub-band GEMM sites) the last library call of THIS thread went through."""
+    m = lib().fsn_debug_core_last_launches()
+    return {name for k, name in enumerate(LAUNCH_BITS) if m >> k & 1}
 
 
 def profile_read(device=None):

@@ -323,6 +323,7 @@ void chain_launch(const ChainArgs& a, hipStream_t s) {
 int fsn_launch_fb_chain(const float* gx0, const float* whh0_p, const float* wih1_p, const float* whh1_p, const float* b1,
                         float* exchange, unsigned* flags, float* hseq1, int Tp, int Npad, int H, hipStream_t s,
                         float* hseq0, float* save0, float* save1, int cell) {
+    fsn_trace(FSN_TR_FB_CHAIN);
     if (!fsn_fb_chain_supported(H, Npad) || Tp < 1 || Tp > fsn_fb_chain_max_steps()) {
         fsn_set_error("fb_chain: built for H = 384 / 512, at most 64 rows and 4095 steps");
         return FSN_ERR_ARG;

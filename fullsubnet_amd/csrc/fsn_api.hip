@@ -192,6 +192,8 @@ PersistLaunch::~PersistLaunch() {
 static thread_local StreamCtx* t_ctx = nullptr;
 static thread_local hipStream_t t_stream = nullptr;
 static thread_local int t_dev = 0;
+static thread_local unsigned t_launch_trace = 0;  // FsnTraceBit mask of the running (or last) call on this thread
+void fsn_trace(unsigned bit) { t_launch_trace |= bit; }
 
 static StreamCtx* ctx_lookup(int dev, hipStream_t s) {
     std::lock_guard<std::mutex> lock(g_ctx_mutex);
@@ -226,6 +228,7 @@ FsnCallScope::FsnCallScope(void* stream) : prev(-1), switched(false) {
     t_dev = (int)sd;
     t_stream = s;
     t_ctx = nullptr;
+    t_launch_trace = 0;
 }
 FsnCallScope::~FsnCallScope() {
     t_ctx = nullptr;
@@ -389,6 +392,7 @@ extern "C" int fsn_debug_persist_stats(unsigned* launches, unsigned* waits, unsi
     if (unreported) *unreported = g_persist_unreported.load(std::memory_order_relaxed);
     return FSN_OK;
 }
+extern "C" unsigned fsn_debug_core_last_launches(void) { return t_launch_trace; }
 extern "C" int fsn_set_persistent_timeout_ms(int ms) {
     FSN_REQUIRE(ms >= 1 && ms <= 3600000, "timeout %d ms out of range [1, 3600000]", ms);
     g_persist_timeout_ms.store(ms, std::memory_order_relaxed);

@@ -1,6 +1,8 @@
 // C ABI of libfsn_hip.so, the FullSubNet model (fullsubnet/model.py): weight packing, the model core and its batch
 // chunking, the full-band / row-range / streaming forms, the STFT / iSTFT and elementwise boundary and the whole
 // enhancement path (fsn_enhance, fsn_enhance_ragged).
+#include <algorithm>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -224,14 +226,22 @@ static CoreWs core_carve(Carver& cv, const CoreDims& d, int norm_type) {
 
 // One sub-band LSTM layer over all Tp steps: the persistent kernel on `s` and, concurrently, the
 // few left-over row tiles as per-step launches on the auxiliary stream (the fields of RecArgs, fsn_api_internal.h).
+// How run_recurrence spreads the rows that run step by step (also what fsn_debug_core_call_plan reports).
+// No persistent part (fewer than ~160 tiles): the steps run on the caller's stream itself - groups of four tiles through
+// the one-workgroup-per-CU step kernel (cu_tiles), the up to three tiles that do not fill a group beside it on the
+// auxiliary stream (a 33rd group of 8 workgroups would be a second round on 8 CUs and double the step).
+struct StepSplit {
+    int cu_tiles, aux_tiles;
+};
+static StepSplit step_split(const FsnRecPlan& r) {
+    const int cu_tiles = r.main_wgs == 0 && r.left_tiles >= 8 ? r.left_tiles / 4 * 4 : 0;
+    return StepSplit{cu_tiles, r.left_tiles - cu_tiles};
+}
 int run_recurrence(const RecArgs& a, hipStream_t s) {
     const FsnRecPlan& r = a.plan;
     const int Tp = a.Tp, Npad = a.Npad, H = a.H;
-    // No persistent part (fewer than ~160 tiles): the steps run on `s` itself - groups of four tiles through the
-    // one-workgroup-per-CU step kernel, the up to three tiles that do not fill a group beside it on the
-    // auxiliary stream (a 33rd group of 8 workgroups would be a second round on 8 CUs and double the step).
-    const int cu_tiles = r.main_wgs == 0 && r.left_tiles >= 8 ? r.left_tiles / 4 * 4 : 0;
-    const int aux_tiles = r.left_tiles - cu_tiles;
+    const StepSplit split = step_split(r);
+    const int cu_tiles = split.cu_tiles, aux_tiles = split.aux_tiles;
     const bool fork = aux_tiles > 0 && (r.main_wgs > 0 || cu_tiles > 0);
     hipStream_t ls = s;
     if (fork) FSN_TRY(aux_fork(s, &ls));
@@ -351,6 +361,7 @@ static int core_sb_divisor(const CoreCall& k) {
 // Projection of layer 0 for the `tiles` row tiles per step from local row `first` on -> w.gx_sb (rows that run step by step)
 static int core_sb_projection(const CoreCall& k, const FsnSbInput& xin, long first, int tiles) {
     StageTimer st(ST_SB_GEMM_L0, k.s);
+    fsn_trace(FSN_TR_GEMM_SB_PROJ);
     // the provider works on global rows: first row and row limit
     return fsn_launch_gemm(gemm_a_subband(xin, k.d.row0 + first, tiles * 16), k.pk + k.p.sb_wih0,
                            gemm_c_frag(k.w.gx_sb, k.pk + k.p.sb_b0), k.d.Tp * tiles, 4 * k.d.Hs / 16, k.p.sb_kin_pad / 16, k.s);
@@ -358,6 +369,7 @@ static int core_sb_projection(const CoreCall& k, const FsnSbInput& xin, long fir
 // Output layer (model.py:53-61,129-135) of the `tiles` row tiles per step from local row `first` on, w.hseq_sb1 -> mask planes
 static int core_sb_output(const CoreCall& k, long first, int tiles, hipStream_t s) {
     const CoreDims& d = k.d;
+    fsn_trace(FSN_TR_GEMM_SB_OUT);
     // global rows, like the A provider above
     return fsn_launch_gemm(gemm_a_rows(k.w.hseq_sb1, d.Hs), k.pk + k.p.sb_fc,
                            gemm_c_masks(k.g, k.crm_r, k.crm_i, k.pk + k.p.sb_fcb, tiles * 16, d.row0 + first, d.row0 + d.N),
@@ -476,6 +488,7 @@ static int core_sb_persistent(const CoreCall& k, const FsnSbInput& xin, const Fs
         // the main rows form this projection inside lstm_rec_x_kernel; only the left-over rows (step kernels) get one
         if (d.rec.left_tiles > 0) {
             StageTimer st(ST_SB_GEMM_L1, s);
+            fsn_trace(FSN_TR_GEMM_SB_L1);
             FSN_TRY(fsn_launch_gemm(gemm_a_rows(w.hseq_left0, d.Hs), pk + p.sb_wih1, gemm_c_frag(w.gx_sb, pk + p.sb_b1),
                                     d.Tp * d.rec.left_tiles, 4 * d.Hs / 16, d.Hs / 16, s));
         }
@@ -485,6 +498,7 @@ static int core_sb_persistent(const CoreCall& k, const FsnSbInput& xin, const Fs
         l1.bias_main = pk + p.sb_b1;
     } else {
         StageTimer st(ST_SB_GEMM_L1, s);
+        fsn_trace(FSN_TR_GEMM_SB_L1);
         if (f16x3)
             FSN_TRY(fsn_launch_gemm_f16x3(w.hseq_sb0, d.Hs, pk + p.sb_wih1_f16x3, pk + p.sb_b1, w.gx_sb, sb_rt, 4 * d.Hs,
                                           d.Hs, s));
@@ -613,7 +627,11 @@ static int core_chunks_search(const fsn_fullsubnet_cfg* cfg, int B, int* sizes, 
             }
         }
     }
+    const int rem_begin = n;
     for (int b = rem; b > 0 && n < max_sizes; b -= first[b]) sizes[n++] = first[b];
+    // largest first, as documented: the search puts the round size it picked before what is left, which may be the
+    // larger (17 utterances: 8, then 9 - found on the device by tests/test_host_cpu.py, whose plans need one)
+    std::sort(sizes + rem_begin, sizes + n, std::greater<int>());
     return n;
 }
 constexpr int kMaxChunks = 80;  // 4096 utterances (check_bt) in rounds of >= 64, plus the remainder's few calls
@@ -676,6 +694,34 @@ extern "C" int fsn_debug_core_plan(const fsn_fullsubnet_cfg* cfg, int B, int T, 
         }
         plan[8] = (int)rows;
     }
+    return FSN_OK;
+}
+
+// the CoreDims of one core call, whole utterances or a row slice (defined with the row-range form below)
+static int core_call_dims(const fsn_fullsubnet_cfg* cfg, int B, int T, long row_begin, long row_end, CoreDims* d);
+
+extern "C" int fsn_debug_core_call_plan(const fsn_fullsubnet_cfg* cfg, int B, int T, long row_begin, long row_end, int* plan,
+                                        int n) {
+    if (check_cfg(cfg) != FSN_OK || check_bt(B, T) != FSN_OK || !plan || n < 15) return -1;
+    CoreDims d;
+    if (core_call_dims(cfg, B, T, row_begin, row_end, &d) != FSN_OK) return -1;
+    const StepSplit split = step_split(d.rec);
+    const bool persistent = d.grp_clusters == 0 && !(d.rec.main_wgs == 0 && d.rec.left_tiles < kWavefrontBelowTiles);
+    plan[0] = d.N;
+    plan[1] = d.rec.tiles;
+    plan[2] = d.Npad;
+    plan[3] = d.rec.rt;
+    plan[4] = d.rec.main_wgs;
+    plan[5] = d.rec.left_tiles;
+    plan[6] = d.grp_clusters;
+    plan[7] = d.grp_clusters > 0 ? d.rec.tiles - 4 * d.grp_clusters : 0;
+    plan[8] = persistent ? split.cu_tiles : 0;   // run_recurrence is only reached in the persistent / step regime
+    plan[9] = persistent ? split.aux_tiles : 0;
+    plan[10] = d.fb_chain ? 1 : 0;
+    plan[11] = d.Npad_fb;
+    plan[12] = d.fc_fused ? 1 : 0;
+    plan[13] = d.l1x ? 1 : 0;
+    plan[14] = packed_layout(cfg).sb_kin_pad / 16;
     return FSN_OK;
 }
 
@@ -775,12 +821,26 @@ static int row_slice(const fsn_fullsubnet_cfg* cfg, int B, long row_begin, long 
     return FSN_OK;
 }
 
+// The CoreDims of ONE core call: row_end < 0 - the B utterances whole, as a chunk of fsn_fullsubnet_forward runs them;
+// otherwise the slice [row_begin, row_end) exactly as fsn_fullsubnet_forward_rows forms it.
+static int core_call_dims(const fsn_fullsubnet_cfg* cfg, int B, int T, long row_begin, long row_end, CoreDims* d) {
+    if (row_end < 0) {
+        *d = core_dims(cfg, B, T);
+        return FSN_OK;
+    }
+    RowSlice r;
+    FSN_TRY(row_slice(cfg, B, row_begin, row_end, &r));
+    *d = core_dims(cfg, r.Bs, T, r.r0, r.n);
+    return FSN_OK;
+}
+
 extern "C" size_t fsn_fullsubnet_rows_workspace_bytes(const fsn_fullsubnet_cfg* cfg, int B, int T, long row_begin,
                                                       long row_end) {
     RowSlice r;
     if (check_cfg(cfg) != FSN_OK || check_bt(B, T) != FSN_OK || row_slice(cfg, B, row_begin, row_end, &r) != FSN_OK)
         return 0;
-    const CoreDims d = core_dims(cfg, r.Bs, T, r.r0, r.n);
+    CoreDims d;
+    if (core_call_dims(cfg, B, T, row_begin, row_end, &d) != FSN_OK) return 0;
     Carver cv(nullptr);
     cv.take<float>((size_t)r.Bs * d.Tp * d.FP);  // magT
     cv.take<float>((size_t)r.Bs * d.T * d.FP);   // crm_r
@@ -804,7 +864,8 @@ extern "C" int fsn_fullsubnet_forward_rows(const fsn_fullsubnet_cfg* cfg, const 
         return FSN_ERR_WORKSPACE;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const CoreDims d = core_dims(cfg, r.Bs, T, r.r0, r.n);
+    CoreDims d;
+    FSN_TRY(core_call_dims(cfg, B, T, row_begin, row_end, &d));
     Carver cv(workspace);
     float* magT = cv.take<float>((size_t)r.Bs * d.Tp * d.FP);
     float* crm_r = cv.take<float>((size_t)r.Bs * d.T * d.FP);

@@ -48,6 +48,23 @@ struct FsnCallScope {
 };
 int fsn_check_launch(const char* what);
 
+// Launch trace (test hook, fsn_debug_core_last_launches): one 32-bit mask per host thread, cleared by FsnCallScope at
+// entry; every launcher the model core can reach, and the core's three sub-band GEMM sites, OR their bit in.
+enum FsnTraceBit : unsigned {
+    FSN_TR_LSTM_REC = 1u << 0,
+    FSN_TR_LSTM_REC_IN = 1u << 1,
+    FSN_TR_LSTM_REC_X = 1u << 2,
+    FSN_TR_LSTM_STEP = 1u << 3,
+    FSN_TR_LSTM_STEP_CU = 1u << 4,
+    FSN_TR_LSTM_WAVEFRONT2 = 1u << 5,
+    FSN_TR_LSTM2_GROUP = 1u << 6,
+    FSN_TR_FB_CHAIN = 1u << 7,
+    FSN_TR_GEMM_SB_PROJ = 1u << 8,  // layer-0 projection of rows that run step by step (core_sb_projection)
+    FSN_TR_GEMM_SB_L1 = 1u << 9,    // layer-1 projection GEMM (whole, or of the left-over rows under lstm_rec_x)
+    FSN_TR_GEMM_SB_OUT = 1u << 10,  // output layer as a GEMM (core_sb_output)
+};
+void fsn_trace(unsigned bit);  // fsn_api.hip
+
 // Raise `kernel`'s dynamic-LDS limit to at least `bytes` on the current device, before a launch that asks for more than
 // the 64 KB every kernel may have.  Called at every such launch; the runtime is asked once per (device, kernel) and size
 // that grows - the limit belongs to that pair, so the record is keyed by it, and it is kept under a mutex (the per-launcher

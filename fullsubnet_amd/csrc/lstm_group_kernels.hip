@@ -563,6 +563,7 @@ int fsn_lstm2_group_clusters(int tiles) {
 int fsn_launch_lstm2_group(const FsnSbInput* xin, const float* whh0_p, const float* wih1_p, const float* whh1_p,
                            const float* bias1, float* exchange, unsigned* flags, const FsnRecFc* fc, int Tp, int clusters,
                            int H, hipStream_t s) {
+    fsn_trace(FSN_TR_LSTM2_GROUP);
     if (H != GH || !xin || xin->x_rows || xin->kin_chunks != 2 || !fc || !fc->w_p || clusters < 1) {
         fsn_set_error("lstm2_group: built for the sub-band model (H = 384, 32 input columns, fused output layer)");
         return FSN_ERR_ARG;

@@ -351,6 +351,7 @@ bool fsn_lstm_rec_in_supported(const FsnSbInput* xin, const float* whh_p, int H,
 
 int fsn_launch_lstm_rec_in(const FsnSbInput* xin, const float* whh_p, float* hseq, int Tp, int Npad, int H, int RT,
                            int main_wgs, hipStream_t s, int cell) {
+    fsn_trace(FSN_TR_LSTM_REC_IN);
     if (!fsn_lstm_rec_in_supported(xin, whh_p, H, RT) || (cell && !xin->x_rows)) {
         fsn_set_error("lstm_rec_in: unsupported configuration");
         return FSN_ERR_ARG;

@@ -493,7 +493,8 @@ bool fsn_lstm_rec_can_fuse_fc(int RT, bool xin) { return !xin && RT >= 2; }
 
 int fsn_launch_lstm_rec(const float* gx, const FsnSbInput* xin, const float* whh_p, float* hseq, int Tp, int Npad,
                         int H, int RT, int main_wgs, hipStream_t s, const FsnRecFc* fc) {
-#define FSN_REC_CASE(HH, R)                                                                              \
+    fsn_trace(FSN_TR_LSTM_REC);
+#define FSN_REC_CASE(HH, R)                                                                             \
     if (H == HH && RT == R)                                                                              \
         return xin ? launch_rec<HH, R, true>(gx, xin, whh_p, hseq, Tp, Npad, main_wgs, s, fc)            \
                    : launch_rec<HH, R, false>(gx, xin, whh_p, hseq, Tp, Npad, main_wgs, s, fc);

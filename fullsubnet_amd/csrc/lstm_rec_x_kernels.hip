@@ -428,6 +428,7 @@ bool fsn_lstm_rec_x_supported(int H, int RT) { return H == 384 && RT >= 2 && RT 
 
 int fsn_launch_lstm_rec_x(const float* xseq, const float* wih_p, const float* whh_p, const float* bias, int Tp, int Npad,
                           int H, int RT, int main_wgs, hipStream_t s, const FsnRecFc* fc, float* hseq_out, int cell) {
+    fsn_trace(FSN_TR_LSTM_REC_X);
     if (((!fc || !fc->w_p) && !hseq_out) || !fsn_lstm_rec_x_supported(H, RT)) {
         fsn_set_error("lstm_rec_x: needs the fused output layer or a hidden-sequence buffer, H = 384 and 2 - 4 row tiles "
                       "(got H %d, RT %d)", H, RT);

@@ -546,6 +546,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(40))) void lstm
 // ordered projection, h_prev / h_out / c point at the first of those rows.
 int fsn_launch_lstm_step(const float* gx, const float* whh_p, const float* h_prev, float* h_out, float* c,
                          long gx_rt0, int row_tiles, int H, int first, hipStream_t s, int beside_persistent) {
+    fsn_trace(FSN_TR_LSTM_STEP);
     if (beside_persistent) {  // must fit next to a resident persistent workgroup, see lstm_step1_kernel
         if (H % 64 != 0) {
             fsn_set_error("lstm_step: hidden size %d must be a multiple of 64", H);
@@ -563,6 +564,7 @@ int fsn_launch_lstm_step(const float* gx, const float* whh_p, const float* h_pre
 int fsn_launch_lstm_step_cu(const float* gx, const float* whh_p, const float* h_prev, float* h_out, float* c,
                             long gx_rt0, int row_tiles, int H, int first, hipStream_t s, const float* c_prev,
                             float* gates_out) {
+    fsn_trace(FSN_TR_LSTM_STEP_CU);
     if (!c_prev) c_prev = c;
     if (H % 16 != 0 || row_tiles % 4 != 0 || row_tiles <= 0) {
         fsn_set_error("lstm_step_cu: H %d must be a multiple of 16 and row_tiles %d a positive multiple of 4", H, row_tiles);
@@ -693,6 +695,7 @@ int fsn_launch_lstm_wavefront2(const float* gx0, long gx_stride, long gx_off, co
                                const float* bias1_frag, const float* whh1_p, float* hseq0, float* hseq1, long hs_stride,
                                long hs_off, float* c0, float* c1, int T, int row_tiles, int H, hipStream_t s,
                                float* state_h0, float* state_h1, int beside_group) {
+    fsn_trace(FSN_TR_LSTM_WAVEFRONT2);
     return fsn_launch_lstm_wavefront2w(gx0, gx_stride, gx_off, whh0_p, wih1_p, bias1_frag, whh1_p, hseq0, hseq1,
                                        hs_stride, hs_off, c0, c1, T, row_tiles, H, H, s, state_h0, state_h1, beside_group);
 }

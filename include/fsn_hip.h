@@ -845,7 +845,8 @@ int fsn_debug_persist_set_fits(int n, const double* fracs, const int* occs);
 int fsn_debug_tn_plan(int M, int Nc, long K, int arith, int* splits, long* bound);
 /* Test hook: fsn_enhance / fsn_fullsubnet_forward run a batch of B utterances as one or several calls of the model core
  * (whole rounds of the persistent kernels, a remainder split by a cost model of the plans - the model has no
- * cross-utterance term); sizes[0..n) = their utterance counts, n returned (max_sizes >= 80), -1 on bad arguments. */
+ * cross-utterance term); sizes[0..n) = their utterance counts, largest first, n returned (max_sizes >= 80), -1 on bad
+ * arguments. */
 int fsn_debug_core_chunks(const fsn_fullsubnet_cfg* cfg, int B, int* sizes, int max_sizes);
 /* Diagnostic: how the sub-band model of a B-utterance, T-frame call is spread over the device (of its first chunk when the
  * batch runs as several).  plan[0..8) = sub-band rows, 16-row tiles, row tiles per workgroup of the persistent pair, its
@@ -854,6 +855,20 @@ int fsn_debug_core_chunks(const fsn_fullsubnet_cfg* cfg, int B, int* sizes, int 
  * the persistent pair processes summed over ALL chunks (whole rounds and a remainder have different plans).  bench.py
  * prints it per rank and counts the roofline's FLOPs on the rows the persistent launches actually process. */
 int fsn_debug_core_plan(const fsn_fullsubnet_cfg* cfg, int B, int T, int* plan, int n);
+/* Test hook: the plan of ONE call of the model core, formed by the code the entries themselves use.  row_end < 0: the B
+ * utterances whole as a single call (what one chunk of fsn_fullsubnet_forward runs; no chunking is applied here);
+ * otherwise the row slice [row_begin, row_end) exactly as fsn_fullsubnet_forward_rows forms it.  plan[0..15) (n >= 15):
+ * 0 sub-band rows N, 1 16-row tiles (padding tiles of whole rounds included), 2 padded rows, 3 row tiles per workgroup of
+ * the persistent pair, 4 its workgroups, 5 left-over tiles, 6 clusters of the group kernel, 7 tiles beside the group
+ * launch, 8 / 9 tiles on the one-workgroup-per-CU step kernel / on the small step kernel of the persistent and step
+ * regimes (0 in the other regimes), 10 full-band model on the chain kernel, 11 its padded rows, 12 output layer fused into
+ * layer 1's persistent kernel, 13 layer 1 on lstm_rec_x, 14 16-column chunks of the sub-band input.  -1 on bad arguments. */
+int fsn_debug_core_call_plan(const fsn_fullsubnet_cfg* cfg, int B, int T, long row_begin, long row_end, int* plan, int n);
+/* Test hook: which launchers the last call of this library ON THE CALLING THREAD went through - one 32-bit mask per
+ * thread, cleared when an entry that enqueues work is entered.  Bits, from 0: lstm_rec, lstm_rec_in, lstm_rec_x,
+ * lstm_step, lstm_step_cu, lstm_wavefront2, lstm2_group, fb_chain, then the model core's sub-band GEMM sites: layer-0
+ * projection of rows that run step by step, layer-1 projection, output layer as a GEMM. */
+unsigned fsn_debug_core_last_launches(void);
 int fsn_profile_num_stages(void);
 const char* fsn_profile_stage_name(int stage);
 int fsn_profile_read(void* stream, float* ms_per_stage, int n);

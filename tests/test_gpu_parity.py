@@ -264,11 +264,12 @@ def test_oracle_parity_fresh_weights(fsn):
 def test_more_row_tiles_than_cus(fsn, batch):
     """(Also the three shapes of the full-band chain kernel: one row tile with K split over four waves, two row tiles
     x two K halves at batch 24, one row tile per wave from batch 33.)
-    B*F/16 > 256 tiles: the persistent recurrent kernel takes floor(tiles/CUs) tiles per CU and
-    the left-over tiles run step by step on the auxiliary stream (B=16: 257 tiles -> 256 + 1;
-    B=33: 531 tiles -> 2 x 256 + 19 -> general multi-round plan; B=48: 771 tiles -> 3 x 256 + 3).  At 2 - 4 tiles
-    per workgroup the last layer forms its input projection itself (lstm_rec_x_kernel); at one tile per workgroup it
-    runs on the projection GEMM + lstm_rec_kernel pair.  Every row must still match."""
+    B*F/16 > 256 tiles.  The plans, as fsn_debug_core_call_plan reports them at 256 CUs (tests/test_gpu_core_sweep.py asserts
+    each): B=16: 257 tiles -> 64 clusters of the two-per-set group kernel + 1 tile beside it; B=24: two core calls of 16 + 8
+    utterances (64 clusters + 1, 32 clusters + 1); B=33: core calls of 32 + 1 (514 tiles -> 256 workgroups x 2 tiles + 2
+    left-over tiles step by step on the auxiliary stream; 17 tiles on the per-step wavefront); B=48: 771 tiles -> 256 x 3 + 3.
+    At 2 - 4 tiles per workgroup the last layer forms its input projection itself (lstm_rec_x_kernel).  Every row must
+    still match."""
     meta = dict(seed_w=5, gain=2.0, mask_gain=24.0, norm_type="offline_laplace_norm", groups=1)
     model, params = build_model(fsn, meta)
     noisy = O.make_noisy(batch, 1300, seed=31)
@@ -281,9 +282,10 @@ def test_more_row_tiles_than_cus(fsn, batch):
 
 @pytest.mark.parametrize("batch", [10, 24, 40, 96, 104, 128])
 def test_full_rounds_plus_leftover_tiles_for_large_batches(fsn, batch):
-    """More than five row tiles per CU: the plan takes FULL rounds of the persistent kernels and hands the few tiles that
-    remain to the step kernels (96 utterances: 1542 tiles = two rounds of 3 tiles per workgroup + 6; 128: two rounds of 4
-    + 8 - where whole rounds only would take three).  The model has no cross-utterance term: every utterance must equal
+    """More than 64 utterances run as core calls of 64 (256 workgroups x 4 tiles + 4 left-over tiles) and a remainder: 96 =
+    64 + 32, 104 = 64 + 32 + 8, 128 = 64 + 64 (core_chunk splits at 64, so the full-rounds plans of fsn_lstm_rec_plan - two
+    rounds of 4 + 8 tiles for 2056 tiles - are reached through fsn_fullsubnet_forward_rows only; tests/test_gpu_core_sweep.py
+    runs them).  The model has no cross-utterance term: every utterance must equal
     its result in a batch of 32 (another plan: one round of 2 tiles per workgroup, held to the oracle above).  Likewise
     the batches BETWEEN the regimes (10, 24, 40: run as 8 + 2, 16 + 8, 32 + 8 by the cost model of run_core_chunks) against
     batches of 8 (the group kernel, held to the oracle by test_few_rows_on_the_group_kernel)."""
@@ -425,11 +427,11 @@ def test_errors_are_loud(fsn):
     (161, 1, 7, 256, 3, 9, "offline_laplace_norm"),       # another spectrum size / neighbourhood / full-band width
     (129, 3, 0, 128, 2, 6, "cumulative_laplace_norm"),    # no neighbours at all: K = 2 -> one padded chunk
     (65, 2, 31, 64, 5, 4, "cumulative_laplace_norm"),     # neighbourhood almost as wide as the spectrum
-    (257, 2, 15, 512, 17, 3, "offline_laplace_norm"),     # 273 row tiles: persistent kernel + 17 left-over tiles
-    (257, 2, 15, 512, 8, 3, "offline_laplace_norm"),      # 129 row tiles: 32 groups of four through the
-                                                          # one-workgroup-per-CU step kernel + 1 tile beside it
+    (257, 2, 15, 512, 17, 3, "offline_laplace_norm"),     # two core calls of 9 + 8 utterances: the group kernel with 32
+                                                          # clusters + 17 / + 1 tiles beside it
+    (257, 2, 15, 512, 8, 3, "offline_laplace_norm"),      # 129 row tiles: 32 clusters of the group kernel + 1 tile beside it
     (161, 1, 7, 256, 11, 4, "cumulative_laplace_norm"),   # 111 row tiles: 27 groups (two unit groups per wave) + 3
-    (257, 1, 15, 512, 6, 2, "offline_laplace_norm"),      # 97 row tiles: the first size of the step regime
+    (257, 1, 15, 512, 6, 2, "offline_laplace_norm"),      # 97 row tiles: 24 clusters of the group kernel + 1 tile beside it
 ])
 def test_fused_forward_other_shapes_vs_oracle(fsn, F, la, nb, fbh, B, T, norm):
     """fsn_fullsubnet_forward away from the shipped configuration (cfg fields are free: num_freqs, look_ahead,
