@@ -10,6 +10,7 @@ from .acoustics.mask import (build_complex_ideal_ratio_mask, complex_mul, compre
 from .graphs import GraphedCall  # noqa: F401
 from .inferencer import Inferencer  # noqa: F401
 from .long_form import LongPlan  # noqa: F401
+from .mix import MixBank, MixConfig, MixItem, MixLoader, draw_item, mix_batch  # noqa: F401
 from .model import Model  # noqa: F401
 from .optim import ClipAdam  # noqa: F401
 from .stream_pool import SessionBook, StreamPool  # noqa: F401

@@ -296,6 +296,12 @@ SIGNATURES = {
     "fsn_rows_to_bft": (_c.c_int, [_f32p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_void_p]),
     "fsn_improved_mask_apply": (_c.c_int, [_c.c_int, _c.c_void_p, _f32p, _f32p, _c.c_int, _c.c_int, _c.c_int, _f32p, _f32p,
                                            _c.c_void_p]),
+    "fsn_conv_rows_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "fsn_conv_rows": (_c.c_int, [_f32p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _f32p,
+                                 _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_mix_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "fsn_mix_pairs": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                 _c.c_int, _c.c_int, _c.c_float, _f32p, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "fsn_profile_num_stages": (_c.c_int, []),
     "fsn_profile_stage_name": (_c.c_char_p, [_c.c_int]),
     "fsn_profile_read": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_float), _c.c_int]),

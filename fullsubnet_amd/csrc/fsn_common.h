@@ -383,6 +383,16 @@ int fsn_launch_pool_synthesis(void* state, const FsnPoolLayout& L, int capacity,
                               int k, const int* first_frame, const int* tail_samples, const float* window, float* wframes,
                               float* out, hipStream_t s);
 
+// mix_kernels.hip (fsn_conv_rows / fsn_mix_pairs).  Z: B rows of 2^logN fp64 complex points, or NULL when the workspace
+// holds no transform (rows with a response then come back as NaN, the others are copied); live: B ints of scratch
+// h_off / h_len: row b's offset (long) and length (int) at byte b * stride of each (arrays, or fields of the item table)
+int fsn_launch_conv_rows(const float* x, int B, int L, const void* h_slab, int fmt, const void* h_off, int off_stride,
+                         const void* h_len, int len_stride, float* y, void* Z, int* live, int logN, hipStream_t s);
+int fsn_launch_mix_gather(const void* clean_slab, const void* noise_slab, int fmt, const fsn_mix_item* items,
+                          const fsn_mix_seg* segs, int n_segs, int B, int L, float* c0, float* nz, hipStream_t s);
+int fsn_launch_mix_level(const float* c, const float* nz, const fsn_mix_item* items, int B, int L, float eps, float* noisy,
+                         float* clean, hipStream_t s);
+
 // dft_kernels.hip (any even n_fft / any hop: direct fp64 DFT; reference layout [B][F][T] only).  lengths (device, [B], may
 // be NULL): per-row sample counts of a ragged batch; L / length is then the row stride and the longest row, T its frames
 int fsn_launch_dft_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag, int T,

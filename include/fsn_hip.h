@@ -869,6 +869,59 @@ int fsn_debug_core_call_plan(const fsn_fullsubnet_cfg* cfg, int B, int T, long r
  * lstm_step, lstm_step_cu, lstm_wavefront2, lstm2_group, fb_chain, then the model core's sub-band GEMM sites: layer-0
  * projection of rows that run step by step, layer-1 projection, output layer as a GEMM. */
 unsigned fsn_debug_core_last_launches(void);
+/* ---- training pairs mixed on the device : recipes/dns_interspeech_2020/dataset_train.py ---------------------------
+ * The arithmetic of Dataset.snr_mix (dataset_train.py:137-195, with norm_amplitude / tailor_dB_FS / is_clipped of
+ * audio_zen/acoustics/feature.py:99-114) as deterministic functions of host-drawn descriptors: every random draw stays
+ * with the caller (fullsubnet_amd/mix.py).  The source audio lives in three device slabs - clean speech, noise, room
+ * impulse responses - of fp32 samples (slab_format FSN_SLAB_F32) or 16-bit PCM read as v / 32768 (FSN_SLAB_I16, what a
+ * 16-bit wav loads as); offsets and lengths count samples.  `items`, `segs`, `h_off` and `h_len` are DEVICE pointers;
+ * the calls copy nothing, never synchronise and can be captured in a graph.  1 <= L <= FSN_MIX_MAX_L.
+ *
+ * Convolution: y[b, n] = sum_k h_b[k] x[b, n - k] for 0 <= n < L, i.e. fftconvolve(x_b, h_b)[:L]; taps from L on cannot
+ * reach those outputs and are never read; h_len[b] <= 0 copies the row.  y must not alias x.  It is an FFT convolution
+ * of circular length N = 2^k >= L + min(h, L) - 1 in fp64 (DESIGN "mixing on the device").  The host cannot see h_len, so
+ * N follows from the WORKSPACE: the largest transform workspace_bytes pays for, at most the one of max_h_len = L; the
+ * size query is what states the longest response.  A row whose response is longer than that transform carries
+ * (workspace sized for a smaller max_h_len) is written as NaN - never a silently aliased result.
+ *
+ * fsn_mix_pairs, per row: the clean row is clean_slab[clean_off, clean_off + clean_len) zero-padded to L
+ * (feature.py:subsample); the noise row is silence except where a segment copies noise_slab[src_off, src_off + len) to
+ * [dst_off, dst_off + len) (the files and 0.2 s silences of _select_noise_y after its crop); then
+ *   1. the clean row is convolved with the response (rir_len > 0);
+ *   2. c / (max|c| + eps) levelled to target_dbfs, the same for the noise;
+ *   3. noise gain clean_rms / 10^(snr / 20) / (noise_rms + eps), noisy = clean + gain * noise;
+ *   4. noisy levelled to noisy_target_dbfs, clean scaled by the same factor;
+ *   5. if any |noisy| > 0.999, both divided by max|noisy| / (0.99 - eps).
+ * Sums and scalars are fp64; noisy / clean [B][L] are rounded to fp32 once.  Rows do not depend on one another: a
+ * descriptor gives the same bits in any row of any batch.  Descriptor fields the host cannot see are clamped on the
+ * device so that nothing is WRITTEN outside the outputs and the workspace (clean_len to [0, L], segments to the row);
+ * the offsets into the slabs are the caller's responsibility.
+ * Refused without a launch (size queries return 0, fsn_last_error has the reason): L outside the range, B < 1, negative
+ * lengths, a NULL or misaligned (256 bytes) or short workspace. */
+#define FSN_SLAB_F32 0
+#define FSN_SLAB_I16 1
+#define FSN_MIX_MAX_L 131072
+typedef struct fsn_mix_seg {
+    long src_off; /* first sample in the noise slab */
+    int dst_off;  /* first sample of the row it lands on */
+    int len;
+} fsn_mix_seg;
+typedef struct fsn_mix_item {
+    long clean_off;
+    int clean_len;            /* <= L */
+    int seg_begin, seg_count; /* this row's slice of the segment table */
+    long rir_off;
+    int rir_len;              /* 0: no reverb */
+    float snr_db, target_dbfs, noisy_target_dbfs;
+} fsn_mix_item;
+size_t fsn_conv_rows_workspace_bytes(int B, int L, int max_h_len);
+int fsn_conv_rows(const float* x, int B, int L, const void* h_slab, int slab_format, const long* h_off, const int* h_len,
+                  float* y, void* workspace, size_t workspace_bytes, void* stream);
+size_t fsn_mix_workspace_bytes(int B, int L, int max_rir_len);
+int fsn_mix_pairs(const void* clean_slab, const void* noise_slab, const void* rir_slab, int slab_format,
+                  const fsn_mix_item* items, const fsn_mix_seg* segs, int n_segs, int B, int L, float eps, float* noisy,
+                  float* clean, void* workspace, size_t workspace_bytes, void* stream);
+
 int fsn_profile_num_stages(void);
 const char* fsn_profile_stage_name(int stage);
 int fsn_profile_read(void* stream, float* ms_per_stage, int n);
