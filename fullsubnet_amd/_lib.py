@@ -302,10 +302,16 @@ SIGNATURES = {
     "fsn_mix_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
     "fsn_mix_pairs": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
                                  _c.c_int, _c.c_int, _c.c_float, _f32p, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_stoi_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "fsn_stoi": (_c.c_int, [_f32p, _f32p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                            _c.c_void_p]),
+    "fsn_si_sdr": (_c.c_int, [_f32p, _f32p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "fsn_profile_num_stages": (_c.c_int, []),
     "fsn_profile_stage_name": (_c.c_char_p, [_c.c_int]),
     "fsn_profile_read": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_float), _c.c_int]),
 }
+# Entries added to revision 118 without a new number: a library built from an older tree of the same revision lacks them
+ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr")
 
 
 def lib():
@@ -321,6 +327,10 @@ def lib():
         built = handle.fsn_version()
         if built != ABI_VERSION:  # argument lists differ between revisions: a stale library would misread them silently
             raise FsnError(f"{LIB_PATH} was built for ABI revision {built}, this package binds revision {ABI_VERSION}: "
+                           "rebuild it with `python -m fullsubnet_amd.build`")
+        missing = [name for name in ADDED_IN_118 if not hasattr(handle, name)]
+        if missing:
+            raise FsnError(f"{LIB_PATH} has no {', '.join(missing)}: it was built before the metric entries were added; "
                            "rebuild it with `python -m fullsubnet_amd.build`")
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(handle, name)  # AttributeError if the ABI drifted from include/fsn_hip.h

@@ -393,6 +393,41 @@ int fsn_launch_mix_gather(const void* clean_slab, const void* noise_slab, int fm
 int fsn_launch_mix_level(const float* c, const float* nz, const fsn_mix_item* items, int B, int L, float eps, float* noisy,
                          float* clean, hipStream_t s);
 
+// stoi_kernels.hip (fsn_stoi / fsn_si_sdr).  The plan is host arithmetic on (B, L_max, sr) alone (fsn_api_metrics.hip);
+// every per-row count follows on the device from the row's own length.
+struct FsnStoiPlan {
+    int B, L_max;
+    int up, down, half;  // resampling ratio and half-length of its filter (2 half + 1 taps); half = 0: the rate is 10 kHz
+    int n10_max;         // samples of the longest row at 10 kHz
+    int nf_max;          // its 256-sample frames at hop 128 (the last full one not taken)
+    int m_max;           // spectral frames when nothing is removed: nf_max - 1
+    int j_blocks;        // workgroups of the correlation kernel per (row, band)
+};
+struct FsnStoiBuffers {
+    double* taps;     // [2 half + 1]
+    double* rs;       // [B][2][n10_max] clean, estimate at 10 kHz
+    double* energy;   // [B][nf_max] frame energies of the clean row in dB
+    int* kept;        // [B][nf_max] indices of the frames that stay, in order
+    int* n_kept;      // [B]
+    double* tob;      // [B][2][15][m_max] one-third-octave band magnitudes
+    double* partial;  // [B][15][j_blocks] per-workgroup sums of the correlations
+};
+// a row's samples (lengths[b] clamped into [0, L_max]; NULL: L_max), its samples at 10 kHz (ceil(n up / down)) and its
+// frames of 256 at hop 128 whose start is < n10 - 256 (the last full frame is not taken)
+__device__ __forceinline__ int fsn_stoi_row_samples(const int* lengths, int b, int L_max) {
+    if (!lengths) return L_max;
+    const int l = lengths[b];
+    return l < 0 ? 0 : (l > L_max ? L_max : l);
+}
+__host__ __device__ inline int fsn_stoi_n10(int n, int up, int down, int half) {
+    return half ? (int)(((long)n * up + down - 1) / down) : n;
+}
+__host__ __device__ inline int fsn_stoi_frames(int n10) { return n10 > 256 ? (n10 - 256 + 127) / 128 : 0; }
+int fsn_launch_stoi(const float* clean, const float* estimate, const int* lengths, const FsnStoiPlan& p,
+                    const FsnStoiBuffers& w, double* d, hipStream_t s);
+int fsn_launch_si_sdr(const float* reference, const float* estimate, const int* lengths, int B, int L_max, double* out_db,
+                      hipStream_t s);
+
 // dft_kernels.hip (any even n_fft / any hop: direct fp64 DFT; reference layout [B][F][T] only).  lengths (device, [B], may
 // be NULL): per-row sample counts of a ragged batch; L / length is then the row stride and the longest row, T its frames
 int fsn_launch_dft_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag, int T,

@@ -22,61 +22,16 @@
 
 namespace {
 
-struct cd {
-    double x, y;
-};
-__device__ __forceinline__ cd cadd(cd a, cd b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ cd csub(cd a, cd b) { return {a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ cd cmul(cd a, cd b) { return {fma(a.x, b.x, -(a.y * b.y)), fma(a.x, b.y, a.y * b.x)}; }
+#include "fft64_lds.h"  // cd, cadd / csub / cmul, bitrev, fill_twiddles, lds_fft
 
 __device__ __forceinline__ float slab_sample(const void* slab, int fmt, long i) {
     return fmt == FSN_SLAB_I16 ? (float)static_cast<const short*>(slab)[i] * (1.0f / 32768.0f)
                                : static_cast<const float*>(slab)[i];
 }
 
-__device__ __forceinline__ int bitrev(int v, int bits) { return bits == 0 ? 0 : (int)(__brev((unsigned)v) >> (32 - bits)); }
-
-constexpr int kThreads = 256;
+constexpr int kThreads = kFftThreads;
 constexpr int kMaxSub = 512;  // longest sub-transform: N <= 2^18 = 512 x 512
 constexpr int kCols = 4;      // columns of the N1 x N2 matrix per workgroup of the column kernels
-
-// tw[j] = e^(-2 pi i j / M), j < M / 2
-__device__ __forceinline__ void fill_twiddles(cd* tw, int M) {
-    for (int j = threadIdx.x; j < (M >> 1); j += kThreads) {
-        double s, c;
-        sincospi(-2.0 * (double)j / (double)M, &s, &c);
-        tw[j] = cd{c, s};
-    }
-}
-
-// `rows` transforms of M = 2^logM points each, a[r * M + i], in place, by the whole workgroup.  Forward: decimation in
-// frequency, natural order in, bit-reversed out.  Inverse (unscaled): decimation in time, bit-reversed in, natural out.
-// Ends with a barrier; the caller has one between its fill of `a` / `tw` and the call.
-template <bool INV>
-__device__ __forceinline__ void lds_fft(cd* a, const cd* tw, int M, int logM, int rows) {
-    const int half = M >> 1, total = rows * half;
-    for (int st = 0; st < logM; ++st) {
-        const int lh = INV ? st : logM - 1 - st;  // log2 of the butterfly span h
-        const int h = 1 << lh;
-        for (int j = threadIdx.x; j < total; j += kThreads) {
-            const int r = j / half, jj = j - r * half;
-            const int pos = jj & (h - 1);
-            const int i0 = r * M + ((jj >> lh) << (lh + 1)) + pos, i1 = i0 + h;
-            cd w = tw[pos << (logM - 1 - lh)];  // W_2h^pos
-            const cd u = a[i0], v = a[i1];
-            if (INV) {
-                w.y = -w.y;
-                const cd t = cmul(v, w);
-                a[i0] = cadd(u, t);
-                a[i1] = csub(u, t);
-            } else {
-                a[i0] = cadd(u, v);
-                a[i1] = cmul(csub(u, v), w);
-            }
-        }
-        __syncthreads();
-    }
-}
 
 // e^(-+ 2 pi i m / N) for 0 <= m < N (forward: minus)
 template <bool INV>

@@ -25,7 +25,15 @@ import.  With both present the returned score is the reference's (STOI + transfo
 "With_reverb" set (base_trainer.py:362-369, fullsubnet/trainer.py:181); otherwise it is the mean SI_SDR of the
 enhanced validation utterances (higher is better as well) and ``self.validation_score_kind`` says so.
 TensorBoard and the spectrogram plots of the reference are host-side tooling and not reproduced; the scalars
-they would receive are kept in ``self.history``."""
+they would receive are kept in ``self.history``.
+
+``[trainer.validation] device_metrics = true`` (opt-in) scores on the device instead: noisy / clean / enhanced stay
+there, each speech type is padded into one ragged batch and scored by one ``fsn_stoi`` and one ``fsn_si_sdr`` call for
+the noisy and one for the enhanced signals (fullsubnet_amd/metrics.py; the reference's Noisy / Enhanced scalars, kept in
+``self.history["Metrics"]``).  The returned score is then the mean device STOI of the enhanced "With_reverb" set
+(``validation_score_kind = "STOI (device)"``), or (STOI + transformed WB_PESQ) / 2 with the host WB_PESQ when a ``pesq``
+package imports.  The device STOI follows the published method and is held to an fp64 numpy reference; equality with
+pystoi is not demonstrated."""
 from pathlib import Path
 
 import numpy as np
@@ -33,7 +41,8 @@ import torch
 
 from .acoustics.feature import istft, stft
 from .acoustics.mask import build_complex_ideal_ratio_mask, decompress_cIRM
-from . import _lib
+from . import _lib, metrics as fsn_metrics
+from .ragged import pad_utterances
 from .train import mse_loss, train_step
 
 
@@ -129,6 +138,7 @@ class Trainer:
         assert self.validation_interval >= 1, \
             "Check the 'validation_interval' parameter in the config. It should be large than one."
         self.visualization_config = tc.get("visualization", {})
+        self.device_metrics = bool(self.validation_config.get("device_metrics", False))
 
         self.start_epoch = 1
         self.best_score = -np.inf if self.save_max_metric_score else np.inf
@@ -141,6 +151,8 @@ class Trainer:
         self.validation_score_kind = None
         self.history = {"Loss/Train": {}, "Loss/Validation_Total": {}, "Loss/With_reverb": {}, "Loss/No_reverb": {},
                         "Score": {}}
+        if self.device_metrics:
+            self.history["Metrics"] = {}
         self.last_loss = None
         self.persistent_timeouts = 0  # training steps in which a persistent kernel ran out of time (update skipped)
         self.nonfinite_losses = 0     # training steps whose loss was not finite (update skipped on the device)
@@ -298,9 +310,12 @@ class Trainer:
             enhanced_real = m[..., 0] * noisy_real - m[..., 1] * noisy_imag
             enhanced_imag = m[..., 1] * noisy_real + m[..., 0] * noisy_imag
             enhanced = self.torch_istft((enhanced_real, enhanced_imag), length=noisy.size(-1), input_type="real_imag")
-            noisy_np = noisy.detach().squeeze(0).cpu().numpy()
-            clean_np = clean.detach().squeeze(0).cpu().numpy()
-            enhanced_np = enhanced.detach().squeeze(0).cpu().numpy()
+            if self.device_metrics:  # scored after the loop, one ragged batch per speech type; nothing is copied back
+                noisy_np, clean_np, enhanced_np = (t.detach().squeeze(0) for t in (noisy, clean, enhanced))
+            else:
+                noisy_np = noisy.detach().squeeze(0).cpu().numpy()
+                clean_np = clean.detach().squeeze(0).cpu().numpy()
+                enhanced_np = enhanced.detach().squeeze(0).cpu().numpy()
             assert len(noisy_np) == len(clean_np) == len(enhanced_np)
             loss_total += loss
             loss_list[speech_type] += loss
@@ -313,7 +328,11 @@ class Trainer:
         scores = {}
         for k in kinds:
             self.history[f"Loss/{k}"][epoch] = loss_list[k] / n_items  # the reference divides by the loader length
-            scores[k] = self.metrics_score(lists[k]["noisy"], lists[k]["clean"], lists[k]["enhanced"])
+            if self.device_metrics:
+                scores[k], per_metric = self.device_metrics_score(lists[k]["noisy"], lists[k]["clean"], lists[k]["enhanced"])
+                self.history["Metrics"].setdefault(epoch, {})[k] = per_metric
+            else:
+                scores[k] = self.metrics_score(lists[k]["noisy"], lists[k]["clean"], lists[k]["enhanced"])
         self.history["Score"][epoch] = scores
         self.last_validation = lists
         return float(scores["With_reverb"])
@@ -331,6 +350,30 @@ class Trainer:
             return float((stoi + transform_pesq_range(pesq)) / 2)
         self.validation_score_kind = "SI_SDR"
         return float(np.mean([self.metrics["SI_SDR"](r, e) for r, e in zip(clean_list, enhanced_list)]))
+
+    def device_metrics_score(self, noisy_list, clean_list, enhanced_list):
+        """base_trainer.py:319-369 on the device: the utterances (1-D device tensors) of one speech type as one ragged
+        batch, STOI and SI_SDR of the noisy and of the enhanced signals against the clean ones in one call each.  Returns
+        (score, {"STOI": {"Noisy": mean, "Enhanced": mean}, "SI_SDR": {..}}); the score is the enhanced mean STOI, or
+        (STOI + transform(WB_PESQ)) / 2 with the host WB_PESQ when that metric is registered."""
+        if not enhanced_list:
+            return 0.0, {}
+        sr = self.acoustic_config.get("sr", 16000)
+        clean, lengths = pad_utterances(clean_list, self.device)
+        per_metric = {"STOI": {}, "SI_SDR": {}}
+        for tag, signals in (("Noisy", noisy_list), ("Enhanced", enhanced_list)):
+            batch, _ = pad_utterances(signals, self.device)
+            per_metric["STOI"][tag] = float(fsn_metrics.stoi(clean, batch, sr, lengths).mean())
+            per_metric["SI_SDR"][tag] = float(fsn_metrics.si_sdr(clean, batch, lengths).mean())
+        stoi = per_metric["STOI"]["Enhanced"]
+        if "WB_PESQ" in self.metrics:
+            self.validation_score_kind = "(STOI (device) + WB_PESQ) / 2"
+            pesq = np.mean([self.metrics["WB_PESQ"](r.cpu().numpy(), e.cpu().numpy(), sr)
+                            for r, e in zip(clean_list, enhanced_list)])
+            per_metric["WB_PESQ"] = {"Enhanced": float(pesq)}
+            return float((stoi + transform_pesq_range(pesq)) / 2), per_metric
+        self.validation_score_kind = "STOI (device)"
+        return stoi, per_metric
 
     def train(self):
         """base_trainer.py:372-420."""

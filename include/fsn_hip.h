@@ -922,6 +922,32 @@ int fsn_mix_pairs(const void* clean_slab, const void* noise_slab, const void* ri
                   const fsn_mix_item* items, const fsn_mix_seg* segs, int n_segs, int B, int L, float eps, float* noisy,
                   float* clean, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- validation metrics on the device : audio_zen/metrics.py (STOI, SI_SDR) ------------------------------------------
+ * Row b of clean / reference and of estimate [B][L_max] (fp32) holds lengths[b] samples (device pointer; a value is
+ * clamped into [0, L_max]; NULL: every row holds L_max); nothing past a row's length is read.  All arithmetic is fp64,
+ * every sum runs in a fixed order and no row's result depends on the rows around it: a pair gives the same bits alone
+ * and in any batch.  The calls copy nothing, never synchronise, can be captured in a graph and use no library state
+ * beyond the per-stream record of every entry.  Added without a new FSN_ABI_VERSION (additive; a binding looks the
+ * three symbols up by name).
+ *
+ * fsn_stoi: the short-time objective intelligibility of Taal, Hendriks, Heusdens and Jensen (2011), not extended, as
+ * DESIGN "metrics on the device" pins it constant by constant: polyphase resampling to 10 kHz (sr = 10000: none,
+ * 16000: 5 / 8, 48000: 5 / 24, Kaiser-windowed sinc formed on the device), removal of the 256-sample frames (hop 128)
+ * of the CLEAN row more than 40 dB below its loudest, 512-point spectra, 15 one-third-octave bands from 150 Hz,
+ * clipped and normalised correlations over every 30 consecutive frames.  d [B] (device, fp64):
+ *   - a row that is left with fewer than 30 spectral frames: 1e-5 exactly;
+ *   - an all-zero clean row or an all-zero estimate row (of 30 frames or more): 0, never NaN (the "+ eps" terms).
+ * fsn_si_sdr: out_db[b] = 10 log10(|a r|^2 / |e - a r|^2), a = <r, e> / <r, r>, the residual summed in a second
+ * pass (the expanded form cancels at high SDR).  An all-zero or empty reference row gives NaN, estimate == a r gives +inf,
+ * as the formula does.
+ * Refused with FSN_ERR_ARG, a message and no launch (the size query returns 0): an sr other than the three, B < 1,
+ * L_max < 1, a NULL pointer, a NULL, misaligned (256 bytes) or short workspace. */
+size_t fsn_stoi_workspace_bytes(int B, int L_max, int sr);
+int fsn_stoi(const float* clean, const float* estimate, const int* lengths, int B, int L_max, int sr, double* d,
+             void* workspace, size_t workspace_bytes, void* stream);
+int fsn_si_sdr(const float* reference, const float* estimate, const int* lengths, int B, int L_max, double* out_db,
+               void* stream);
+
 int fsn_profile_num_stages(void);
 const char* fsn_profile_stage_name(int stage);
 int fsn_profile_read(void* stream, float* ms_per_stage, int n);
