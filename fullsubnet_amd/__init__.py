@@ -3,7 +3,7 @@
 Host-side mirror of the reference's plugin surface (audio_zen ``Model.forward`` / ``Inferencer`` /
 ``stft`` / ``istft`` / cIRM helpers) over the C ABI of ``libfsn_hip.so`` (include/fsn_hip.h).
 """
-from . import _lib, metrics  # noqa: F401
+from . import _lib, metrics, resample  # noqa: F401
 from .acoustics.feature import drop_band, istft, mag_phase, stft  # noqa: F401
 from .acoustics.mask import (build_complex_ideal_ratio_mask, complex_mul, compress_cIRM,  # noqa: F401
                              decompress_cIRM)

@@ -306,12 +306,20 @@ SIGNATURES = {
     "fsn_stoi": (_c.c_int, [_f32p, _f32p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t,
                             _c.c_void_p]),
     "fsn_si_sdr": (_c.c_int, [_f32p, _f32p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "fsn_resample_out_length": (_c.c_long, [_c.c_long, _c.c_int, _c.c_int]),
+    "fsn_resample_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_double]),
+    "fsn_resample_taps": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_double, _c.c_void_p, _c.c_size_t,
+                                     _c.c_void_p]),
+    "fsn_resample": (_c.c_int, [_f32p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_double,
+                                _c.c_double, _f32p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_debug_resample_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int]),
     "fsn_profile_num_stages": (_c.c_int, []),
     "fsn_profile_stage_name": (_c.c_char_p, [_c.c_int]),
     "fsn_profile_read": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_float), _c.c_int]),
 }
 # Entries added to revision 118 without a new number: a library built from an older tree of the same revision lacks them
-ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr")
+ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr", "fsn_resample_out_length",
+                "fsn_resample_workspace_bytes", "fsn_resample_taps", "fsn_resample", "fsn_debug_resample_plan")
 
 
 def lib():
@@ -330,7 +338,7 @@ def lib():
                            "rebuild it with `python -m fullsubnet_amd.build`")
         missing = [name for name in ADDED_IN_118 if not hasattr(handle, name)]
         if missing:
-            raise FsnError(f"{LIB_PATH} has no {', '.join(missing)}: it was built before the metric entries were added; "
+            raise FsnError(f"{LIB_PATH} has no {', '.join(missing)}: it was built before these entries were added; "
                            "rebuild it with `python -m fullsubnet_amd.build`")
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(handle, name)  # AttributeError if the ABI drifted from include/fsn_hip.h

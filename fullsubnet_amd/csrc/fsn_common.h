@@ -428,6 +428,29 @@ int fsn_launch_stoi(const float* clean, const float* estimate, const int* length
 int fsn_launch_si_sdr(const float* reference, const float* estimate, const int* lengths, int B, int L_max, double* out_db,
                       hipStream_t s);
 
+// resample_kernels.hip (fsn_resample / fsn_resample_taps).  The plan is host arithmetic on the rates and the design
+// (fsn_api_resample.hip); a row's output length follows on the device from the row's own length.
+constexpr int kFsnResampleThreads = 512;
+constexpr int kFsnResampleOutPerThread = 8;       // outputs of one phase per thread: one tap load per eight multiply-adds
+constexpr int kFsnResampleMaxStretch = 24576;     // input samples a workgroup stages (fp32: 96 KB)
+constexpr size_t kFsnResampleLdsBytes = 160 * 1024;  // what a workgroup of gfx950 may hold
+struct FsnResamplePlan {
+    int u, d;         // sr_out / g, sr_in / g
+    int H, taps;      // half length zeros * max(u, d), 2 H + 1
+    int J, Js;        // taps of the longest phase ceil(taps / u); row stride of the polyphase table (J made odd)
+    int S;            // outputs of one pass of a workgroup (its threads take them 512 at a time): a multiple of u, so that
+                      // k and k + S share their phase
+    int tile;         // outputs of a workgroup: kFsnResampleOutPerThread * S
+    int stretch;      // input samples a workgroup stages at most: (tile - 1) d / u + J + 1
+    int taps_in_lds;  // the whole polyphase table sits in LDS beside the stretch
+    double beta, rolloff;
+};
+__host__ __device__ inline long fsn_resample_n_out(long n, int u, int d) { return (n * u + d - 1) / d; }
+// h [taps]: the filter in natural order; poly [u][Js] (may be NULL): the same in polyphase order, zero-padded rows
+int fsn_launch_resample_taps(const FsnResamplePlan& p, double* h, double* poly, hipStream_t s);
+int fsn_launch_resample(const float* x, const int* lengths, int B, int L_max, const FsnResamplePlan& p, const double* poly,
+                        float* y, int L_out_max, int* out_lengths, hipStream_t s);
+
 // dft_kernels.hip (any even n_fft / any hop: direct fp64 DFT; reference layout [B][F][T] only).  lengths (device, [B], may
 // be NULL): per-row sample counts of a ragged batch; L / length is then the row stride and the longest row, T its frames
 int fsn_launch_dft_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag, int T,

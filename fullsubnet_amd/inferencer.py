@@ -58,6 +58,8 @@ class Inferencer:
             self.segment_frames = int(self.segment_frames)
             if not 1 <= self.segment_frames <= 4096:
                 raise ValueError(f"[inferencer] segment_frames must be in [1, 4096], got {self.segment_frames}")
+        # [inferencer] input_sr / output_sr / resample_design (optional): loader items at another rate than the model's
+        self.input_sr, self.output_sr, self.resample_design = self.resample_keys(self.inference_config)
 
         epoch = 0
         if model is None:
@@ -122,12 +124,64 @@ class Inferencer:
         ``lengths[b]`` samples (``Model.enhance``; libfsn_hip ``fsn_enhance_ragged``)."""
         return self.model.enhance(noisy.to(self.device), n_fft=self.n_fft, hop_length=self.hop_length, lengths=lengths)
 
+    @staticmethod
+    def resample_keys(inference_config):
+        """``(input_sr, output_sr, design)`` of ``[inferencer]``: ``input_sr`` the rate of the loader's items (None: the
+        model's), ``output_sr`` what is written - "model" (default), "input" or a rate -, ``resample_design`` one of
+        ``resample.DESIGNS`` (default "scipy").  Raises ``ValueError`` on anything else."""
+        input_sr = inference_config.get("input_sr")
+        if input_sr is not None:
+            if isinstance(input_sr, bool) or not isinstance(input_sr, int) or input_sr < 1:
+                raise ValueError(f"[inferencer] input_sr must be a positive integer, got {input_sr!r}")
+        output_sr = inference_config.get("output_sr", "model")
+        if output_sr not in ("model", "input"):
+            if isinstance(output_sr, bool) or not isinstance(output_sr, int) or output_sr < 1:
+                raise ValueError(f'[inferencer] output_sr must be "model", "input" or a positive integer, got {output_sr!r}')
+        design = inference_config.get("resample_design", "scipy")
+        if design not in ("scipy", "sharp"):
+            raise ValueError(f'[inferencer] resample_design must be "scipy" or "sharp", got {design!r}')
+        return input_sr, output_sr, design
+
+    def _rates(self, sr, output_sr):
+        """The rate of the input and the rate to return (``output_sr``: None / "model", "input" or a number)."""
+        sr_in = self.sr if sr is None else int(sr)
+        if output_sr is None or output_sr == "model":
+            return sr_in, self.sr
+        return sr_in, sr_in if output_sr == "input" else int(output_sr)
+
     @torch.no_grad()
-    def enhance_utterances(self, utterances):
+    def enhance_utterances(self, utterances, sr=None, output_sr=None, design="scipy"):
         """1-D utterances of any lengths -> their enhanced 1-D waveforms (device), in ONE ragged call: padded to the
-        longest, enhanced with their lengths, cut back."""
+        longest, enhanced with their lengths, cut back.
+
+        ``sr``: the rate of the utterances when it is not the model's (``[acoustics] sr``): they are resampled to the
+        model's rate on the device in one ragged call (``resample.resample``, filter ``design``), enhanced, and returned at
+        ``output_sr`` - the model's rate (default), ``"input"`` or a rate in Hz - cut to ``out_length`` of their original
+        lengths (``"input"``: exactly the original lengths)."""
+        sr_in, sr_out = self._rates(sr, output_sr)
+        if sr_in == self.sr and sr_out == self.sr:
+            noisy, lengths = pad_utterances(utterances, device=self.device)
+            return trim_rows(self.enhance_batch(noisy, lengths=lengths), lengths)
+        from . import resample as rs
         noisy, lengths = pad_utterances(utterances, device=self.device)
-        return trim_rows(self.enhance_batch(noisy, lengths=lengths), lengths)
+        if sr_in != self.sr:
+            noisy, _ = rs.resample(noisy, sr_in, self.sr, lengths=lengths, design=design)
+        enhanced = self._enhance_model_rate(trim_rows(noisy, [rs.out_length(n, sr_in, self.sr) for n in lengths]))
+        if sr_out == self.sr:
+            return enhanced
+        rows, row_lengths = pad_utterances(enhanced, device=self.device)
+        rows, _ = rs.resample(rows, self.sr, sr_out, lengths=row_lengths, design=design)
+        return trim_rows(rows, [rs.out_length(n, sr_in, sr_out) for n in lengths])
+
+    def _enhance_model_rate(self, utterances):
+        """Utterances at the model's rate -> enhanced, as ``__call__`` runs a group: one ragged call where the model has one
+        and no item is past ``segment_frames``, otherwise one ``full_band_crm_mask`` each (``enhance_long`` for those)."""
+        items = [(u.unsqueeze(0), None) for u in utterances]
+        if self._ragged_ok(items):
+            noisy, lengths = pad_utterances(utterances, device=self.device)
+            return trim_rows(self.enhance_batch(noisy, lengths=lengths), lengths)
+        args = self.inference_config.get("args", {})
+        return [torch.as_tensor(self.full_band_crm_mask(n.to(self.device), args), device=self.device) for n, _ in items]
 
     def _ragged_ok(self, items):
         """Whether a group of loader items runs as one ragged call: 1-D utterances (one channel) on a model whose
@@ -153,9 +207,16 @@ class Inferencer:
         batch_size = int(self.inference_config.get("batch_size", 1))
         if batch_size < 1:
             raise ValueError(f"[inferencer] batch_size must be >= 1, got {batch_size}")
+        resampled = self.__dict__.get("input_sr") is not None or self.__dict__.get("output_sr", "model") != "model"
         group = []
         for noisy, name in self.dataloader:
             assert len(name) == 1, "The batch size of inference stage must 1."
+            if resampled:
+                group.append((noisy, name[0]))
+                if len(group) == batch_size:
+                    self._enhance_group_resampled(group)
+                    group = []
+                continue
             if batch_size == 1:
                 enhanced = getattr(self, inference_type)(noisy.to(self.device), inference_args)
                 self._write_item(name[0], noisy, enhanced)
@@ -165,7 +226,22 @@ class Inferencer:
                 self._enhance_group(group, inference_type, inference_args)
                 group = []
         if group:  # the last, partial group
-            self._enhance_group(group, inference_type, inference_args)
+            if resampled:
+                self._enhance_group_resampled(group)
+            else:
+                self._enhance_group(group, inference_type, inference_args)
+
+    def _enhance_group_resampled(self, items):
+        """Loader items at ``[inferencer] input_sr``: resampled, enhanced and resampled to ``output_sr`` on the device
+        (``enhance_utterances``); the enhanced file carries the output rate, the noisy file beside it the input's."""
+        for noisy, name in items:
+            if noisy.dim() != 2 or noisy.shape[0] != 1:
+                raise ValueError(f"[inferencer] input_sr / output_sr: item {name!r} of shape {tuple(noisy.shape)} is not one "
+                                 "single-channel utterance [1, L]")
+        sr_in, sr_out = self._rates(self.input_sr, self.output_sr)
+        outs = self.enhance_utterances([n[0] for n, _ in items], sr=sr_in, output_sr=sr_out, design=self.resample_design)
+        for (noisy, name), enhanced in zip(items, outs):
+            self._write_item(name, noisy, enhanced.detach().cpu().numpy(), enhanced_sr=sr_out, noisy_sr=sr_in)
 
     def _enhance_group(self, items, inference_type, inference_args):
         """Several loader items as ONE ragged call of the library where the model has one; otherwise one
@@ -178,13 +254,15 @@ class Inferencer:
         for (noisy, name), enhanced in zip(items, outs):
             self._write_item(name, noisy, enhanced)
 
-    def _write_item(self, name, noisy, enhanced):
+    def _write_item(self, name, noisy, enhanced, enhanced_sr=None, noisy_sr=None):
         """base_inferencer.py:178-195: the enhanced waveform peak-normalised to 0.8 of int16 full scale, the noisy
-        input beside it trimmed to the same length."""
+        input beside it trimmed to the same length (whole when the two files are at different rates)."""
+        enhanced_sr = self.sr if enhanced_sr is None else enhanced_sr
+        noisy_sr = self.sr if noisy_sr is None else noisy_sr
         amp = np.iinfo(np.int16).max
         enhanced = np.int16(0.8 * amp * enhanced / np.max(np.abs(enhanced)))
-        _write_wav(self.enhanced_dir / f"{name}.wav", enhanced, self.sr)
+        _write_wav(self.enhanced_dir / f"{name}.wav", enhanced, enhanced_sr)
         noisy = noisy.detach().squeeze(0).numpy()
         if np.ndim(noisy) > 1:
             noisy = noisy[0, :]
-        _write_wav(self.noisy_dir / f"{name}.wav", noisy[: enhanced.shape[-1]], self.sr)
+        _write_wav(self.noisy_dir / f"{name}.wav", noisy[: enhanced.shape[-1]] if noisy_sr == enhanced_sr else noisy, noisy_sr)

@@ -948,6 +948,43 @@ int fsn_stoi(const float* clean, const float* estimate, const int* lengths, int 
 int fsn_si_sdr(const float* reference, const float* estimate, const int* lengths, int B, int L_max, double* out_db,
                void* stream);
 
+/* ---- sample-rate conversion on the device : what the reference gets from librosa.load(path, sr=sr) ------------------
+ * A rational-ratio polyphase FIR resampler, scipy.signal.resample_poly's construction with three design parameters
+ * (DESIGN "resampling on the device" pins it).  For a row x of n fp32 samples, sr_in -> sr_out and (zeros, beta, rolloff):
+ *   u = sr_out / g, d = sr_in / g, g = gcd;  P = max(u, d), H = zeros P, fc = rolloff / P;
+ *   g[t] = kaiser(2H + 1, beta)[t] fc sinc(fc t) for t = -H .. H,  h = u g / sum(g)               (fp64)
+ *   n_out = ceil(n u / d),  y[k] = fp32(sum_m h[k d + H - m u] x[m]) over the m in [0, n) whose tap exists  (fp64 sums)
+ * Nothing outside the row is read: no reflection, no carried state.  u == d == 1 copies the row bit for bit.
+ * (zeros, beta, rolloff) = (10, 5.0, 1.0) is resample_poly(x, u, d) with its default window; (32, 12.0, 0.92) is a
+ * steeper anti-alias filter (-43 dB at the new Nyquist rate, below -120 dB past 9 / 8 of it, for 3 : 1).
+ *
+ * Row b of x [B][L_max] holds lengths[b] samples (device pointer; a value is clamped into [0, L_max]; NULL: every row
+ * holds L_max); nothing past a row's length is read.  y [B][L_out_max]: row b receives its n_out samples and zeros from
+ * there to L_out_max; out_lengths (device, [B], may be NULL) receives n_out.  The taps are formed on the device by the
+ * call itself (workspace), so a call copies nothing, never synchronises and can be captured in a graph; the order of an
+ * output's sum depends on (u, d, design, k) alone, so a row has the same bits alone and in any batch; an all-zero row
+ * gives exact zeros.  Additive entries (no new FSN_ABI_VERSION; a binding looks them up by name).
+ *
+ * fsn_resample_out_length: ceil(n u / d) on the host, no device call; -1 for rates < 1 or n < 0.
+ * fsn_resample_taps: h in natural order, h[t + H], as fp64 into device memory of h_count >= 2H + 1 doubles.
+ * fsn_debug_resample_plan (test hook): out[0 .. n) = u, d, H, taps, taps per phase, row stride of the polyphase table,
+ * outputs per workgroup, the longest row one workgroup covers, input samples a workgroup stages, table in LDS (0 / 1).
+ * Refused with FSN_ERR_ARG, a message and no launch (the size query returns 0): a rate < 1, zeros < 1, beta outside
+ * [0, FSN_RESAMPLE_MAX_BETA], rolloff outside (0, 1], max(u, d) > FSN_RESAMPLE_MAX_P, 2H + 1 > FSN_RESAMPLE_MAX_TAPS, a ratio and filter whose
+ * smallest workgroup tile (8 u outputs) lies over more than 24576 input samples, B outside [1, 65535], L_max < 1,
+ * L_out_max smaller than ceil(L_max u / d), y == x, a NULL pointer, a NULL, misaligned (256 bytes) or short workspace. */
+#define FSN_RESAMPLE_MAX_P 4096
+#define FSN_RESAMPLE_MAX_TAPS 262145
+#define FSN_RESAMPLE_MAX_BETA 256
+long fsn_resample_out_length(long n, int sr_in, int sr_out);
+size_t fsn_resample_workspace_bytes(int sr_in, int sr_out, int zeros, double beta, double rolloff);
+int fsn_resample_taps(int sr_in, int sr_out, int zeros, double beta, double rolloff, double* h, size_t h_count,
+                      void* stream);
+int fsn_resample(const float* x, const int* lengths, int B, int L_max, int sr_in, int sr_out, int zeros, double beta,
+                 double rolloff, float* y, int L_out_max, int* out_lengths, void* workspace, size_t workspace_bytes,
+                 void* stream);
+int fsn_debug_resample_plan(int sr_in, int sr_out, int zeros, int* out, int n);
+
 int fsn_profile_num_stages(void);
 const char* fsn_profile_stage_name(int stage);
 int fsn_profile_read(void* stream, float* ms_per_stage, int n);
