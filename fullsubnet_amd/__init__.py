@@ -14,6 +14,7 @@ from .mix import MixBank, MixConfig, MixItem, MixLoader, draw_item, mix_batch  #
 from .model import Model  # noqa: F401
 from .optim import ClipAdam  # noqa: F401
 from .stream_pool import SessionBook, StreamPool  # noqa: F401
+from .stream_resample import ResampleBook, StreamResampler  # noqa: F401
 from .streaming import StreamingEnhancer  # noqa: F401
 
 __version__ = "0.1.0"

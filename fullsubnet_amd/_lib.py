@@ -313,13 +313,23 @@ SIGNATURES = {
     "fsn_resample": (_c.c_int, [_f32p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_double,
                                 _c.c_double, _f32p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "fsn_debug_resample_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int]),
+    "fsn_resample_stream_ready": (_c.c_long, [_c.c_long, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "fsn_resample_stream_state_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "fsn_resample_stream_init": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_double,
+                                            _c.c_double, _c.c_void_p]),
+    "fsn_resample_stream_push": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                            _c.c_int, _f32p, _c.c_int, _f32p, _c.c_int, _c.c_void_p]),
+    "fsn_resample_stream_reset": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                             _c.c_int, _c.c_void_p]),
     "fsn_profile_num_stages": (_c.c_int, []),
     "fsn_profile_stage_name": (_c.c_char_p, [_c.c_int]),
     "fsn_profile_read": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_float), _c.c_int]),
 }
 # Entries added to revision 118 without a new number: a library built from an older tree of the same revision lacks them
 ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr", "fsn_resample_out_length",
-                "fsn_resample_workspace_bytes", "fsn_resample_taps", "fsn_resample", "fsn_debug_resample_plan")
+                "fsn_resample_workspace_bytes", "fsn_resample_taps", "fsn_resample", "fsn_debug_resample_plan",
+                "fsn_resample_stream_ready", "fsn_resample_stream_state_bytes", "fsn_resample_stream_init",
+                "fsn_resample_stream_push", "fsn_resample_stream_reset")
 
 
 def lib():

@@ -1,5 +1,6 @@
 // C ABI of the sample-rate conversion on the device: fsn_resample, its size and length queries, fsn_resample_taps
-// (include/fsn_hip.h "sample-rate conversion on the device"; kernels: resample_kernels.hip).
+// (include/fsn_hip.h "sample-rate conversion on the device"; kernels: resample_kernels.hip), and of its streaming form,
+// fsn_resample_stream_* ("sample-rate conversion of streams"; kernels: resample_stream_kernels.hip).
 #include <limits.h>
 #include <math.h>
 #include <stddef.h>
@@ -152,4 +153,141 @@ extern "C" int fsn_resample(const float* x, const int* lengths, int B, int L_max
     FsnCallScope scope(stream);
     if (p.u != 1 || p.d != 1) FSN_TRY(fsn_launch_resample_taps(p, w.h, w.poly, s));
     return fsn_launch_resample(x, lengths, B, L_max, p, w.poly, y, L_out_max, out_lengths, s);
+}
+
+// ---- streams (include/fsn_hip.h "sample-rate conversion of streams"; kernels: resample_stream_kernels.hip) -------------
+namespace {
+
+// The streaming plan of a ratio and a filter length: whatever fsn_resample refuses of them is refused here (beta and
+// rolloff shape the taps, not the plan: fsn_resample_stream_init checks them).
+bool stream_plan(const char* who, int sr_in, int sr_out, int zeros, FsnResamplePlan* offline, FsnResampleStreamPlan* p) {
+    if (!resample_plan(who, sr_in, sr_out, zeros, offline->beta, offline->rolloff, offline)) return false;
+    const bool copy = offline->u == 1 && offline->d == 1;
+    p->u = offline->u;
+    p->d = offline->d;
+    p->H = copy ? 0 : offline->H;
+    p->J = copy ? 1 : offline->J;
+    p->Js = copy ? 1 : offline->Js;
+    for (int tile = kFsnResampleStreamThreads;; tile /= 2) {
+        const long stretch = (long)(tile - 1) * p->d / p->u + p->J + 1;
+        if (stretch <= kFsnResampleStreamMaxStretch) {
+            p->tile = tile;
+            p->stretch = (int)stretch;
+            break;
+        }
+        if (tile == 1) {
+            fsn_set_error("%s: %d taps per phase at the ratio %d / %d: a workgroup stages at most %d input samples", who, p->J,
+                          p->u, p->d, kFsnResampleStreamMaxStretch);
+            return false;
+        }
+    }
+    // staging the table costs u Js loads; the tile reads tile J entries of it
+    const size_t table = (size_t)p->u * p->Js * sizeof(double);
+    p->taps_in_lds = !copy && table + (size_t)p->stretch * sizeof(float) <= kFsnResampleLdsBytes &&
+                             (long)p->u * p->Js <= (long)p->tile * p->J
+                         ? 1
+                         : 0;
+    p->slot_floats = fsn_round_up(2 * (p->J - 1) > 1 ? 2 * (p->J - 1) : 1, 64);
+    return true;
+}
+
+struct StreamBlob {
+    double* h;     // [taps] natural order (what resample_taps_kernel sums over)
+    double* poly;  // [u][Js]
+    float* slots;  // [capacity][slot_floats]
+};
+size_t stream_carve(const FsnResamplePlan& offline, const FsnResampleStreamPlan& p, int capacity, void* base, StreamBlob* b) {
+    Carver c(base);
+    b->h = c.take<double>((size_t)offline.taps);
+    b->poly = c.take<double>((size_t)offline.u * offline.Js);
+    b->slots = c.take<float>((size_t)capacity * p.slot_floats);
+    return fsn_round_up_sz(c.off, 256);
+}
+
+// the checks every call on a blob shares; beta / rolloff as given (init) or the defaults (they do not enter the layout)
+int stream_call(const char* who, void* state, size_t state_bytes, int capacity, int sr_in, int sr_out, int zeros, double beta,
+                double rolloff, FsnResamplePlan* offline, FsnResampleStreamPlan* p, StreamBlob* b) {
+    offline->beta = beta;
+    offline->rolloff = rolloff;
+    if (!stream_plan(who, sr_in, sr_out, zeros, offline, p)) return FSN_ERR_ARG;
+    FSN_REQUIRE(capacity >= 1 && capacity <= 65535, "%s: capacity = %d: 1 to 65535 sessions", who, capacity);
+    FSN_REQUIRE(state, "%s: NULL state", who);
+    FSN_REQUIRE((reinterpret_cast<uintptr_t>(state) & 255) == 0, "%s: the state must be 256-byte aligned", who);
+    const size_t want = stream_carve(*offline, *p, capacity, state, b);
+    FSN_REQUIRE(state_bytes == want, "%s: a state of %zu bytes, %d sessions at %d -> %d Hz with zeros = %d have %zu", who,
+                state_bytes, capacity, sr_in, sr_out, zeros, want);
+    return FSN_OK;
+}
+
+}  // namespace
+
+extern "C" long fsn_resample_stream_ready(long n_in, int final, int sr_in, int sr_out, int zeros) {
+    FsnResamplePlan offline;
+    FsnResampleStreamPlan p;
+    offline.beta = 5.0;
+    offline.rolloff = 1.0;
+    if (!stream_plan("fsn_resample_stream_ready", sr_in, sr_out, zeros, &offline, &p)) return -1;
+    if (n_in < 0) {
+        fsn_set_error("fsn_resample_stream_ready: n_in = %ld", n_in);
+        return -1;
+    }
+    if (final) return fsn_resample_n_out(n_in, p.u, p.d);
+    return n_in * p.u <= p.H ? 0 : (n_in * p.u - p.H - 1) / p.d + 1;
+}
+
+extern "C" size_t fsn_resample_stream_state_bytes(int sr_in, int sr_out, int zeros, int capacity) {
+    FsnResamplePlan offline;
+    FsnResampleStreamPlan p;
+    StreamBlob b;
+    offline.beta = 5.0;
+    offline.rolloff = 1.0;
+    if (!stream_plan("fsn_resample_stream_state_bytes", sr_in, sr_out, zeros, &offline, &p)) return 0;
+    if (capacity < 1 || capacity > 65535) {
+        fsn_set_error("fsn_resample_stream_state_bytes: capacity = %d: 1 to 65535 sessions", capacity);
+        return 0;
+    }
+    return stream_carve(offline, p, capacity, nullptr, &b);
+}
+
+extern "C" int fsn_resample_stream_init(void* state, size_t state_bytes, int capacity, int sr_in, int sr_out, int zeros,
+                                        double beta, double rolloff, void* stream) {
+    FsnResamplePlan offline;
+    FsnResampleStreamPlan p;
+    StreamBlob b;
+    FSN_TRY(stream_call("fsn_resample_stream_init", state, state_bytes, capacity, sr_in, sr_out, zeros, beta, rolloff, &offline,
+                        &p, &b));
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    FsnCallScope scope(stream);
+    if (p.u != 1 || p.d != 1) FSN_TRY(fsn_launch_resample_taps(offline, b.h, b.poly, s));
+    return fsn_launch_zero_words(reinterpret_cast<unsigned*>(b.slots), (size_t)capacity * p.slot_floats, s);
+}
+
+extern "C" int fsn_resample_stream_push(void* state, size_t state_bytes, int capacity, int sr_in, int sr_out, int zeros,
+                                        const fsn_resample_stream_item* items, int n, const float* x, int C_max, float* y,
+                                        int O_max, void* stream) {
+    FsnResamplePlan offline;
+    FsnResampleStreamPlan p;
+    StreamBlob b;
+    FSN_TRY(stream_call("fsn_resample_stream_push", state, state_bytes, capacity, sr_in, sr_out, zeros, 5.0, 1.0, &offline, &p,
+                        &b));
+    FSN_REQUIRE(n >= 1 && n <= capacity, "fsn_resample_stream_push: n = %d sessions of %d", n, capacity);
+    FSN_REQUIRE(items && x && y, "fsn_resample_stream_push: NULL pointer argument");
+    FSN_REQUIRE(x != y, "fsn_resample_stream_push: y must not alias x");
+    FSN_REQUIRE(C_max >= 1 && C_max <= (1 << 30) && O_max >= 1 && O_max <= (1 << 30),
+                "fsn_resample_stream_push: C_max = %d, O_max = %d: both in [1, 2^30]", C_max, O_max);
+    FsnCallScope scope(stream);
+    return fsn_launch_resample_stream(p, b.poly, b.slots, capacity, items, n, x, C_max, y, O_max, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fsn_resample_stream_reset(void* state, size_t state_bytes, int capacity, int sr_in, int sr_out, int zeros,
+                                         const int* slots, int n, void* stream) {
+    FsnResamplePlan offline;
+    FsnResampleStreamPlan p;
+    StreamBlob b;
+    FSN_TRY(stream_call("fsn_resample_stream_reset", state, state_bytes, capacity, sr_in, sr_out, zeros, 5.0, 1.0, &offline, &p,
+                        &b));
+    FSN_REQUIRE(n >= 1 && n <= capacity, "fsn_resample_stream_reset: n = %d sessions of %d", n, capacity);
+    FSN_REQUIRE(slots, "fsn_resample_stream_reset: NULL pointer argument");
+    FsnCallScope scope(stream);
+    return fsn_launch_resample_stream_reset(p, b.slots, capacity, slots, n, static_cast<hipStream_t>(stream));
 }

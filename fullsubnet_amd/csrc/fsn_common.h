@@ -451,6 +451,24 @@ int fsn_launch_resample_taps(const FsnResamplePlan& p, double* h, double* poly, 
 int fsn_launch_resample(const float* x, const int* lengths, int B, int L_max, const FsnResamplePlan& p, const double* poly,
                         float* y, int L_out_max, int* out_lengths, hipStream_t s);
 
+// resample_stream_kernels.hip (fsn_resample_stream_*).  A tick of a serving pool is a few hundred outputs per session, so
+// a workgroup takes `tile` consecutive outputs of one session, one per thread.
+constexpr int kFsnResampleStreamThreads = 256;
+constexpr int kFsnResampleStreamMaxStretch = 16384;  // input samples a workgroup stages (fp32: 64 KB)
+struct FsnResampleStreamPlan {
+    int u, d, H;      // as FsnResamplePlan; H = 0 for u == d == 1 (the chunks pass through)
+    int J, Js;        // taps per phase (1 for u == d == 1); row stride of the polyphase table
+    int tile;         // outputs of a workgroup: 256, halved until its stretch can be staged
+    int stretch;      // input samples a workgroup stages at most: (tile - 1) d / u + J + 1
+    int taps_in_lds;  // the table is staged: it fits beside the stretch and is no longer than the tile's tile * J reads
+    int slot_floats;  // two history buffers of J - 1 samples, rounded up to 64 floats
+};
+int fsn_launch_resample_stream(const FsnResampleStreamPlan& p, const double* poly, float* slots, int capacity,
+                               const fsn_resample_stream_item* items, int n, const float* x, int C_max, float* y, int O_max,
+                               hipStream_t s);
+int fsn_launch_resample_stream_reset(const FsnResampleStreamPlan& p, float* slots, int capacity, const int* ids, int n,
+                                     hipStream_t s);
+
 // dft_kernels.hip (any even n_fft / any hop: direct fp64 DFT; reference layout [B][F][T] only).  lengths (device, [B], may
 // be NULL): per-row sample counts of a ragged batch; L / length is then the row stride and the longest row, T its frames
 int fsn_launch_dft_stft(const float* y, int B, int L, const float* window, float* re, float* im, float* mag, int T,

@@ -17,6 +17,15 @@ model step (``fsn_fullsubnet_stream_pool_step``) and frame synthesis (``fsn_stre
 host-to-device copy of the slot list.  Everything a session carries (LSTM states, norm sums, its own step count, the last
 hop, the spectra waiting for their mask, the overlap-add half frame) lives in its slot of one device blob.
 
+Sessions at another sample rate (``input_sr``, ``output_sr`` = "model" | "input" | Hz, ``resample_design``): ``push`` keeps
+the raw chunk; ``step()`` first converts every session's pending input to the model's rate in ONE
+``fsn_resample_stream_push`` call, runs the tick as above and sends its outputs through ONE call of a second resampler -
+at most two more library calls and two small table copies per tick, whatever the number of sessions.  Both resamplers
+carry their state (``stream_resample.StreamResampler``), so the model sees, bit for bit, ``resample.resample`` of the whole
+utterance; ``close()`` flushes both and trims to ``out_length(n, input_sr, output_sr)`` samples in all.  The conversion adds
+H / u samples of delay each way (0.625 ms at 48 <-> 16 kHz with "scipy", 2 ms with "sharp").  With the default arguments
+no resampler exists and nothing here runs differently.
+
 ``SessionBook`` is the host book-keeping (which frame is next, who is ready, model steps versus output frames, the
 look-ahead drop); it makes no device call, so it is tested without a GPU.
 """
@@ -25,8 +34,11 @@ import ctypes
 import torch
 
 from . import _lib
+from .resample import out_length
+from .stream_resample import StreamResampler
 
 N_FFT, HOP = 512, 256
+MODEL_SR = 16000  # the rate the fused FullSubNet configuration is trained at (a model may say otherwise: model.sr)
 
 
 class _Session:
@@ -41,6 +53,15 @@ class _Session:
         self.steps = 0                 # model steps, the look-ahead zero frames at the end included
         self.n_out = 0                 # samples emitted
         self.closing = False
+
+
+class _RateSession:
+    """What a session carries when the pool converts rates: its ids in the two resamplers, the raw chunks that wait
+    for the next step(), samples received at the input rate and samples emitted at the output rate."""
+    __slots__ = ("down", "up", "pending", "n_in", "n_out")
+
+    def __init__(self, down, up):
+        self.down, self.up, self.pending, self.n_in, self.n_out = down, up, [], 0, 0
 
 
 class SessionBook:
@@ -168,7 +189,8 @@ def _check_slots(slots, capacity):
 
 
 class StreamPool:
-    def __init__(self, model, capacity=64, poison_buffers=False):
+    def __init__(self, model, capacity=64, poison_buffers=False, input_sr=None, output_sr="model", resample_design="scipy",
+                 record_model_rate=False):
         if not getattr(model, "_fused", False):
             raise NotImplementedError("StreamPool runs the fused FullSubNet configuration only (model._fused is false: "
                                       "use one StreamingEnhancer per stream for composed configurations)")
@@ -192,6 +214,29 @@ class StreamPool:
         self._window = torch.hann_window(N_FFT, device=self.device)
         self.poison_buffers = bool(poison_buffers)  # debugging: NaN-fill every workspace and output before its call
         self._buf = {}   # sid -> (device samples from global index buf0 on, buf0)
+        # Sessions at another rate than the model's (module docstring): two stateful resamplers around the tick.  With
+        # the default arguments neither exists and no code below this block runs differently.
+        self.model_sr = int(getattr(model, "sr", MODEL_SR))
+        if input_sr is not None and (isinstance(input_sr, bool) or not isinstance(input_sr, int) or input_sr < 1):
+            raise ValueError(f"input_sr must be a positive integer or None, got {input_sr!r}")
+        self.input_sr = self.model_sr if input_sr is None else input_sr
+        if output_sr == "model":
+            self.output_sr = self.model_sr
+        elif output_sr == "input":
+            self.output_sr = self.input_sr
+        elif isinstance(output_sr, bool) or not isinstance(output_sr, int) or output_sr < 1:
+            raise ValueError(f'output_sr must be "model", "input" or a positive integer, got {output_sr!r}')
+        else:
+            self.output_sr = output_sr
+        self.resample_design = resample_design
+        self._down = self._up = None
+        if self.input_sr != self.model_sr:
+            self._down = StreamResampler(self.input_sr, self.model_sr, self.capacity, resample_design, self.device)
+        if self.output_sr != self.model_sr:
+            self._up = StreamResampler(self.model_sr, self.output_sr, self.capacity, resample_design, self.device)
+        self.record_model_rate = bool(record_model_rate)  # debugging: keep every session's model-rate input and output
+        self._recorded = {}  # sid -> ([input chunks], [output chunks]) at the model's rate; kept after close
+        self._rate = {}      # sid -> _RateSession, while a resampler exists
 
     # ---- the three entries on a list of slots -------------------------------------------------
     def _ints(self, rows):
@@ -255,6 +300,11 @@ class StreamPool:
     def open(self):
         sid = self.book.open()
         self._buf[sid] = (torch.zeros(0, dtype=torch.float32, device=self.device), 0)
+        if self._down is not None or self._up is not None:
+            self._rate[sid] = _RateSession(self._down.open() if self._down is not None else None,
+                                           self._up.open() if self._up is not None else None)
+        if self.record_model_rate:
+            self._recorded[sid] = ([], [])
         return sid
 
     def slot(self, sid):
@@ -267,10 +317,53 @@ class StreamPool:
         chunk = torch.as_tensor(chunk).to(self.device, torch.float32)
         if chunk.dim() != 1:
             raise ValueError(f"chunk must be 1-D samples, got shape {tuple(chunk.shape)}")
+        if sid in self._rate:
+            self._rate[sid].n_in += chunk.numel()
+        if self._down is not None:  # the raw chunk waits for the next step()
+            if chunk.numel():
+                self._rate[sid].pending.append(chunk)
+            return
+        self._append(sid, chunk)
+
+    def _append(self, sid, chunk):
+        """Samples at the model's rate join the session's buffer."""
         if chunk.numel():
             buf, b0 = self._buf[sid]
             self._buf[sid] = (torch.cat([buf, chunk]), b0)
             self.book.push(sid, chunk.numel())
+            if self.record_model_rate:
+                self._recorded[sid][0].append(chunk)
+
+    def recorded(self, sid):
+        """(input, output) of a session at the model's rate so far (``record_model_rate=True``); kept after close."""
+        x, y = self._recorded[sid]
+        empty = torch.zeros(0, dtype=torch.float32, device=self.device)
+        return torch.cat(x) if x else empty, torch.cat(y) if y else empty
+
+    def _convert(self):
+        """Every session's pending input to the model's rate: ONE call of the down resampler."""
+        todo = {sid: r for sid, r in self._rate.items() if r.pending}
+        if not todo:
+            return
+        got = self._down.push({r.down: torch.cat(r.pending) if len(r.pending) > 1 else r.pending[0] for r in todo.values()})
+        for sid, r in todo.items():
+            r.pending = []
+            self._append(sid, got[r.down])
+
+    def _emit(self, out):
+        """A tick's outputs {sid: samples at the model's rate} to the output rate: ONE call of the up resampler."""
+        if self.record_model_rate:
+            for sid, y in out.items():
+                self._recorded[sid][1].append(y)
+        if self._up is None or not out:
+            return out
+        got = self._up.push({self._rate[sid].up: y for sid, y in out.items()})
+        res = {}
+        for sid in out:
+            r = self._rate[sid]
+            res[sid] = got[r.up]
+            r.n_out += res[sid].numel()
+        return res
 
     def _trim(self, sid):
         buf, b0 = self._buf[sid]
@@ -306,8 +399,12 @@ class StreamPool:
 
     def step(self):
         """One frame for every session that has one ready: {sid: samples} (empty while the look-ahead fills)."""
+        if self._down is not None:
+            self._convert()
         sids = self.book.ready()
-        return self._tick(sids) if sids else {}
+        if self._up is None and not self.record_model_rate:
+            return self._tick(sids) if sids else {}
+        return self._emit(self._tick(sids)) if sids else {}
 
     def drain(self):
         """step() until no session has a frame ready; the samples concatenated per session."""
@@ -320,9 +417,43 @@ class StreamPool:
                 parts.setdefault(sid, []).append(y)
         return {sid: torch.cat(ys) for sid, ys in parts.items()}
 
-    @torch.no_grad()
     def close(self, sid):
-        """End of the session: its remaining samples.  Complete frames that were not stepped yet run one by one (n = 1);
+        """End of the session: its remaining samples; over drain() + close() a session of n samples at ``input_sr`` has
+        returned exactly ``out_length(n, input_sr, output_sr)``."""
+        if self._down is None and self._up is None and not self.record_model_rate:
+            return self._close_model_rate(sid)
+        r = self._rate.get(sid)
+        if r is None:  # recording only
+            tail = self._close_model_rate(sid)
+            self._recorded[sid][1].append(tail)
+            return tail
+        self.book.session(sid)
+        n_model = out_length(r.n_in, self.input_sr, self.model_sr)
+        if n_model <= HOP:  # before anything is flushed: the session stays as it is, like the plain pool's
+            raise _lib.FsnError(f"session shorter than n_fft / 2 + 1 = {HOP + 1} samples at the model's rate (reflect padding), "
+                                f"like torch.stft: {r.n_in} samples at {self.input_sr} Hz are {n_model}")
+        if self._down is not None:
+            raw = torch.cat(r.pending) if r.pending else torch.zeros(0, dtype=torch.float32, device=self.device)
+            r.pending = []
+            self._append(sid, self._down.push({r.down: raw}, final=(r.down,))[r.down])
+            self._down.close(r.down)
+            assert self.book.session(sid).n_in == n_model
+        tail = self._close_model_rate(sid)
+        if self.record_model_rate:
+            self._recorded[sid][1].append(tail)
+        if self._up is not None:
+            target = out_length(r.n_in, self.input_sr, self.output_sr)
+            assert r.n_out <= target, (r.n_out, target)  # nothing beyond the target left before the end was known
+            tail = self._up.push({r.up: tail}, final=(r.up,))[r.up]
+            assert r.n_out + tail.numel() >= target
+            tail = tail[:target - r.n_out]  # the round trip n -> model rate -> out can be a few samples long
+            self._up.close(r.up)
+        del self._rate[sid]
+        return tail
+
+    @torch.no_grad()
+    def _close_model_rate(self, sid):
+        """End of the session at the model's rate: its remaining samples.  Complete frames that were not stepped yet run one by one (n = 1);
         then the last frame (right-edge reflection) and the look_ahead zero frames run as ONE model call with n = 1,
         k = 1 + look_ahead, the overlap-add tail follows, and the slot is reset and freed."""
         left = self.book.begin_close(sid)

@@ -985,6 +985,56 @@ int fsn_resample(const float* x, const int* lengths, int B, int L_max, int sr_in
                  void* stream);
 int fsn_debug_resample_plan(int sr_in, int sr_out, int zeros, int* out, int n);
 
+/* ---- sample-rate conversion of streams : sessions that receive their input chunk by chunk ---------------------------
+ * The same filter and the same sums as fsn_resample (notation above; J = ceil((2H + 1) / u) taps per phase), for up to
+ * `capacity` sessions that each carry their last J - 1 input samples in a slot of one device blob.  Output k of a session
+ * has newest input q(k) = floor((k d + H) / u) and is fp32(sum_{j < J} poly[(k d + H) mod u][j] x[q - j]), an fp64 fma
+ * chain in that order with x[m] = 0 for m < 0 - so whatever the chunking, a session's outputs are bit for bit those of
+ * fsn_resample on its whole input (DESIGN "resampling streams").
+ *   before the end of input, after n_in samples the outputs k < ready(n_in) may be emitted: ready = 0 while
+ *     n_in u <= H, else floor((n_in u - H - 1) / d) + 1 - those whose newest input has arrived;
+ *   at the end (`final`, n samples in all) the rest up to ceil(n u / d), with x[m] = 0 for m >= n;
+ *   u == d == 1 passes chunks through bit for bit with no delay (ready(n_in) = n_in).
+ * The delay this adds is H / u input samples: 30 samples at 48 kHz in (0.625 ms) for 48 -> 16 kHz and 10 samples at
+ * 16 kHz in (0.625 ms) for 16 -> 48 kHz with zeros = 10; 2 ms each way with zeros = 32.
+ *
+ * All counts live with the caller (fsn_resample_stream_ready is host arithmetic, no device call; -1 for a refused
+ * request).  The blob: a header (the taps [2H + 1] and the polyphase table [u][Js], formed on the device by
+ * fsn_resample_stream_init) and `capacity` slots of two history buffers [J - 1] each; all zeros is a fresh slot, and
+ * init clears every slot.  fsn_resample_stream_push is ONE launch for the n listed sessions: row i of x [n][C_max] holds
+ * item i's chunk, row i of y [n][O_max] receives its `count` outputs k0 .. k0 + count - 1 and zeros from there to O_max.
+ * `items` is a device table the caller writes (n entries).  An item reads buffer `parity` of its slot and, when its chunk
+ * is not empty and it is not final, writes the session's new history into the other one: the caller flips a session's
+ * parity after exactly those pushes (a final push leaves the slot stale: reset it before it is used again).  Chunks of 0
+ * and 1 samples are legal, and chunks longer than the history.  What an item says is clamped on the device (a slot
+ * outside [0, capacity) or a position outside [0, 2^40) writes zeros only; n_chunk into [0, C_max]; count into [0, O_max]); slots must be distinct.  Slots
+ * that are not listed are not written.  The calls never synchronise and copy nothing; a session has the same bits alone
+ * and beside any others; an all-zero input gives exact zeros.  fsn_resample_stream_reset zeroes the listed slots (device
+ * list of n ids).  Additive entries (no new FSN_ABI_VERSION; a binding looks them up by name).
+ * Refused with FSN_ERR_ARG, a message and no launch (the size query returns 0): what fsn_resample refuses of rates and
+ * design, a filter of more than 16383 taps per phase, capacity outside [1, 65535], n < 1 or n > capacity, a state blob
+ * that is NULL, not 256-byte aligned or not of exactly fsn_resample_stream_state_bytes, a NULL pointer, C_max or O_max
+ * outside [1, 2^30]. */
+typedef struct fsn_resample_stream_item {
+    long long slot;      /* [0, capacity) */
+    long long n_chunk;   /* samples in row i of x */
+    long long final;     /* 0 / 1: the session's input ends with this chunk */
+    long long parity;    /* 0 / 1: the history buffer that holds the samples before this chunk */
+    long long n_before;  /* samples the session received before this chunk */
+    long long k0;        /* first output to write = outputs emitted so far */
+    long long count;     /* outputs to write */
+    long long reserved;  /* 0 */
+} fsn_resample_stream_item;
+long fsn_resample_stream_ready(long n_in, int final, int sr_in, int sr_out, int zeros);
+size_t fsn_resample_stream_state_bytes(int sr_in, int sr_out, int zeros, int capacity);
+int fsn_resample_stream_init(void* state, size_t state_bytes, int capacity, int sr_in, int sr_out, int zeros, double beta,
+                             double rolloff, void* stream);
+int fsn_resample_stream_push(void* state, size_t state_bytes, int capacity, int sr_in, int sr_out, int zeros,
+                             const fsn_resample_stream_item* items, int n, const float* x, int C_max, float* y, int O_max,
+                             void* stream);
+int fsn_resample_stream_reset(void* state, size_t state_bytes, int capacity, int sr_in, int sr_out, int zeros,
+                              const int* slots, int n, void* stream);
+
 int fsn_profile_num_stages(void);
 const char* fsn_profile_stage_name(int stage);
 int fsn_profile_read(void* stream, float* ms_per_stage, int n);
