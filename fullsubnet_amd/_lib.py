@@ -291,6 +291,8 @@ SIGNATURES = {
     "fsn_debug_core_plan": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int]),
     "fsn_debug_core_call_plan": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_long, _c.c_long, _c.c_void_p, _c.c_int]),
     "fsn_debug_core_last_launches": (_c.c_uint, []),
+    "fsn_debug_stream_state_layout": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
+    "fsn_debug_stream_pool_layout": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int]),
     "fsn_improved_front": (_c.c_int, [_f32p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_void_p]),
     "fsn_bft_to_rows": (_c.c_int, [_f32p, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_int, _c.c_int, _c.c_void_p]),
     "fsn_rows_to_bft": (_c.c_int, [_f32p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_void_p]),
@@ -329,7 +331,8 @@ SIGNATURES = {
 ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr", "fsn_resample_out_length",
                 "fsn_resample_workspace_bytes", "fsn_resample_taps", "fsn_resample", "fsn_debug_resample_plan",
                 "fsn_resample_stream_ready", "fsn_resample_stream_state_bytes", "fsn_resample_stream_init",
-                "fsn_resample_stream_push", "fsn_resample_stream_reset")
+                "fsn_resample_stream_push", "fsn_resample_stream_reset", "fsn_debug_stream_state_layout",
+                "fsn_debug_stream_pool_layout")
 
 
 def lib():
@@ -498,6 +501,29 @@ def core_last_launches():
     """Names of the launchers (and sub-band GEMM sites) the last library call of THIS thread went through."""
     m = lib().fsn_debug_core_last_launches()
     return {name for k, name in enumerate(LAUNCH_BITS) if m >> k & 1}
+
+
+STREAM_STATE_LAYOUT = ("fb_h0", "fb_h1", "fb_c0", "fb_c1", "sb_h0", "sb_h1", "sb_c0", "sb_c1", "fb_sum", "sb_sum", "npad_fb",
+                       "npad_sb", "bytes")
+STREAM_POOL_LAYOUT = ("fb_h0", "fb_h1", "fb_c0", "fb_c1", "sb_h0", "sb_h1", "sb_c0", "sb_c1", "fb_sum", "sb_sum", "steps",
+                      "in_tail", "ola_tail", "ring_re", "ring_im", "slot_bytes", "F", "FP", "Hf", "Hs", "R")
+
+
+def stream_state_layout(cfg, B):
+    """Byte offsets of the arrays of the stream step's state blob at batch B, its padded row counts and its size
+    (fsn_debug_stream_state_layout); the blob of the segment entries starts with the same arrays."""
+    buf = (ctypes.c_long * len(STREAM_STATE_LAYOUT))()
+    if lib().fsn_debug_stream_state_layout(ctypes.byref(cfg), B, buf, len(buf)) != 0:
+        raise FsnError("fsn_debug_stream_state_layout: bad arguments")
+    return dict(zip(STREAM_STATE_LAYOUT, list(buf)))
+
+
+def stream_pool_layout(cfg):
+    """Byte offsets into one record of the streaming pool, its size and dimensions (fsn_debug_stream_pool_layout)."""
+    buf = (ctypes.c_long * len(STREAM_POOL_LAYOUT))()
+    if lib().fsn_debug_stream_pool_layout(ctypes.byref(cfg), buf, len(buf)) != 0:
+        raise FsnError("fsn_debug_stream_pool_layout: bad arguments")
+    return dict(zip(STREAM_POOL_LAYOUT, list(buf)))
 
 
 def profile_read(device=None):

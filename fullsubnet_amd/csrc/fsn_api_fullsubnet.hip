@@ -1111,6 +1111,33 @@ extern "C" int fsn_fullsubnet_stream_pool_step(const fsn_fullsubnet_cfg* cfg, co
     return fsn_launch_pool_scatter(state, L, capacity, slots, n, 1, t.sb[0], t.sb[1], t.sb[2], t.sb[3], Npad, k, s);
 }
 
+// test hooks (host only): where the arrays of the two state blobs lie, from the code the entries carve them with
+extern "C" int fsn_debug_stream_state_layout(const fsn_fullsubnet_cfg* cfg, int B, long* out, int n) {
+    if (check_cfg(cfg) != FSN_OK || B < 1 || B > 4096 || !out || n < 13) return -1;
+    char* const base = reinterpret_cast<char*>((uintptr_t)1 << 20);  // never dereferenced: only differences are taken
+    Carver cv(base);
+    const StreamState st = stream_carve(cv, cfg, B);
+    const void* const at[10] = {st.fb_h0, st.fb_h1, st.fb_c0, st.fb_c1, st.sb_h0, st.sb_h1, st.sb_c0, st.sb_c1, st.fb_sum, st.sb_sum};
+    for (int i = 0; i < 10; ++i) out[i] = (long)(static_cast<const char*>(at[i]) - base);
+    out[10] = fsn_round_up(B, 16);
+    out[11] = fsn_round_up(B * cfg->num_freqs, 16);
+    out[12] = (long)fsn_round_up_sz(cv.off, 256);
+    return FSN_OK;
+}
+extern "C" int fsn_debug_stream_pool_layout(const fsn_fullsubnet_cfg* cfg, long* out, int n) {
+    if (check_cfg(cfg) != FSN_OK || !out || n < 21) return -1;
+    const FsnPoolLayout L = pool_layout(cfg);
+    for (int a = 0; a < 4; ++a) {
+        out[a] = (long)L.fb[a];
+        out[4 + a] = (long)L.sb[a];
+    }
+    const size_t rest[8] = {L.fb_sum, L.sb_sum, L.steps, L.in_tail, L.ola_tail, L.ring_re, L.ring_im, L.slot_bytes};
+    for (int i = 0; i < 8; ++i) out[8 + i] = (long)rest[i];
+    const int dims[5] = {L.F, L.FP, L.Hf, L.Hs, L.R};
+    for (int i = 0; i < 5; ++i) out[16 + i] = dims[i];
+    return FSN_OK;
+}
+
 // ---- recordings of any length: the model in segments of k frames, both norms --------------------------------------------
 // The stream step's two halves as entries of their own, so that the offline norm - whose divisors are means over the whole
 // recording - can run in three passes over the segments: (1) per-bin magnitude sums, (2) the full-band model, which needs

@@ -869,6 +869,19 @@ int fsn_debug_core_call_plan(const fsn_fullsubnet_cfg* cfg, int B, int T, long r
  * lstm_step, lstm_step_cu, lstm_wavefront2, lstm2_group, fb_chain, then the model core's sub-band GEMM sites: layer-0
  * projection of rows that run step by step, layer-1 projection, output layer as a GEMM. */
 unsigned fsn_debug_core_last_launches(void);
+/* Test hooks that need no device: where the arrays of the opaque state blobs lie, formed by the code the entries carve
+ * them with (tests/test_gpu_stream_sweep.py writes and reads states through them).
+ * fsn_debug_stream_state_layout: the blob of fsn_fullsubnet_stream_step at batch B, which is also the head of the blob of
+ * the fsn_fullsubnet_segment_* entries (either norm).  out[0..13) (n >= 13): byte offsets of 0 - 3 the full-band model's
+ * h0, h1, c0, c1 [padded rows][fb_hidden] floats, 4 - 7 the sub-band model's [padded rows][sb_hidden], 8 fb_sum [B]
+ * doubles, 9 sb_sum [B num_freqs] doubles; 10 / 11 the padded row counts of the full-band / sub-band arrays; 12 the size
+ * fsn_fullsubnet_stream_state_bytes returns.
+ * fsn_debug_stream_pool_layout: one record of the streaming pool.  out[0..21) (n >= 21): byte offsets into the record of
+ * 0 - 3 the full-band h0, h1, c0, c1 [fb_hidden], 4 - 7 the sub-band ones [num_freqs][sb_hidden], 8 fb_sum (double), 9 sb_sum
+ * [num_freqs] doubles, 10 steps (int), 11 in_tail, 12 ola_tail, 13 ring_re, 14 ring_im; 15 the bytes of a record; 16 - 20
+ * num_freqs, its padded width, fb_hidden, sb_hidden, ring frames.  Both: -1 on bad arguments. */
+int fsn_debug_stream_state_layout(const fsn_fullsubnet_cfg* cfg, int B, long* out, int n);
+int fsn_debug_stream_pool_layout(const fsn_fullsubnet_cfg* cfg, long* out, int n);
 /* ---- training pairs mixed on the device : recipes/dns_interspeech_2020/dataset_train.py ---------------------------
  * The arithmetic of Dataset.snr_mix (dataset_train.py:137-195, with norm_amplitude / tailor_dB_FS / is_clipped of
  * audio_zen/acoustics/feature.py:99-114) as deterministic functions of host-drawn descriptors: every random draw stays
