@@ -323,6 +323,25 @@ SIGNATURES = {
                                             _c.c_int, _f32p, _c.c_int, _f32p, _c.c_int, _c.c_void_p]),
     "fsn_resample_stream_reset": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
                                              _c.c_int, _c.c_void_p]),
+    "fsn_lstm_bilayer_save_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "fsn_lstm_bilayer_fwd_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "fsn_lstm_bilayer_forward": (_c.c_int, [_f32p, _c.c_long, _f32p, _f32p, _f32p, _f32p, _c.c_int, _c.c_int, _c.c_int,
+                                            _c.c_int, _f32p, _c.c_long, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t,
+                                            _c.c_void_p]),
+    "fsn_lstm_bilayer_bwd_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "fsn_lstm_bilayer_backward": (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _f32p, _c.c_int, _c.c_int, _c.c_int,
+                                             _c.c_int, _f32p, _c.c_long, _c.c_void_p, _f32p, _c.c_long, _f32p, _f32p, _f32p,
+                                             _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_gru_bilayer_save_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "fsn_gru_bilayer_fwd_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "fsn_gru_bilayer_forward": (_c.c_int, [_f32p, _c.c_long, _f32p, _f32p, _f32p, _f32p, _c.c_int, _c.c_int, _c.c_int,
+                                           _c.c_int, _f32p, _c.c_long, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t,
+                                           _c.c_void_p]),
+    "fsn_gru_bilayer_bwd_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "fsn_gru_bilayer_backward": (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _f32p, _c.c_int, _c.c_int, _c.c_int,
+                                            _c.c_int, _f32p, _c.c_long, _c.c_void_p, _f32p, _c.c_long, _f32p, _f32p, _f32p, _f32p,
+                                            _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_debug_bilayer_last_step_launches": (_c.c_uint, []),
     "fsn_profile_num_stages": (_c.c_int, []),
     "fsn_profile_stage_name": (_c.c_char_p, [_c.c_int]),
     "fsn_profile_read": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_float), _c.c_int]),
@@ -332,7 +351,8 @@ ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr", "fsn_resam
                 "fsn_resample_workspace_bytes", "fsn_resample_taps", "fsn_resample", "fsn_debug_resample_plan",
                 "fsn_resample_stream_ready", "fsn_resample_stream_state_bytes", "fsn_resample_stream_init",
                 "fsn_resample_stream_push", "fsn_resample_stream_reset", "fsn_debug_stream_state_layout",
-                "fsn_debug_stream_pool_layout")
+                "fsn_debug_stream_pool_layout", "fsn_lstm_bilayer_forward", "fsn_lstm_bilayer_backward",
+                "fsn_gru_bilayer_forward", "fsn_gru_bilayer_backward", "fsn_debug_bilayer_last_step_launches")
 
 
 def lib():

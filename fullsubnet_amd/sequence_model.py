@@ -9,6 +9,10 @@ parameters; every layer runs through the C ABI:
 * training: ``LstmLayerFunction`` / ``GruLayerFunction`` / ``LinearFunction`` (fullsubnet_amd/train.py:
   forward with saved activations + back-propagation through time).
 
+``bidirectional=True`` holds torch's bidirectional rnn (``*_reverse`` parameters, ``nn.Linear(2 * hidden_size, ..)``) and runs
+layer by layer through ``fsn_lstm_bilayer_forward`` / ``fsn_gru_bilayer_forward`` (``BiLstmLayerFunction`` /
+``BiGruLayerFunction`` in training): both directions of a layer advance in one launch per step.
+
 Hidden sizes that are not a multiple of 64 (Fast FullSubNet's 257) are run zero-padded: a unit whose
 weights and biases are all zero keeps h = c = 0 at every step, so the padding is exact.
 """
@@ -22,18 +26,28 @@ def _round_up(x, m):
     return (x + m - 1) // m * m
 
 
-def pad_lstm_weights(w_ih, w_hh, b_ih, b_hh, in_pad, hidden_pad=None):
+def pad_lstm_weights(w_ih, w_hh, b_ih, b_hh, in_pad, hidden_pad=None, in_halves=None):
     """nn.LSTM / nn.GRU layer tensors ([gH, I], [gH, H], [gH], [gH], g = 4 / 3 gates) -> the same layer
     with H padded to a multiple of 64 (or to ``hidden_pad``) and I padded to ``in_pad`` columns (gate blocks stay
-    contiguous).  Plain torch ops, so gradients flow back to the unpadded parameters when autograd is recording."""
+    contiguous).  Plain torch ops, so gradients flow back to the unpadded parameters when autograd is recording.
+    ``in_halves`` = the width Hb of each direction of a bidirectional layer below (I = 2 Hb): its padded output is
+    ``in_pad`` = 2 Hbp columns wide, so input columns [0, Hb) stay at [0, Hb) and columns [Hb, 2 Hb) go to
+    [Hbp, Hbp + Hb)."""
     H, I = w_hh.shape[1], w_ih.shape[1]
     g = w_hh.shape[0] // H
     Hp = _round_up(H, 64) if hidden_pad is None else hidden_pad
+    if in_halves is not None and (I != 2 * in_halves or in_pad % 2 or in_pad // 2 < in_halves):
+        raise _lib.FsnError(f"pad_lstm_weights: {I} input columns are not two halves of {in_halves} within {in_pad}")
     if Hp == H and in_pad == I:
         return w_ih, w_hh, b_ih, b_hh
     dev = w_ih.device
     wi = torch.zeros((g, Hp, in_pad), dtype=torch.float32, device=dev)
-    wi[:, :H, :I] = w_ih.reshape(g, H, I)
+    if in_halves is None:
+        wi[:, :H, :I] = w_ih.reshape(g, H, I)
+    else:
+        Hb, Hbp = in_halves, in_pad // 2
+        wi[:, :H, :Hb] = w_ih.reshape(g, H, I)[:, :, :Hb]
+        wi[:, :H, Hbp:Hbp + Hb] = w_ih.reshape(g, H, I)[:, :, Hb:]
     wh = torch.zeros((g, Hp, Hp), dtype=torch.float32, device=dev)
     wh[:, :H, :H] = w_hh.reshape(g, H, H)
     bi = torch.zeros((g, Hp), dtype=torch.float32, device=dev)
@@ -106,6 +120,23 @@ def gru_layer_infer(x, w_ih, w_hh, b_ih, b_hh):
     return hseq
 
 
+def bilayer_infer(cell, x, w_ih, w_hh, b_ih, b_hh):
+    """One bidirectional LSTM / GRU layer, inference mode (fsn_lstm_bilayer_forward / fsn_gru_bilayer_forward: both directions
+    per step launch).  x [T, N, ldx] as lstm_layer_infer takes it; the tensors carry a leading direction axis (0 forward,
+    1 ``*_reverse``): w_ih [2, gH, I], w_hh [2, gH, H], b_* [2, gH].  Returns hseq [T, N, 2H], forward | reverse."""
+    L = _lib.lib()
+    T, N, ldx = x.shape
+    I, H = w_ih.shape[2], w_hh.shape[2]
+    query, entry = (L.fsn_lstm_bilayer_fwd_workspace_bytes, L.fsn_lstm_bilayer_forward) if cell == "LSTM" else \
+        (L.fsn_gru_bilayer_fwd_workspace_bytes, L.fsn_gru_bilayer_forward)
+    hseq = torch.empty((T, N, 2 * H), dtype=torch.float32, device=x.device)
+    ws = _lib.workspace(query(T, N, I, H), x.device)
+    _lib.check(entry(_lib.dev_ptr(x, "x"), ldx, _lib.dev_ptr(w_ih, "w_ih"), _lib.dev_ptr(w_hh, "w_hh"),
+                     _lib.dev_ptr(b_ih, "b_ih"), _lib.dev_ptr(b_hh, "b_hh"), T, N, I, H, _lib.dev_ptr(hseq), 2 * H, None, 0,
+                     ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device)))
+    return hseq
+
+
 def linear_infer(x2, w, b, relu):
     """x2 [R, ldx] (columns beyond I = w.shape[1] zero, ldx % 16 == 0) -> [R, O] (+ ReLU)."""
     L = _lib.lib()
@@ -153,14 +184,13 @@ class SequenceModel(nn.Module):
         super().__init__()
         if sequence_model not in ("LSTM", "GRU"):
             raise NotImplementedError(f"Not implemented {sequence_model}")
-        if bidirectional:
-            raise NotImplementedError("libfsn_hip: unidirectional only (every FullSubNet TOML)")
         rnn = nn.LSTM if sequence_model == "LSTM" else nn.GRU
+        self.bidirectional = bool(bidirectional)
         self.sequence_model = rnn(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
-                                  batch_first=True, bidirectional=False)
+                                  batch_first=True, bidirectional=self.bidirectional)
         self.cell = sequence_model
         if int(output_size):
-            self.fc_output_layer = nn.Linear(hidden_size, output_size)
+            self.fc_output_layer = nn.Linear(hidden_size * 2 if self.bidirectional else hidden_size, output_size)
         if output_activate_function:
             acts = {"Tanh": nn.Tanh, "ReLU": nn.ReLU, "ReLU6": nn.ReLU6, "LeakyReLU": nn.LeakyReLU, "PReLU": nn.PReLU}
             if output_activate_function not in acts:
@@ -180,19 +210,38 @@ class SequenceModel(nn.Module):
         return (getattr(m, f"weight_ih_l{k}"), getattr(m, f"weight_hh_l{k}"), getattr(m, f"bias_ih_l{k}"),
                 getattr(m, f"bias_hh_l{k}"))
 
+    def _bi_layer_tensors(self, k):
+        """Layer k of a bidirectional block, padded, each tensor with a leading direction axis (0 forward, 1 ``*_reverse``):
+        what the bilayer entries take.  Each direction is padded to Hp units, so the layer's output is 2 Hp wide and the layer
+        above reads its two halves at columns [0, H) and [Hp, Hp + H).  Plain torch ops (gradients reach the parameters)."""
+        m, H, Hp = self.sequence_model, self.hidden_size, _round_up(self.hidden_size, 64)
+        dirs = []
+        for sfx in ("", "_reverse"):
+            t = tuple(getattr(m, f"{n}_l{k}{sfx}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+            dirs.append(pad_lstm_weights(*t, self.input_size) if k == 0 else pad_lstm_weights(*t, 2 * Hp, in_halves=H))
+        return tuple(torch.stack(pair) for pair in zip(*dirs))
+
     def _inference_weights(self):
         ps = list(self.parameters())
         key = tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
         if self._padded is None or key != self._padded_key:
-            Hp = _round_up(self.hidden_size, 64)
+            H, Hp = self.hidden_size, _round_up(self.hidden_size, 64)
             layers = []
             with torch.no_grad():
                 for k in range(self.num_layers):
+                    if self.bidirectional:
+                        layers.append(tuple(t.detach().contiguous() for t in self._bi_layer_tensors(k)))
+                        continue
                     in_pad = self.input_size if k == 0 else Hp
                     layers.append(tuple(t.detach().contiguous()
                                         for t in pad_lstm_weights(*self._layer_tensors(k), in_pad)))
                 fc = None
-                if self.output_size:
+                if self.output_size and self.bidirectional:  # the two halves of the [.., 2 Hp] sequence
+                    w = torch.zeros((self.output_size, 2 * Hp), dtype=torch.float32, device=ps[0].device)
+                    w[:, :H] = self.fc_output_layer.weight.detach()[:, :H]
+                    w[:, Hp:Hp + H] = self.fc_output_layer.weight.detach()[:, H:]
+                    fc = (w, self.fc_output_layer.bias.detach().contiguous())
+                elif self.output_size:
                     w = torch.zeros((self.output_size, Hp), dtype=torch.float32, device=ps[0].device)
                     w[:, :self.hidden_size] = self.fc_output_layer.weight.detach()
                     fc = (w, self.fc_output_layer.bias.detach().contiguous())
@@ -215,6 +264,20 @@ class SequenceModel(nn.Module):
         T, Np, _ = h.shape
         H, Hp = self.hidden_size, _round_up(self.hidden_size, 64)
         layers, fc = self._inference_weights()
+        if self.bidirectional:
+            # layer by layer through the bilayer entry (both directions per step launch); none of the wavefront, chain and
+            # persistent shortcuts below applies.  The sequence is [T, Np, 2 Hp]: forward | reverse, each padded to Hp
+            for w_ih, w_hh, b_ih, b_hh in layers:
+                h = bilayer_infer(self.cell, h, w_ih, w_hh, b_ih, b_hh)
+            relu = self.output_activate_function == "ReLU"
+            if fc is not None:
+                o = linear_infer(h.reshape(T * Np, 2 * Hp), fc[0], fc[1], relu).reshape(T, Np, self.output_size)
+            else:
+                o = h if Hp == H else torch.cat((h[:, :, :H], h[:, :, Hp:Hp + H]), dim=2)
+                relu = False
+            if self.output_activate_function and not relu:
+                o = self.activate_function(o)
+            return o if rows_out else from_rows(o, B)
         layer_infer = lstm_layer_infer if self.cell == "LSTM" else gru_layer_infer
         k = 0
         if self.cell == "LSTM":
@@ -254,6 +317,22 @@ class SequenceModel(nn.Module):
         # autocast arithmetic a two-layer stack of the group kernels' width runs on the persistent training kernels, in
         # pieces of whole clusters when it has more rows than one launch holds (Fast FullSubNet's bottleneck: 3 x 1536 rows
         # at the shipped batch of 72); fp32 and every other shape layer by layer as before
+        if self.bidirectional:
+            # fp32 whatever train_arithmetic says (BiLstmLayerFunction / BiGruLayerFunction)
+            from .train import BiGruLayerFunction, BiLstmLayerFunction
+            bilayer = BiLstmLayerFunction if self.cell == "LSTM" else BiGruLayerFunction
+            for k in range(self.num_layers):
+                h = bilayer.apply(h, *self._bi_layer_tensors(k))
+            if Hp != H:
+                h = torch.cat((h[..., :H], h[..., Hp:Hp + H]), dim=-1)
+            relu = self.output_activate_function == "ReLU"
+            if self.output_size:
+                o = LinearFunction.apply(h, self.fc_output_layer.weight, self.fc_output_layer.bias, relu)
+            else:
+                o, relu = h, False
+            if self.output_activate_function and not relu:
+                o = self.activate_function(o)
+            return o.permute(1, 2, 0)
         arith = getattr(self, "train_arithmetic", "f32")
         chunks = None
         if self.cell == "LSTM" and self.num_layers == 2 and arith != "f32" and Hp == H:
@@ -281,7 +360,7 @@ def multi_plan(models, shapes):
     ONE persistent launch (fsn_lstm2_multi_is_persistent); callers keep small stacks on one stream each otherwise."""
     import ctypes
     n = len(models)
-    if n < 1 or n > 8 or any(m.cell != "LSTM" or m.num_layers != 2 for m in models):
+    if n < 1 or n > 8 or any(m.cell != "LSTM" or m.num_layers != 2 or m.bidirectional for m in models):
         return False
     stacks = (_lib.Lstm2Stack * n)()
     for q, m, (B, F, T) in zip(stacks, models, shapes):
@@ -313,8 +392,8 @@ def multi_forward(models, xs=None, prepared=None, rows_out=False):
     stacks = (_lib.Lstm2Stack * n)()
     keep, hseqs, meta = [], [], []
     for i, (m, (h, B)) in enumerate(zip(models, prepared)):
-        if m.cell != "LSTM" or m.num_layers != 2 or h.dim() != 3 or h.shape[0] != T or not h.is_cuda:
-            raise _lib.FsnError("multi_forward: two-layer LSTM SequenceModels on GPU inputs with a common T")
+        if m.cell != "LSTM" or m.num_layers != 2 or m.bidirectional or h.dim() != 3 or h.shape[0] != T or not h.is_cuda:
+            raise _lib.FsnError("multi_forward: unidirectional two-layer LSTM SequenceModels on GPU inputs with a common T")
         Hp = _round_up(m.hidden_size, 64)
         Np, Ip = h.shape[1], h.shape[2]
         layers, fc = m._inference_weights()
@@ -345,8 +424,9 @@ def multi_forward(models, xs=None, prepared=None, rows_out=False):
 
 def pair_fusable(block0, block1, rows):
     """Whether two consecutive SequenceModel blocks run as ONE two-layer recurrence in inference (``pair_forward``): both
-    single-layer LSTM blocks, block0 without output layer / activation, few rows."""
+    single-layer unidirectional LSTM blocks, block0 without output layer / activation, few rows."""
     return (block0.cell == block1.cell == "LSTM" and block0.num_layers == block1.num_layers == 1
+            and not block0.bidirectional and not block1.bidirectional
             and not block0.output_size and not block0.output_activate_function
             and block1.input_size == block0.hidden_size and _round_up(rows, 16) < WAVEFRONT_BELOW_ROWS)
 
@@ -354,6 +434,8 @@ def pair_fusable(block0, block1, rows):
 def pair_forward_rows(block0, block1, h):
     """``block1(block0(.))`` of a fusable pair on time-major rows: h [T, Np, Ip] (zero beyond the block's input width) ->
     [T, Np, O] as the output layer writes it (rows beyond the batch are not meaningful)."""
+    if block0.bidirectional or block1.bidirectional:
+        raise _lib.FsnError("pair_forward_rows: a bidirectional block does not run as a wavefront pair")
     T, Np, _ = h.shape
     (layer0,), _ = block0._inference_weights()
     _, fc = block1._inference_weights()

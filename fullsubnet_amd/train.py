@@ -69,6 +69,84 @@ class LstmLayerFunction(torch.autograd.Function):
         return (dx[:, :N, :I] if need_dx else None), dw_ih, dw_hh, db, db.clone()
 
 
+def _bilayer_forward(ctx, cell, x, w_ih, w_hh, b_ih, b_hh):
+    L = _lib.lib()
+    T, N, I = x.shape
+    H = w_hh.shape[2]
+    Np, Ip = (N + 15) // 16 * 16, (I + 15) // 16 * 16
+    xp = x
+    if Np != N or Ip != I or not x.is_contiguous():
+        xp = torch.zeros((T, Np, Ip), dtype=torch.float32, device=x.device)
+        xp[:, :N, :I] = x
+    w_ih_c, w_hh_c = w_ih.detach().contiguous(), w_hh.detach().contiguous()
+    hseq = torch.empty((T, Np, 2 * H), dtype=torch.float32, device=x.device)
+    lstm = cell == "LSTM"
+    save = _lib.workspace((L.fsn_lstm_bilayer_save_bytes if lstm else L.fsn_gru_bilayer_save_bytes)(T, Np, H), x.device)
+    ws = _lib.workspace((L.fsn_lstm_bilayer_fwd_workspace_bytes if lstm else L.fsn_gru_bilayer_fwd_workspace_bytes)(T, Np, I, H),
+                        x.device)
+    _lib.check((L.fsn_lstm_bilayer_forward if lstm else L.fsn_gru_bilayer_forward)(
+        _lib.dev_ptr(xp, "x"), Ip, _lib.dev_ptr(w_ih_c, "w_ih"), _lib.dev_ptr(w_hh_c, "w_hh"),
+        _lib.dev_ptr(b_ih.detach().contiguous(), "b_ih"), _lib.dev_ptr(b_hh.detach().contiguous(), "b_hh"),
+        T, Np, I, H, _lib.dev_ptr(hseq), 2 * H, save.data_ptr(), save.numel(), ws.data_ptr(), ws.numel(),
+        _lib.stream_ptr(x.device)))
+    ctx.save_for_backward(xp, w_ih_c, w_hh_c, hseq, save)
+    ctx.dims = (T, N, I, H, Np, Ip)
+    return hseq[:, :N]
+
+
+def _bilayer_backward(ctx, cell, dh):
+    L = _lib.lib()
+    xp, w_ih, w_hh, hseq, save = ctx.saved_tensors
+    T, N, I, H, Np, Ip = ctx.dims
+    dev = dh.device
+    dhp = dh
+    if Np != N or not dh.is_contiguous():
+        dhp = torch.zeros((T, Np, 2 * H), dtype=torch.float32, device=dev)
+        dhp[:, :N] = dh
+    need_dx = ctx.needs_input_grad[0]
+    dx = torch.empty((T, Np, Ip), dtype=torch.float32, device=dev) if need_dx else None
+    dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
+    lstm = cell == "LSTM"
+    g = 4 if lstm else 3
+    dbs = [torch.empty((2, g * H), dtype=torch.float32, device=dev) for _ in range(1 if lstm else 2)]
+    ws = _lib.workspace((L.fsn_lstm_bilayer_bwd_workspace_bytes if lstm else L.fsn_gru_bilayer_bwd_workspace_bytes)(T, Np, I, H), dev)
+    _lib.check((L.fsn_lstm_bilayer_backward if lstm else L.fsn_gru_bilayer_backward)(
+        _lib.dev_ptr(dhp, "dh"), 2 * H, _lib.dev_ptr(xp), Ip, _lib.dev_ptr(w_ih), _lib.dev_ptr(w_hh), T, Np, I, H,
+        _lib.dev_ptr(hseq), 2 * H, save.data_ptr(), _lib.dev_ptr(dx, allow_none=True), Ip, _lib.dev_ptr(dw_ih),
+        _lib.dev_ptr(dw_hh), *[_lib.dev_ptr(b) for b in dbs], ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+    db_ih, db_hh = (dbs[0], dbs[0].clone()) if lstm else dbs
+    return (dx[:, :N, :I] if need_dx else None), dw_ih, dw_hh, db_ih, db_hh
+
+
+class BiLstmLayerFunction(torch.autograd.Function):
+    """One bidirectional nn.LSTM layer (h0 = c0 = 0) on time-major x [T, N, I] -> [T, N, 2H], forward | reverse
+    (fsn_lstm_bilayer_forward with saved activations + fsn_lstm_bilayer_backward: both directions per step launch).  The
+    weights come in stacked, direction 0 forward and 1 ``*_reverse`` - w_ih [2, 4H, I], w_hh [2, 4H, H], b_* [2, 4H] - and the
+    gradients go out stacked: the ``torch.stack`` outside the function hands each parameter its slice.  Runs in fp32 whatever
+    the owning model's ``train_arithmetic`` says: the 16-bit arithmetic is built for the unidirectional group kernels only."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh):
+        return _bilayer_forward(ctx, "LSTM", x, w_ih, w_hh, b_ih, b_hh)
+
+    @staticmethod
+    def backward(ctx, dh):
+        return _bilayer_backward(ctx, "LSTM", dh)
+
+
+class BiGruLayerFunction(torch.autograd.Function):
+    """One bidirectional nn.GRU layer (h0 = 0): as BiLstmLayerFunction with 3H gate rows r, z, n (fsn_gru_bilayer_forward /
+    fsn_gru_bilayer_backward); fp32 whatever ``train_arithmetic`` says."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh):
+        return _bilayer_forward(ctx, "GRU", x, w_ih, w_hh, b_ih, b_hh)
+
+    @staticmethod
+    def backward(ctx, dh):
+        return _bilayer_backward(ctx, "GRU", dh)
+
+
 # "f16" / "bf16": the arithmetic of torch.autocast (16-bit matrix-core operands, fp32 accumulation, everything stored in fp32);
 # "+s16" (Model.train_saves = "16", _lib.ARITH_SAVES16): the activated gates that BPTT re-reads saved in that 16-bit type too -
 # what the vendor LSTM keeps in its reserve space under autocast - half the save traffic of the two persistent launches

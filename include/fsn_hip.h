@@ -1048,6 +1048,45 @@ int fsn_resample_stream_push(void* state, size_t state_bytes, int capacity, int 
 int fsn_resample_stream_reset(void* state, size_t state_bytes, int capacity, int sr_in, int sr_out, int zeros,
                               const int* slots, int n, void* stream);
 
+/* ---- bidirectional nn.LSTM / nn.GRU layer (bidirectional = True of sequence_model.py:52-66) ------------------------------
+ * One layer, both directions: step launch s advances the forward direction at frame s and the reverse one at frame
+ * T - 1 - s, so a layer is T dependent launches (birnn_step_kernels.hip); the input projection of both directions is one
+ * GEMM.  Conventions of fsn_lstm_layer_forward / _backward (time-major rows, N % 16 == 0, H % 64 == 0 - smaller sizes run
+ * zero-padded -, h0 = c0 = 0, save == NULL: inference, dx may be NULL) with these specifics:
+ *   weights in torch's layout with a leading direction axis: w_ih [2][gH][I], w_hh [2][gH][H], b_ih / b_hh [2][gH] (g = 4
+ *     gates i, f, g, o / 3 gates r, z, n); direction 0 is forward, direction 1 torch's `*_reverse`; gradients likewise;
+ *   hseq [T][N][ldh], ldh >= 2 H and a multiple of 4: the forward direction's h_t in columns [0, H), the reverse one's in
+ *     [H, 2 H) - torch's output layout; dh [T][N][lddh] likewise; columns 2 H .. ldh - 1 of hseq and I .. lddx - 1 of dx are
+ *     never written;
+ *   save: fsn_*_bilayer_save_bytes, workspaces exactly the queries' sizes or more;
+ *   a direction's results do not depend on its slot: (w_r, w_f) on the frame-reversed input gives the two halves swapped
+ *     and frame-reversed, bit for bit, weight gradients included.
+ * Bad arguments (N % 16, H % 64, T < 1, ldh < 2 H, a NULL pointer): FSN_ERR_ARG with fsn_last_error text and no launch;
+ * the size queries return 0.  There is no `_state` form: the reverse direction starts from the LAST frame, so a
+ * bidirectional layer cannot be streamed chunk by chunk.  fsn_debug_bilayer_last_step_launches (test hook): the recurrent
+ * step launches the calling thread's last bilayer call issued (T).  Additive entries (no new FSN_ABI_VERSION). */
+size_t fsn_lstm_bilayer_save_bytes(int T, int N, int H);
+size_t fsn_lstm_bilayer_fwd_workspace_bytes(int T, int N, int I, int H);
+int fsn_lstm_bilayer_forward(const float* x, long ldx, const float* w_ih, const float* w_hh, const float* b_ih,
+                             const float* b_hh, int T, int N, int I, int H, float* hseq, long ldh, void* save,
+                             size_t save_bytes, void* workspace, size_t workspace_bytes, void* stream);
+size_t fsn_lstm_bilayer_bwd_workspace_bytes(int T, int N, int I, int H);
+int fsn_lstm_bilayer_backward(const float* dh, long lddh, const float* x, long ldx, const float* w_ih, const float* w_hh,
+                              int T, int N, int I, int H, const float* hseq, long ldh, const void* save, float* dx,
+                              long lddx, float* dw_ih, float* dw_hh, float* db, void* workspace, size_t workspace_bytes,
+                              void* stream);
+size_t fsn_gru_bilayer_save_bytes(int T, int N, int H);
+size_t fsn_gru_bilayer_fwd_workspace_bytes(int T, int N, int I, int H);
+int fsn_gru_bilayer_forward(const float* x, long ldx, const float* w_ih, const float* w_hh, const float* b_ih,
+                            const float* b_hh, int T, int N, int I, int H, float* hseq, long ldh, void* save,
+                            size_t save_bytes, void* workspace, size_t workspace_bytes, void* stream);
+size_t fsn_gru_bilayer_bwd_workspace_bytes(int T, int N, int I, int H);
+int fsn_gru_bilayer_backward(const float* dh, long lddh, const float* x, long ldx, const float* w_ih, const float* w_hh,
+                             int T, int N, int I, int H, const float* hseq, long ldh, const void* save, float* dx,
+                             long lddx, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, void* workspace,
+                             size_t workspace_bytes, void* stream);
+unsigned fsn_debug_bilayer_last_step_launches(void);
+
 int fsn_profile_num_stages(void);
 const char* fsn_profile_stage_name(int stage);
 int fsn_profile_read(void* stream, float* ms_per_stage, int n);
