@@ -95,6 +95,21 @@ class Params(ctypes.Structure):
     _fields_ = [(n, _f32p) for n in PARAM_FIELDS]
 
 
+class FastCfg(ctypes.Structure):  # fsn_fast_cfg
+    _fields_ = [(n, ctypes.c_int) for n in ("F", "num_mels", "shrink", "mel_neighbors", "enc_neighbors", "bn_hidden",
+                                            "bn_layers", "norm")]
+
+
+_LAYER = ("w_ih", "w_hh", "b_ih", "b_hh")
+FAST_PARAM_FIELDS = (["mel_w"] + [f"enc0_{n}" for n in _LAYER] + [f"enc1_{n}" for n in _LAYER] + ["enc1_fc_w", "enc1_fc_b"] +
+                     [f"bn_{n}_l0" for n in _LAYER] + [f"bn_{n}_l1" for n in _LAYER] + ["bn_fc_w", "bn_fc_b"] +
+                     [f"dec0_{n}" for n in _LAYER] + [f"dec1_{n}" for n in _LAYER] + ["dec1_fc_w", "dec1_fc_b"])
+
+
+class FastParams(ctypes.Structure):  # fsn_fast_params
+    _fields_ = [(n, _f32p) for n in FAST_PARAM_FIELDS]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/fsn_hip.h
 _c = ctypes
 SIGNATURES = {
@@ -342,6 +357,13 @@ SIGNATURES = {
                                             _c.c_int, _f32p, _c.c_long, _c.c_void_p, _f32p, _c.c_long, _f32p, _f32p, _f32p, _f32p,
                                             _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "fsn_debug_bilayer_last_step_launches": (_c.c_uint, []),
+    "fsn_fast_stream_packed_bytes": (_c.c_size_t, [_c.c_void_p]),
+    "fsn_fast_stream_pack": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_fast_stream_state_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int]),
+    "fsn_fast_stream_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int, _c.c_int]),
+    "fsn_fast_stream_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _f32p, _c.c_int,
+                                        _c.c_int, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_debug_fast_stream_state_layout": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
     "fsn_profile_num_stages": (_c.c_int, []),
     "fsn_profile_stage_name": (_c.c_char_p, [_c.c_int]),
     "fsn_profile_read": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_float), _c.c_int]),
@@ -352,7 +374,9 @@ ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr", "fsn_resam
                 "fsn_resample_stream_ready", "fsn_resample_stream_state_bytes", "fsn_resample_stream_init",
                 "fsn_resample_stream_push", "fsn_resample_stream_reset", "fsn_debug_stream_state_layout",
                 "fsn_debug_stream_pool_layout", "fsn_lstm_bilayer_forward", "fsn_lstm_bilayer_backward",
-                "fsn_gru_bilayer_forward", "fsn_gru_bilayer_backward", "fsn_debug_bilayer_last_step_launches")
+                "fsn_gru_bilayer_forward", "fsn_gru_bilayer_backward", "fsn_debug_bilayer_last_step_launches",
+                "fsn_fast_stream_packed_bytes", "fsn_fast_stream_pack", "fsn_fast_stream_state_bytes",
+                "fsn_fast_stream_workspace_bytes", "fsn_fast_stream_step", "fsn_debug_fast_stream_state_layout")
 
 
 def lib():
@@ -544,6 +568,21 @@ def stream_pool_layout(cfg):
     if lib().fsn_debug_stream_pool_layout(ctypes.byref(cfg), buf, len(buf)) != 0:
         raise FsnError("fsn_debug_stream_pool_layout: bad arguments")
     return dict(zip(STREAM_POOL_LAYOUT, list(buf)))
+
+
+FAST_STREAM_STATE_LAYOUT = ("enc0_h", "enc0_c", "enc1_h", "enc1_c", "dec0_h", "dec0_c", "dec1_h", "dec1_c", "bn_h0", "bn_c0",
+                            "bn_h1", "bn_c1", "mel_sum", "unit_sum", "partial", "held", "rows", "bn_rows", "enc1_hidden",
+                            "unit_width", "bytes")
+
+
+def fast_stream_state_layout(cfg, B):
+    """Byte offsets of the fields of fsn_fast_stream_step's state blob at batch B (-1: a bottleneck layer the configuration
+    does not have), its row counts, encoder.1's padded hidden size, the unit width and its size
+    (fsn_debug_fast_stream_state_layout)."""
+    buf = (ctypes.c_long * len(FAST_STREAM_STATE_LAYOUT))()
+    if lib().fsn_debug_fast_stream_state_layout(ctypes.byref(cfg), B, buf, len(buf)) != 0:
+        raise FsnError("fsn_debug_fast_stream_state_layout: bad arguments")
+    return dict(zip(FAST_STREAM_STATE_LAYOUT, list(buf)))
 
 
 def profile_read(device=None):

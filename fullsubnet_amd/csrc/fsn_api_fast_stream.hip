@@ -1,0 +1,286 @@
+// C ABI of libfsn_hip.so, Fast FullSubNet as a stream: the packed weights, the state blob and the host sequence of
+// fsn_fast_stream_step (k more model steps with carried state; include/fsn_hip.h states the contract, DESIGN why the model
+// is causal).  The recurrences run on the stateful layer entry (fsn_lstm_layer_forward_state on weights packed once by
+// fsn_lstm_layer_pack), the mel product and the output layers on the linear GEMM, the ends on fast_glue_kernels.hip's
+// spec_rows / mask_out with look-ahead 0, and everything that touches the state between them on fast_stream_kernels.hip.
+#include "fsn_api_internal.h"
+
+namespace {
+
+constexpr int kEnc0H = 384, kEnc1H = 320, kDecH = 512;  // the reference's literals (model.py:36-96); 257 units run padded to 320
+
+int unit_width(const fsn_fast_cfg* c) { return 2 * c->mel_neighbors + 1 + 2 * c->enc_neighbors + 1; }
+
+int check_cfg(const fsn_fast_cfg* c) {
+    FSN_REQUIRE(c, "NULL configuration");
+    FSN_REQUIRE(c->norm == FSN_NORM_CUMULATIVE_LAPLACE, "streaming needs the causal norm (FSN_NORM_CUMULATIVE_LAPLACE)");
+    FSN_REQUIRE(c->F == 257 && c->num_mels == 64, "fast stream: F %d / num_mels %d, the step takes 257 / 64 (the reference's block widths)",
+                c->F, c->num_mels);
+    FSN_REQUIRE(c->shrink >= 1, "fast stream: shrink %d must be >= 1", c->shrink);
+    FSN_REQUIRE(c->mel_neighbors >= 0 && c->mel_neighbors <= 7 && c->enc_neighbors >= 0 && c->enc_neighbors <= 7,
+                "fast stream: neighbours (%d, %d) outside 0 .. 7", c->mel_neighbors, c->enc_neighbors);
+    FSN_REQUIRE(c->bn_hidden >= 128 && c->bn_hidden <= 512 && c->bn_hidden % 128 == 0 && (c->bn_layers == 1 || c->bn_layers == 2),
+                "fast stream: bottleneck %d x %d, the step takes 128, 256, 384 or 512 units with 1 or 2 layers", c->bn_hidden,
+                c->bn_layers);
+    return FSN_OK;
+}
+int check_stream(const fsn_fast_cfg* c, int B, int k) {
+    FSN_TRY(check_cfg(c));
+    FSN_REQUIRE(B >= 1 && B <= 4096 && k >= 1 && k <= 4096, "fast stream: batch %d / frames %d out of range", B, k);
+    return FSN_OK;
+}
+
+// ---- packed weights: float offsets into the blob ------------------------------------------------------------------------
+struct Layer {
+    int I, H;
+    size_t off;
+};
+struct Linear {
+    int I, O;  // I: the (padded) input width
+    size_t w, b;
+};
+struct Packed {
+    Linear mel, enc_fc, bn_fc, dec_fc;
+    Layer enc0, enc1, bn[2], dec0, dec1;
+    size_t total;
+};
+Packed packed_layout(const fsn_fast_cfg* c) {
+    Packed p{};
+    size_t off = 0;
+    auto layer = [&](int I, int H) {
+        Layer l{I, H, off};
+        off += fsn_round_up_sz(fsn_lstm_layer_packed_bytes(I, H) / sizeof(float), 64);
+        return l;
+    };
+    auto linear = [&](int I, int O) {
+        Linear l{I, O, 0, 0};
+        const size_t Ip = fsn_round_up(I, 16), Op = fsn_round_up(O, 16);
+        l.w = off;
+        off += fsn_round_up_sz(Op * Ip, 64);
+        l.b = off;
+        off += fsn_round_up_sz(Op, 64);
+        return l;
+    };
+    const int M = c->num_mels, H = c->bn_hidden;
+    p.mel = linear(c->F, M);
+    p.enc0 = layer(M, kEnc0H);
+    p.enc1 = layer(kEnc0H, kEnc1H);
+    p.enc_fc = linear(kEnc1H, M);
+    p.bn[0] = layer(unit_width(c), H);
+    p.bn[1] = c->bn_layers == 2 ? layer(H, H) : Layer{0, 0, 0};
+    p.bn_fc = linear(H, 1);
+    p.dec0 = layer(2 * M, kDecH);
+    p.dec1 = layer(kDecH, kDecH);
+    p.dec_fc = linear(kDecH, 2 * c->F);
+    p.total = off;
+    return p;
+}
+
+// ---- the state blob and the workspace -------------------------------------------------------------------------------------
+struct State {
+    float *enc0_h, *enc0_c, *enc1_h, *enc1_c, *dec0_h, *dec0_c, *dec1_h, *dec1_c, *bn_h[2], *bn_c[2];
+    double *mel_sum, *unit_sum;
+    float *partial, *held;
+};
+State state_carve(Carver& cv, const fsn_fast_cfg* c, int B) {
+    State st{};
+    const size_t Bp = fsn_round_up(B, 16), N = (size_t)B * c->num_mels;
+    st.enc0_h = cv.take<float>(Bp * kEnc0H);
+    st.enc0_c = cv.take<float>(Bp * kEnc0H);
+    st.enc1_h = cv.take<float>(Bp * kEnc1H);
+    st.enc1_c = cv.take<float>(Bp * kEnc1H);
+    st.dec0_h = cv.take<float>(Bp * kDecH);
+    st.dec0_c = cv.take<float>(Bp * kDecH);
+    st.dec1_h = cv.take<float>(Bp * kDecH);
+    st.dec1_c = cv.take<float>(Bp * kDecH);
+    for (int l = 0; l < c->bn_layers; ++l) {
+        st.bn_h[l] = cv.take<float>(N * c->bn_hidden);
+        st.bn_c[l] = cv.take<float>(N * c->bn_hidden);
+    }
+    st.mel_sum = cv.take<double>((size_t)B);
+    st.unit_sum = cv.take<double>(N);
+    st.partial = cv.take<float>(N * unit_width(c));
+    st.held = cv.take<float>(N);
+    return st;
+}
+struct Ws {
+    float *rows, *mel, *enc_in, *gx, *hseq_a, *hseq_b, *enc, *units, *bn_a, *bn_b, *slow, *dec_in, *out;
+};
+// the low-rate frames a call of k steps can complete, whatever its phase
+int max_low_frames(int k, int shrink) { return (k + shrink - 1) / shrink; }
+Ws ws_carve(Carver& cv, const fsn_fast_cfg* c, int B, int k) {
+    Ws w{};
+    const size_t Bp = fsn_round_up(B, 16), Fp = fsn_fpad(c->F), M = c->num_mels, N = (size_t)B * M, kk = k;
+    const size_t low = max_low_frames(k, c->shrink), Wp = fsn_round_up(unit_width(c), 16), H = c->bn_hidden;
+    w.rows = cv.take<float>(kk * Bp * Fp);
+    w.mel = cv.take<float>(kk * Bp * M);
+    w.enc_in = cv.take<float>(kk * Bp * M);
+    const size_t gx_pairs = kk * Bp * 4 * kDecH, gx_bn = low * N * 4 * H;  // the widest input projection of a layer
+    w.gx = cv.take<float>(gx_pairs > gx_bn ? gx_pairs : gx_bn);
+    w.hseq_a = cv.take<float>(kk * Bp * kDecH);
+    w.hseq_b = cv.take<float>(kk * Bp * kDecH);
+    w.enc = cv.take<float>(kk * Bp * M);
+    w.units = cv.take<float>(low * N * Wp);
+    w.bn_a = cv.take<float>(low * N * H);
+    w.bn_b = cv.take<float>(low * N * H);
+    w.slow = cv.take<float>(low * N);
+    w.dec_in = cv.take<float>(kk * Bp * 2 * M);
+    w.out = cv.take<float>(kk * Bp * 2 * c->F);
+    return w;
+}
+
+int pack_linear(const Linear& l, int I, const float* w, const float* b, float* pk, hipStream_t s) {
+    const int Ip = fsn_round_up(l.I, 16), Op = fsn_round_up(l.O, 16);
+    FSN_TRY(fsn_launch_pack(w, pk + l.w, l.O, I, Op, Ip, s));
+    if (b) return fsn_launch_bias_sum(b, nullptr, pk + l.b, l.O, Op, s);
+    if (hipMemsetAsync(pk + l.b, 0, (size_t)Op * sizeof(float), s) != hipSuccess) {
+        fsn_set_error("fast stream pack: clearing a bias failed");
+        return FSN_ERR_LAUNCH;
+    }
+    return FSN_OK;
+}
+// y [rows][l.O] = x [rows][ldx] W^T + b (+ ReLU); rows a multiple of 16
+int run_linear(const Linear& l, const float* pk, const float* x, long ldx, float* y, int rows, bool relu, hipStream_t s) {
+    return fsn_launch_gemm(gemm_a_rows(x, ldx, rows), pk + l.w, gemm_c_rows(y, l.O, rows, l.O, pk + l.b, relu), rows / 16,
+                           fsn_round_up(l.O, 16) / 16, fsn_round_up(l.I, 16) / 16, s);
+}
+// T more steps of one layer on N rows from (h, c), which are updated in place: x [T][N][ldx] -> hseq [T][N][H]
+int run_layer(const Layer& l, const float* pk, const float* x, long ldx, int T, int N, float* hseq, float* h, float* c, float* gx,
+              void* stream) {
+    return fsn_lstm_layer_forward_state(x, ldx, pk + l.off, T, N, l.I, l.H, hseq, h, c, gx,
+                                        fsn_lstm_layer_state_workspace_bytes(T, N, l.H), stream);
+}
+
+}  // namespace
+
+extern "C" size_t fsn_fast_stream_packed_bytes(const fsn_fast_cfg* cfg) {
+    if (check_cfg(cfg) != FSN_OK) return 0;
+    return fsn_round_up_sz(packed_layout(cfg).total * sizeof(float), 256);
+}
+
+extern "C" int fsn_fast_stream_pack(const fsn_fast_cfg* cfg, const fsn_fast_params* w, void* packed, size_t packed_bytes,
+                                    void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_cfg(cfg));
+    FSN_REQUIRE(w && packed, "NULL pointer argument");
+    const bool two = cfg->bn_layers == 2;
+    FSN_REQUIRE(w->mel_w && w->enc0_w_ih && w->enc0_w_hh && w->enc0_b_ih && w->enc0_b_hh && w->enc1_w_ih && w->enc1_w_hh &&
+                    w->enc1_b_ih && w->enc1_b_hh && w->enc1_fc_w && w->enc1_fc_b && w->bn_w_ih_l0 && w->bn_w_hh_l0 && w->bn_b_ih_l0 &&
+                    w->bn_b_hh_l0 && (!two || (w->bn_w_ih_l1 && w->bn_w_hh_l1 && w->bn_b_ih_l1 && w->bn_b_hh_l1)) && w->bn_fc_w &&
+                    w->bn_fc_b && w->dec0_w_ih && w->dec0_w_hh && w->dec0_b_ih && w->dec0_b_hh && w->dec1_w_ih && w->dec1_w_hh &&
+                    w->dec1_b_ih && w->dec1_b_hh && w->dec1_fc_w && w->dec1_fc_b,
+                "fast stream pack: NULL weight tensor");
+    if (packed_bytes < fsn_fast_stream_packed_bytes(cfg)) {
+        fsn_set_error("fast stream pack: buffer too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Packed p = packed_layout(cfg);
+    float* pk = static_cast<float*>(packed);
+    auto layer = [&](const Layer& l, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh) {
+        return fsn_lstm_layer_pack(w_ih, w_hh, b_ih, b_hh, l.I, l.H, pk + l.off, fsn_lstm_layer_packed_bytes(l.I, l.H), stream);
+    };
+    FSN_TRY(pack_linear(p.mel, cfg->F, w->mel_w, nullptr, pk, s));
+    FSN_TRY(layer(p.enc0, w->enc0_w_ih, w->enc0_w_hh, w->enc0_b_ih, w->enc0_b_hh));
+    FSN_TRY(layer(p.enc1, w->enc1_w_ih, w->enc1_w_hh, w->enc1_b_ih, w->enc1_b_hh));
+    FSN_TRY(pack_linear(p.enc_fc, kEnc1H, w->enc1_fc_w, w->enc1_fc_b, pk, s));
+    FSN_TRY(layer(p.bn[0], w->bn_w_ih_l0, w->bn_w_hh_l0, w->bn_b_ih_l0, w->bn_b_hh_l0));
+    if (two) FSN_TRY(layer(p.bn[1], w->bn_w_ih_l1, w->bn_w_hh_l1, w->bn_b_ih_l1, w->bn_b_hh_l1));
+    FSN_TRY(pack_linear(p.bn_fc, cfg->bn_hidden, w->bn_fc_w, w->bn_fc_b, pk, s));
+    FSN_TRY(layer(p.dec0, w->dec0_w_ih, w->dec0_w_hh, w->dec0_b_ih, w->dec0_b_hh));
+    FSN_TRY(layer(p.dec1, w->dec1_w_ih, w->dec1_w_hh, w->dec1_b_ih, w->dec1_b_hh));
+    return pack_linear(p.dec_fc, kDecH, w->dec1_fc_w, w->dec1_fc_b, pk, s);
+}
+
+extern "C" size_t fsn_fast_stream_state_bytes(const fsn_fast_cfg* cfg, int B) {
+    if (check_stream(cfg, B, 1) != FSN_OK) return 0;
+    Carver cv(nullptr);
+    state_carve(cv, cfg, B);
+    return fsn_round_up_sz(cv.off, 256);
+}
+
+extern "C" size_t fsn_fast_stream_workspace_bytes(const fsn_fast_cfg* cfg, int B, int k) {
+    if (check_stream(cfg, B, k) != FSN_OK) return 0;
+    Carver cv(nullptr);
+    ws_carve(cv, cfg, B, k);
+    return fsn_round_up_sz(cv.off, 256);
+}
+
+extern "C" int fsn_debug_fast_stream_state_layout(const fsn_fast_cfg* cfg, int B, long* out, int n) {
+    if (!out || n < 21 || check_stream(cfg, B, 1) != FSN_OK) return -1;
+    char* const base = reinterpret_cast<char*>((uintptr_t)1 << 20);  // never dereferenced: only differences are taken
+    Carver cv(base);
+    const State st = state_carve(cv, cfg, B);
+    const void* fields[16] = {st.enc0_h, st.enc0_c, st.enc1_h, st.enc1_c, st.dec0_h,  st.dec0_c,   st.dec1_h,  st.dec1_c,
+                              st.bn_h[0], st.bn_c[0], st.bn_h[1], st.bn_c[1], st.mel_sum, st.unit_sum, st.partial, st.held};
+    for (int i = 0; i < 16; ++i) out[i] = fields[i] ? (long)(static_cast<const char*>(fields[i]) - base) : -1;
+    out[16] = fsn_round_up(B, 16);
+    out[17] = (long)B * cfg->num_mels;
+    out[18] = kEnc1H;
+    out[19] = unit_width(cfg);
+    out[20] = (long)fsn_round_up_sz(cv.off, 256);
+    return 0;
+}
+
+// The order of a call (DESIGN "Fast FullSubNet as a stream"): the decoder of step t needs the bottleneck's output of a
+// low-rate frame that may complete in this same call, so the bottleneck runs between the encoder and the decoder, on the
+// n_low frames that complete in [steps_done, steps_done + k) - none of them: skipped, the held output serves.
+extern "C" int fsn_fast_stream_step(const fsn_fast_cfg* cfg, const void* packed, void* state, size_t state_bytes, int steps_done,
+                                    const float* mag, int B, int k, float* crm_out, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_stream(cfg, B, k));
+    FSN_REQUIRE(packed && state && mag && crm_out && workspace && steps_done >= 0, "NULL pointer argument / negative step count");
+    FSN_REQUIRE((long)steps_done + k <= 2147483647L, "fast stream: step count beyond 2^31 - 1");
+    if (state_bytes < fsn_fast_stream_state_bytes(cfg, B) || workspace_bytes < fsn_fast_stream_workspace_bytes(cfg, B, k)) {
+        fsn_set_error("fast stream: state / workspace buffer too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int F = cfg->F, Fp = fsn_fpad(F), M = cfg->num_mels, Bp = fsn_round_up(B, 16), N = B * M;
+    const Packed p = packed_layout(cfg);
+    const float* pk = static_cast<const float*>(packed);
+    Carver cs(state), cw(workspace);
+    const State st = state_carve(cs, cfg, B);
+    const Ws w = ws_carve(cw, cfg, B, k);
+    FsnFastStream g{};
+    g.B = B;
+    g.Bp = Bp;
+    g.M = M;
+    g.k = k;
+    g.t0 = steps_done;
+    g.shrink = cfg->shrink;
+    g.n_mel = cfg->mel_neighbors;
+    g.n_enc = cfg->enc_neighbors;
+    g.W = unit_width(cfg);
+    g.Wp = fsn_round_up(g.W, 16);
+    g.Np = N;
+    g.n_low = fsn_fast_stream_low_frames(steps_done, k, cfg->shrink);
+    // 1. [B, 1, F, k] -> rows [k][Bp][Fp], the mel product, the mel norm (model.py:151-160; the caller appends the look-ahead)
+    FSN_TRY(fsn_fast_spec_rows(mag, B, F, k, 0, w.rows, Bp, Fp, stream));
+    FSN_TRY(run_linear(p.mel, pk, w.rows, Fp, w.mel, k * Bp, false, s));
+    FSN_TRY(fsn_launch_fast_stream_mel_norm(w.mel, w.enc_in, st.mel_sum, g, s));
+    // 2. the encoder pair on all k frames
+    FSN_TRY(run_layer(p.enc0, pk, w.enc_in, M, k, Bp, w.hseq_a, st.enc0_h, st.enc0_c, w.gx, stream));
+    FSN_TRY(run_layer(p.enc1, pk, w.hseq_a, kEnc0H, k, Bp, w.hseq_b, st.enc1_h, st.enc1_c, w.gx, stream));
+    FSN_TRY(run_linear(p.enc_fc, pk, w.hseq_b, kEnc1H, w.enc, k * Bp, true, s));
+    // 3. unit windows, block accumulation, the unit norm (model.py:163-178)
+    FSN_TRY(fsn_launch_fast_stream_units(w.mel, w.enc, M, st.partial, st.unit_sum, w.units, g, s));
+    // 4. the bottleneck on the low-rate frames that completed
+    if (g.n_low > 0) {
+        FSN_TRY(run_layer(p.bn[0], pk, w.units, g.Wp, g.n_low, N, w.bn_a, st.bn_h[0], st.bn_c[0], w.gx, stream));
+        const float* top = w.bn_a;
+        if (cfg->bn_layers == 2) {
+            FSN_TRY(run_layer(p.bn[1], pk, w.bn_a, cfg->bn_hidden, g.n_low, N, w.bn_b, st.bn_h[1], st.bn_c[1], w.gx, stream));
+            top = w.bn_b;
+        }
+        FSN_TRY(run_linear(p.bn_fc, pk, top, cfg->bn_hidden, w.slow, g.n_low * N, true, s));
+    }
+    // 5. - 6. the held output joined to the encoder's (model.py:180-190), the decoder pair on all k frames
+    FSN_TRY(fsn_launch_fast_stream_decoder_input(w.enc, M, w.slow, st.held, w.dec_in, g, s));
+    FSN_TRY(run_layer(p.dec0, pk, w.dec_in, 2 * M, k, Bp, w.hseq_a, st.dec0_h, st.dec0_c, w.gx, stream));
+    FSN_TRY(run_layer(p.dec1, pk, w.hseq_a, kDecH, k, Bp, w.hseq_b, st.dec1_h, st.dec1_c, w.gx, stream));
+    FSN_TRY(run_linear(p.dec_fc, pk, w.hseq_b, kDecH, w.out, k * Bp, false, s));
+    // 7. the mask of all k steps (model.py:200-202 without the look-ahead slice)
+    return fsn_fast_mask_out(w.out, 2L * F, k, B, Bp, F, 0, crm_out, stream);
+}

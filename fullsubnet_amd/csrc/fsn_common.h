@@ -548,6 +548,25 @@ int fsn_launch_pack(const float* w, float* wp, int n_out, int k, int n_out_pad, 
 int fsn_launch_bias_sum(const float* a, const float* b, float* out, int n, int n_pad, hipStream_t s);
 int fsn_launch_bias_frag(const float* bias, float* frag, int n, hipStream_t s);
 
+// fast_stream_kernels.hip: the stateful glue of fsn_fast_stream_step, time-major like fast_glue_kernels.hip.  One call
+// advances B streams by k model steps t0 .. t0 + k - 1; n_low low-rate frames complete in it (the steps t % shrink == 0).
+struct FsnFastStream {
+    int B, Bp, M, k, t0, shrink, n_mel, n_enc, W, Wp, Np, n_low;
+};
+static inline int fsn_fast_stream_low_frames(int t0, int k, int shrink) {  // multiples of shrink in [t0, t0 + k)
+    return (t0 + k - 1) / shrink - (t0 > 0 ? (t0 - 1) / shrink : -1);
+}
+// out[t][b] = mel[t][b] / (float(sum of the stream's mel values up to step t0 + t / (M (t0 + t + 1))) + EPSILON); mel_sum [B]
+int fsn_launch_fast_stream_mel_norm(const float* mel, float* out, double* mel_sum, const FsnFastStream& a, hipStream_t s);
+// unit windows of mel and enc, block accumulation from t0's phase (partial [B][M][W]), the unit norm (unit_sum [B M]):
+// the n_low completed frames as units [n_low][Np][Wp]
+int fsn_launch_fast_stream_units(const float* mel, const float* enc, long ld_enc, float* partial, double* unit_sum,
+                                 float* units, const FsnFastStream& a, hipStream_t s);
+// out[t][b] = enc[t][b] | the bottleneck output of low-rate frame (t0 + t) / shrink: slow [n_low][Np] where it completed in
+// this call, held [B][M] otherwise; held becomes the call's last one
+int fsn_launch_fast_stream_decoder_input(const float* enc, long ld_enc, const float* slow, float* held, float* out,
+                                         const FsnFastStream& a, hipStream_t s);
+
 size_t fsn_lstm2_group_bptt_flag_words(int clusters);  // lstm_group_bptt_kernels.hip
 int fsn_lstm2_group_bptt_clusters(int tiles);
 int fsn_launch_lstm2_group_bptt(const float* dh1, const float* whh1T_p, const float* wih1T_p, const float* whh0T_p,

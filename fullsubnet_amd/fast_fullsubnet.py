@@ -11,6 +11,7 @@ f_min=0, f_max=8000, n_stft)``, model.py:57-63), which is not part of the refere
 below restates torchaudio's documented HTK / norm=None triangular filterbank (parity unpinned at
 that boundary); the buffer keeps torchaudio's name ``mel_scale.fb`` so checkpoints load.
 """
+import ctypes
 import math
 
 import torch
@@ -84,6 +85,7 @@ class Model(BaseModel):
         self.noisy_input_num_neighbors = noisy_input_num_neighbors
         self.enc_output_num_neighbors = encoder_output_num_neighbors
         self.norm = self.norm_wrapper(norm_type)
+        self.norm_type, self.num_freqs = norm_type, encoder_input_size  # what StreamingEnhancer asks a model for
         cell = sequence_model
         # the widths below are literals in the reference too (model.py:36-96): 64 mel bands, 257 bins
         self.encoder = nn.Sequential(_lstm_block(cell, 64, 384, 0),                    # F_l2m, part 1
@@ -228,6 +230,40 @@ class Model(BaseModel):
             _lib.check(L.fsn_fast_mask_out_ragged(_lib.dev_ptr(out), out.stride(1), fr.data_ptr(), T, B, Bp, F, la,
                                                   _lib.dev_ptr(mask), st))
         return mask
+
+    # ---- streaming (fsn_fast_stream_step, streaming.StreamingEnhancer) --------------------------------------------------
+    def stream_cfg(self):
+        """``fsn_fast_cfg`` of this model (a norm the step does not take: -1, which the C entry refuses)."""
+        bn = self.bottleneck
+        return _lib.FastCfg(self.num_freqs, self.num_mels, self.shrink_size, self.noisy_input_num_neighbors,
+                            self.enc_output_num_neighbors, bn.hidden_size, bn.num_layers, _lib.NORM_TYPES.get(self.norm_type, -1))
+
+    def stream_packed_weights(self):
+        """The weights as fsn_fast_stream_step takes them (MFMA-fragment copies of the padded layer tensors, one blob),
+        rebuilt only when a parameter or the filterbank changed."""
+        enc0, enc1 = self.encoder
+        dec0, dec1 = self.decoder_lstm
+        blocks = (enc0, enc1, self.bottleneck, dec0, dec1)
+        padded = [b._inference_weights() for b in blocks]  # ((w_ih, w_hh, b_ih, b_hh) per layer, fc); hidden sizes padded to 64
+        w_mel, _ = self.mel_scale.linear_weights()
+        key = (tuple(b._padded_key for b in blocks), self.mel_scale._w_key)
+        cached = getattr(self, "_stream_packed", None)
+        if cached is None or cached[0] != key:
+            L = _lib.lib()
+            cfg = self.stream_cfg()
+            (l_e0, _), (l_e1, fc_e1), (l_bn, fc_bn), (l_d0, _), (l_d1, fc_d1) = padded
+            second = l_bn[1] if len(l_bn) > 1 else (None,) * 4
+            tensors = [w_mel, *l_e0[0], *l_e1[0], *fc_e1, *l_bn[0], *second, *fc_bn, *l_d0[0], *l_d1[0], *fc_d1]
+            prm = _lib.FastParams(*[_lib.dev_ptr(t, n, allow_none=True) for t, n in zip(tensors, _lib.FAST_PARAM_FIELDS)])
+            nbytes = L.fsn_fast_stream_packed_bytes(ctypes.byref(cfg))
+            if nbytes == 0:
+                raise NotImplementedError(L.fsn_last_error().decode())
+            buf = _lib.workspace(nbytes, w_mel.device)
+            _lib.check(L.fsn_fast_stream_pack(ctypes.byref(cfg), ctypes.byref(prm), buf.data_ptr(), buf.numel(),
+                                              _lib.stream_ptr(w_mel.device)))
+            cached = (key, buf)
+            self._stream_packed = cached
+        return cached[1]
 
     def _forward_row_by_row(self, mix_mag, frames):
         """A ragged batch without the glue's ragged form: each row alone, padded back with zero frames."""

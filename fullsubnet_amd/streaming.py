@@ -16,6 +16,10 @@ waiting for their mask (``look_ahead`` frames) and the last enhanced frame (over
 the same kernel as in the offline path, applied to the new frames only; tests/test_gpu_streaming.py checks
 chunked == whole-utterance.  Configurations outside the fused kernels (other hidden sizes, neighbours ...)
 run the same steps from the per-layer stateful entry (``fsn_lstm_layer_forward_state``) and tensor algebra.
+
+A ``fast_fullsubnet.Model`` (built with the cumulative norm) streams the same way: only ``reset`` and ``_model_steps`` differ -
+they hold the state blob of ``fsn_fast_stream_step`` ((h, c) of the five blocks, both norms' sums, the open down-sampling
+block's sum, the held bottleneck output) and call that entry; tests/test_gpu_fast_stream.py checks chunked == whole-utterance.
 """
 import ctypes
 
@@ -99,6 +103,11 @@ class StreamingEnhancer:
                              "(fullsubnet/train_cumulativeLaplaceNorm.toml)")
         if hop_length * 2 != n_fft:
             raise NotImplementedError("streaming overlap-add is written for hop = n_fft / 2 (every FullSubNet TOML)")
+        # Fast FullSubNet: its own state blob and C entry (fsn_fast_stream_step); everything around the model step is shared
+        from .fast_fullsubnet import Model as FastModel
+        self._fast = isinstance(model, FastModel)
+        if self._fast and any(b.cell != "LSTM" for b in (*model.encoder, model.bottleneck, *model.decoder_lstm)):
+            raise NotImplementedError("streaming Fast FullSubNet is built for LSTM cells (fsn_fast_stream_step)")
         self.model = model.eval()
         self.B = batch_size
         self.n_fft, self.hop = n_fft, hop_length
@@ -115,7 +124,14 @@ class StreamingEnhancer:
         self._n_in = 0          # samples received
         self._t_next = 0        # next STFT frame to compute
         self._tau = 0           # model steps done (input frames incl. the look-ahead zeros at the end)
-        if m._fused:  # the whole frame step is one C call (fsn_fullsubnet_stream_step) on one state blob
+        if self._fast:  # (h, c) of the five blocks, both norms' sums, the open block's sum, the held bottleneck output
+            L = _lib.lib()
+            self._fast_cfg = m.stream_cfg()
+            nbytes = L.fsn_fast_stream_state_bytes(ctypes.byref(self._fast_cfg), B)
+            if nbytes == 0:  # a configuration the C entry refuses
+                raise NotImplementedError(L.fsn_last_error().decode())
+            self._state = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        elif m._fused:  # the whole frame step is one C call (fsn_fullsubnet_stream_step) on one state blob
             nbytes = _lib.lib().fsn_fullsubnet_stream_state_bytes(ctypes.byref(m._cfg), B)
             if nbytes == 0:
                 raise _lib.FsnError(_lib.lib().fsn_last_error().decode())
@@ -137,6 +153,17 @@ class StreamingEnhancer:
         """mag [B, F, k] -> compressed cIRM of model steps tau .. tau + k - 1, [B, 2, F, k]."""
         m = self.model
         B, F, k = mag.shape
+        if self._fast:
+            L = _lib.lib()
+            x = mag.contiguous()
+            cfg = ctypes.byref(self._fast_cfg)
+            out = torch.empty((B, 2, F, k), dtype=torch.float32, device=x.device)
+            ws = _lib.workspace(L.fsn_fast_stream_workspace_bytes(cfg, B, k), x.device)
+            _lib.check(L.fsn_fast_stream_step(
+                cfg, m.stream_packed_weights().data_ptr(), self._state.data_ptr(), self._state.numel(), self._tau,
+                _lib.dev_ptr(x, "mag"), B, k, _lib.dev_ptr(out), ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device)))
+            self._tau += k
+            return out
         if m._fused:
             L = _lib.lib()
             x = mag.contiguous()

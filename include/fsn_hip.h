@@ -1087,6 +1087,64 @@ int fsn_gru_bilayer_backward(const float* dh, long lddh, const float* x, long ld
                              size_t workspace_bytes, void* stream);
 unsigned fsn_debug_bilayer_last_step_launches(void);
 
+/* ---- Fast FullSubNet, streaming: the model on k more frames with carried state ---------------------------------------
+ * fsn_fullsubnet_stream_step's contract for recipes/dns_interspeech_2020/fast_fullsubnet/model.py:143-202 under the
+ * cumulative norm (DESIGN "Fast FullSubNet as a stream" derives why every stage is causal).  mag [B, 1, F, k] are the next
+ * k input frames of the model (the caller appends the look_ahead zero frames of model.py:161 at the end of the stream),
+ * steps_done the number of frames passed in before this call, crm_out [B, 2, F, k] the model output of exactly these steps
+ * (step t is the compressed mask of frame t - look_ahead; the caller does the matching, so look_ahead is no field of the
+ * configuration).  `state` (fsn_fast_stream_state_bytes, zero-filled for a new stream) carries (h, c) of encoder.0,
+ * encoder.1, decoder_lstm.0, decoder_lstm.1 (B rows padded to 16) and of the bottleneck's layers (B num_mels rows), the
+ * fp64 running sums of the mel norm [B] and of the unit norm [B num_mels], the fp32 partial sum of the open down-sampling
+ * block [B][num_mels][W] (W = 2 mel_neighbors + 1 + 2 enc_neighbors + 1; added in frame order, divided by `shrink` once
+ * the block is whole, zero while no block is open) and the last bottleneck output [B][num_mels] held for up-sampling.  Any
+ * chunking of the same frames gives the same masks and the same final state bit for bit; a call in which no low-rate
+ * frame completes (no t in [steps_done, steps_done + k) with t % shrink == 0) does not run the bottleneck.
+ * Configuration: F = 257 and num_mels = 64 (the block widths are literals in the reference), shrink >= 1, neighbours
+ * 0 .. 7, bn_hidden 128, 256, 384 or 512 with bn_layers 1 or 2, LSTM cells, norm = FSN_NORM_CUMULATIVE_LAPLACE.
+ * Anything else: FSN_ERR_ARG with fsn_last_error text; the size queries (which need no device) return 0, as they do for B
+ * or k outside 1 .. 4096.
+ * Weights: fsn_fast_stream_pack copies them once into MFMA-fragment order (fsn_fast_stream_packed_bytes).  The tensors of
+ * fsn_fast_params are nn.LSTM / nn.Linear tensors with every hidden size padded to a multiple of 64 (encoder.1: 257 ->
+ * 320 units, zero weights and biases in the padding) and the input widths that follow from it: mel_w [64][F] (the
+ * filterbank transposed); enc0 I 64, H 384; enc1 I 384, H 320, enc1_fc_w [64][320]; bn layer 0 I W, H bn_hidden, layer 1
+ * (bn_layers = 2, else NULL) I = H = bn_hidden, bn_fc_w [1][bn_hidden]; dec0 I 128, H 512; dec1 I 512, H 512, dec1_fc_w
+ * [2 F][512].  A layer is w_ih [4H][I], w_hh [4H][H], b_ih [4H], b_hh [4H].
+ * fsn_debug_fast_stream_state_layout (test hook, no device): out[0..21) (n >= 21): byte offsets of 0 / 1 encoder.0's h, c
+ * [rows][384], 2 / 3 encoder.1's [rows][320], 4 / 5 decoder_lstm.0's [rows][512], 6 / 7 decoder_lstm.1's [rows][512], 8 / 9
+ * the bottleneck's layer 0 h, c [B num_mels][bn_hidden], 10 / 11 its layer 1 (-1 with one layer), 12 the mel norm's sums
+ * [B] doubles, 13 the unit norm's sums [B num_mels] doubles, 14 the open block's partial sum [B][num_mels][W] floats, 15
+ * the held bottleneck output [B][num_mels] floats; 16 the padded row count of 0 - 7, 17 the bottleneck's row count, 18
+ * encoder.1's padded hidden size, 19 W, 20 the size fsn_fast_stream_state_bytes returns.  -1 on bad arguments.
+ * Additive entries (no new FSN_ABI_VERSION; a binding looks them up by name). */
+typedef struct fsn_fast_cfg {
+    int F;              /* STFT bins, 257 */
+    int num_mels;       /* 64 */
+    int shrink;         /* shrink_size >= 1 */
+    int mel_neighbors;  /* noisy_input_num_neighbors */
+    int enc_neighbors;  /* encoder_output_num_neighbors */
+    int bn_hidden;
+    int bn_layers;
+    int norm;           /* FSN_NORM_CUMULATIVE_LAPLACE */
+} fsn_fast_cfg;
+typedef struct fsn_fast_params {
+    const float* mel_w;
+    const float *enc0_w_ih, *enc0_w_hh, *enc0_b_ih, *enc0_b_hh;
+    const float *enc1_w_ih, *enc1_w_hh, *enc1_b_ih, *enc1_b_hh, *enc1_fc_w, *enc1_fc_b;
+    const float *bn_w_ih_l0, *bn_w_hh_l0, *bn_b_ih_l0, *bn_b_hh_l0;
+    const float *bn_w_ih_l1, *bn_w_hh_l1, *bn_b_ih_l1, *bn_b_hh_l1, *bn_fc_w, *bn_fc_b;
+    const float *dec0_w_ih, *dec0_w_hh, *dec0_b_ih, *dec0_b_hh;
+    const float *dec1_w_ih, *dec1_w_hh, *dec1_b_ih, *dec1_b_hh, *dec1_fc_w, *dec1_fc_b;
+} fsn_fast_params;
+size_t fsn_fast_stream_packed_bytes(const fsn_fast_cfg* cfg);
+int fsn_fast_stream_pack(const fsn_fast_cfg* cfg, const fsn_fast_params* w, void* packed, size_t packed_bytes, void* stream);
+size_t fsn_fast_stream_state_bytes(const fsn_fast_cfg* cfg, int B);
+size_t fsn_fast_stream_workspace_bytes(const fsn_fast_cfg* cfg, int B, int k);
+int fsn_fast_stream_step(const fsn_fast_cfg* cfg, const void* packed, void* state, size_t state_bytes, int steps_done,
+                         const float* mag, int B, int k, float* crm_out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int fsn_debug_fast_stream_state_layout(const fsn_fast_cfg* cfg, int B, long* out, int n);
+
 int fsn_profile_num_stages(void);
 const char* fsn_profile_stage_name(int stage);
 int fsn_profile_read(void* stream, float* ms_per_stage, int n);
