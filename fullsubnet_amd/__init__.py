@@ -13,7 +13,7 @@ from .long_form import LongPlan  # noqa: F401
 from .mix import MixBank, MixConfig, MixItem, MixLoader, draw_item, mix_batch  # noqa: F401
 from .model import Model  # noqa: F401
 from .optim import ClipAdam  # noqa: F401
-from .stream_pool import SessionBook, StreamPool  # noqa: F401
+from .stream_pool import SessionBook, StreamPool, fast_pool_order  # noqa: F401
 from .stream_resample import ResampleBook, StreamResampler  # noqa: F401
 from .streaming import StreamingEnhancer  # noqa: F401
 

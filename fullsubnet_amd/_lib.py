@@ -364,6 +364,18 @@ SIGNATURES = {
     "fsn_fast_stream_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _f32p, _c.c_int,
                                         _c.c_int, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "fsn_debug_fast_stream_state_layout": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
+    "fsn_fast_stream_pool_state_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int, _c.c_int]),
+    "fsn_fast_stream_pool_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int, _c.c_int]),
+    "fsn_fast_stream_pool_reset": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int,
+                                              _c.c_void_p]),
+    "fsn_fast_stream_pool_step": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p,
+                                             _c.c_int, _c.c_int, _f32p, _c.c_int, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_fast_stream_pool_analysis": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int,
+                                                 _f32p, _f32p, _c.c_void_p, _c.c_int, _c.c_int, _f32p, _f32p, _c.c_void_p]),
+    "fsn_fast_stream_pool_synthesis": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int,
+                                                  _f32p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _f32p, _f32p,
+                                                  _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_debug_fast_stream_pool_layout": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
     "fsn_profile_num_stages": (_c.c_int, []),
     "fsn_profile_stage_name": (_c.c_char_p, [_c.c_int]),
     "fsn_profile_read": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_float), _c.c_int]),
@@ -376,7 +388,10 @@ ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr", "fsn_resam
                 "fsn_debug_stream_pool_layout", "fsn_lstm_bilayer_forward", "fsn_lstm_bilayer_backward",
                 "fsn_gru_bilayer_forward", "fsn_gru_bilayer_backward", "fsn_debug_bilayer_last_step_launches",
                 "fsn_fast_stream_packed_bytes", "fsn_fast_stream_pack", "fsn_fast_stream_state_bytes",
-                "fsn_fast_stream_workspace_bytes", "fsn_fast_stream_step", "fsn_debug_fast_stream_state_layout")
+                "fsn_fast_stream_workspace_bytes", "fsn_fast_stream_step", "fsn_debug_fast_stream_state_layout",
+                "fsn_fast_stream_pool_state_bytes", "fsn_fast_stream_pool_workspace_bytes", "fsn_fast_stream_pool_reset",
+                "fsn_fast_stream_pool_step", "fsn_fast_stream_pool_analysis", "fsn_fast_stream_pool_synthesis",
+                "fsn_debug_fast_stream_pool_layout")
 
 
 def lib():
@@ -583,6 +598,20 @@ def fast_stream_state_layout(cfg, B):
     if lib().fsn_debug_fast_stream_state_layout(ctypes.byref(cfg), B, buf, len(buf)) != 0:
         raise FsnError("fsn_debug_fast_stream_state_layout: bad arguments")
     return dict(zip(FAST_STREAM_STATE_LAYOUT, list(buf)))
+
+
+FAST_STREAM_POOL_LAYOUT = ("enc0_h", "enc0_c", "enc1_h", "enc1_c", "dec0_h", "dec0_c", "dec1_h", "dec1_c", "bn_h0", "bn_c0", "bn_h1",
+                           "bn_c1", "mel_sum", "unit_sum", "partial", "held", "steps", "in_tail", "ola_tail", "ring_re", "ring_im",
+                           "slot_bytes", "F", "FP", "R", "bn_hidden", "bn_layers", "unit_width")
+
+
+def fast_stream_pool_layout(cfg, look_ahead):
+    """Byte offsets into one record of Fast FullSubNet's streaming pool (-1: a bottleneck layer the configuration does not
+    have), its size and dimensions (fsn_debug_fast_stream_pool_layout)."""
+    buf = (ctypes.c_long * len(FAST_STREAM_POOL_LAYOUT))()
+    if lib().fsn_debug_fast_stream_pool_layout(ctypes.byref(cfg), look_ahead, buf, len(buf)) != 0:
+        raise FsnError("fsn_debug_fast_stream_pool_layout: bad arguments")
+    return dict(zip(FAST_STREAM_POOL_LAYOUT, list(buf)))
 
 
 def profile_read(device=None):

@@ -284,3 +284,207 @@ extern "C" int fsn_fast_stream_step(const fsn_fast_cfg* cfg, const void* packed,
     // 7. the mask of all k steps (model.py:200-202 without the look-ahead slice)
     return fsn_fast_mask_out(w.out, 2L * F, k, B, Bp, F, 0, crm_out, stream);
 }
+
+// ---- streaming pool: the same step over a subset of the slots of a pool, each slot at its own block phase ---------------------
+// State: one record per slot (FsnFastPoolLayout, fsn_common.h).  A window of k consecutive steps holds lo = k / shrink or hi =
+// ceil(k / shrink) multiples of shrink, so every listed slot completes lo or hi low-rate frames; the caller lists the ones
+// that complete hi first (n_long of them), which makes the bottleneck's rows of low-rate frame ordinal lo a prefix of its
+// compact rows: the bottleneck is T = lo on all n 64 rows, then T = 1 on the first n_long 64 rows of the same (h, c) tiles.
+// The launches are sized from n_long on the host; the record's own count decides every piece of arithmetic, and a kernel at
+// the head of the call checks the one against the other (fast_stream_pool_kernels.hip).
+namespace {
+
+FsnFastPoolLayout pool_layout(const fsn_fast_cfg* c, int look_ahead) {
+    return fsn_fast_pool_layout(c->F, c->bn_hidden, c->bn_layers, unit_width(c), look_ahead);
+}
+int check_pool(const fsn_fast_cfg* c, int look_ahead, int capacity) {
+    FSN_TRY(check_cfg(c));
+    FSN_REQUIRE(look_ahead >= 0 && look_ahead <= 64, "fast streaming pool: look_ahead %d out of range [0, 64]", look_ahead);
+    FSN_REQUIRE(capacity >= 1 && capacity <= 4096, "fast streaming pool: capacity %d out of range [1, 4096]", capacity);
+    return FSN_OK;
+}
+int check_pool_call(const fsn_fast_cfg* c, int look_ahead, const void* state, size_t state_bytes, int capacity, const int* slots,
+                    int n) {
+    FSN_TRY(check_pool(c, look_ahead, capacity));
+    FSN_REQUIRE(state && slots, "NULL pointer argument");
+    FSN_REQUIRE(n >= 1 && n <= capacity, "fast streaming pool: %d slots listed, need 1 .. capacity = %d", n, capacity);
+    if (state_bytes < (size_t)capacity * pool_layout(c, look_ahead).slot_bytes) {
+        fsn_set_error("fast streaming pool: state buffer too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    return FSN_OK;
+}
+struct PoolWs {
+    unsigned* status;
+    FsnFastPoolTiles t;
+};
+PoolWs pool_ws_carve(Carver& cv, const fsn_fast_cfg* c, int n) {
+    PoolWs p{};
+    const size_t Bp = fsn_round_up(n, 16), N = (size_t)n * c->num_mels;
+    p.status = cv.take<unsigned>(64);
+    for (int a = 0; a < 8; ++a) p.t.pair[a] = cv.take<float>(Bp * fsn_fast_pair_h(a / 2));
+    for (int l = 0; l < c->bn_layers; ++l)
+        for (int a = 0; a < 2; ++a) p.t.bn[l][a] = cv.take<float>(N * c->bn_hidden);
+    return p;
+}
+// the transform entries are built for the 512 / 256 transform, like fsn_stream_pool_analysis
+int check_pool_fft(const fsn_fast_cfg* c, int n_fft, int hop) {
+    FSN_REQUIRE(n_fft == 512 && hop == 256, "fast streaming pool: only n_fft = 512, hop = 256 is built (got %d/%d)", n_fft, hop);
+    FSN_REQUIRE(c->F == n_fft / 2 + 1, "F %d != n_fft/2+1", c->F);
+    return FSN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t fsn_fast_stream_pool_state_bytes(const fsn_fast_cfg* cfg, int look_ahead, int capacity) {
+    if (check_pool(cfg, look_ahead, capacity) != FSN_OK) return 0;
+    return (size_t)capacity * pool_layout(cfg, look_ahead).slot_bytes;
+}
+
+extern "C" size_t fsn_fast_stream_pool_workspace_bytes(const fsn_fast_cfg* cfg, int n, int k) {
+    if (check_stream(cfg, n, k) != FSN_OK) return 0;
+    Carver cv(nullptr);
+    ws_carve(cv, cfg, n, k);  // sized for hi = ceil(k / shrink) low-rate frames of all rows
+    pool_ws_carve(cv, cfg, n);
+    return fsn_round_up_sz(cv.off, 256);
+}
+
+extern "C" int fsn_fast_stream_pool_reset(const fsn_fast_cfg* cfg, int look_ahead, void* state, size_t state_bytes, int capacity,
+                                          const int* slots, int n, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_pool_call(cfg, look_ahead, state, state_bytes, capacity, slots, n));
+    // the FullSubNet pool's reset kernel: it reads slot_bytes alone
+    return fsn_launch_pool_reset(state, fsn_fast_pool_transform_layout(pool_layout(cfg, look_ahead)), capacity, slots, n,
+                                 static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fsn_fast_stream_pool_step(const fsn_fast_cfg* cfg, int look_ahead, const void* packed, void* state,
+                                         size_t state_bytes, int capacity, const int* slots, int n, int n_long, const float* mag,
+                                         int k, float* crm_out, void* workspace, size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_pool_call(cfg, look_ahead, state, state_bytes, capacity, slots, n));
+    FSN_TRY(check_stream(cfg, n, k));
+    FSN_REQUIRE(packed && mag && crm_out && workspace, "NULL pointer argument");
+    FSN_REQUIRE(n_long >= 0 && n_long <= n, "fast streaming pool: n_long %d outside 0 .. n = %d", n_long, n);
+    FSN_REQUIRE(k % cfg->shrink != 0 || n_long == n,
+                "fast streaming pool: shrink %d divides k = %d, so every slot completes k / shrink frames: n_long must be n = %d (got %d)",
+                cfg->shrink, k, n, n_long);
+    if (workspace_bytes < fsn_fast_stream_pool_workspace_bytes(cfg, n, k)) {
+        fsn_set_error("fast streaming pool: workspace buffer too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int F = cfg->F, Fp = fsn_fpad(F), M = cfg->num_mels, Bp = fsn_round_up(n, 16), N = n * M, H = cfg->bn_hidden;
+    const Packed p = packed_layout(cfg);
+    const float* pk = static_cast<const float*>(packed);
+    Carver cw(workspace);
+    const Ws w = ws_carve(cw, cfg, n, k);
+    const PoolWs pw = pool_ws_carve(cw, cfg, n);
+    const FsnFastPoolTiles& t = pw.t;
+    FsnFastPool g{};
+    g.state = static_cast<char*>(state);
+    g.L = pool_layout(cfg, look_ahead);
+    g.slots = slots;
+    g.status = pw.status;
+    g.capacity = capacity;
+    g.n = n;
+    g.n_long = n_long;
+    g.k = k;
+    g.Bp = Bp;
+    g.Np = N;
+    g.shrink = cfg->shrink;
+    g.n_mel = cfg->mel_neighbors;
+    g.n_enc = cfg->enc_neighbors;
+    g.W = unit_width(cfg);
+    g.Wp = fsn_round_up(g.W, 16);
+    g.lo = k / cfg->shrink;
+    g.hi = max_low_frames(k, cfg->shrink);
+    const int lo = g.lo, extra = g.hi > g.lo ? n_long * M : 0;  // the rows of low-rate frame ordinal lo
+    // 0. the caller's order against the records' own counts -> the status word every record-writing kernel reads
+    FSN_TRY(fsn_launch_fast_pool_check(g, s));
+    // 1. [n, 1, F, k] -> rows [k][Bp][Fp], the mel product, the mel norm with each row's own sum and count
+    FSN_TRY(fsn_fast_spec_rows(mag, n, F, k, 0, w.rows, Bp, Fp, stream));
+    FSN_TRY(run_linear(p.mel, pk, w.rows, Fp, w.mel, k * Bp, false, s));
+    FSN_TRY(fsn_launch_fast_pool_gather_pairs(g, t, s));
+    FSN_TRY(fsn_launch_fast_pool_mel_norm(w.mel, w.enc_in, g, s));
+    // 2. the encoder pair on all k frames
+    FSN_TRY(run_layer(p.enc0, pk, w.enc_in, M, k, Bp, w.hseq_a, t.pair[0], t.pair[1], w.gx, stream));
+    FSN_TRY(run_layer(p.enc1, pk, w.hseq_a, kEnc0H, k, Bp, w.hseq_b, t.pair[2], t.pair[3], w.gx, stream));
+    FSN_TRY(run_linear(p.enc_fc, pk, w.hseq_b, kEnc1H, w.enc, k * Bp, true, s));
+    // 3. unit windows, block accumulation and the unit norm, each row from its own phase
+    FSN_TRY(fsn_launch_fast_pool_units(w.mel, w.enc, M, w.units, g, s));
+    // 4. the bottleneck: lo steps on all rows, one more on the long rows' prefix; none of it when no listed slot is due
+    if (lo > 0 || extra > 0) {
+        const int slots_run = lo > 0 ? n : n_long;
+        FSN_TRY(fsn_launch_fast_pool_gather_bn(g, t, slots_run, s));
+        auto bn_layer = [&](const Layer& l, const float* x, long ldx, float* hseq, float* h, float* c) {
+            if (lo > 0) FSN_TRY(run_layer(l, pk, x, ldx, lo, N, hseq, h, c, w.gx, stream));
+            if (extra > 0)
+                FSN_TRY(run_layer(l, pk, x + (size_t)lo * N * ldx, ldx, 1, extra, hseq + (size_t)lo * N * H, h, c, w.gx, stream));
+            return (int)FSN_OK;
+        };
+        FSN_TRY(bn_layer(p.bn[0], w.units, g.Wp, w.bn_a, t.bn[0][0], t.bn[0][1]));
+        const float* top = w.bn_a;
+        if (cfg->bn_layers == 2) {
+            FSN_TRY(bn_layer(p.bn[1], w.bn_a, H, w.bn_b, t.bn[1][0], t.bn[1][1]));
+            top = w.bn_b;
+        }
+        FSN_TRY(run_linear(p.bn_fc, pk, top, H, w.slow, lo * N + extra, true, s));
+        FSN_TRY(fsn_launch_fast_pool_scatter_bn(g, t, slots_run, s));
+    }
+    // 5. - 6. the held output joined to the encoder's, the decoder pair on all k frames
+    FSN_TRY(fsn_launch_fast_pool_decoder_input(w.enc, M, w.slow, w.dec_in, g, s));
+    FSN_TRY(run_layer(p.dec0, pk, w.dec_in, 2 * M, k, Bp, w.hseq_a, t.pair[4], t.pair[5], w.gx, stream));
+    FSN_TRY(run_layer(p.dec1, pk, w.hseq_a, kDecH, k, Bp, w.hseq_b, t.pair[6], t.pair[7], w.gx, stream));
+    FSN_TRY(run_linear(p.dec_fc, pk, w.hseq_b, kDecH, w.out, k * Bp, false, s));
+    // 7. the mask of all k steps; NaN instead when the order check failed
+    FSN_TRY(fsn_fast_mask_out(w.out, 2L * F, k, n, Bp, F, 0, crm_out, stream));
+    FSN_TRY(fsn_launch_poison_if(g.status, crm_out, (size_t)n * 2 * F * k, s));
+    // last: it advances the listed slots' step counts
+    return fsn_launch_fast_pool_scatter_pairs(g, t, s);
+}
+
+extern "C" int fsn_fast_stream_pool_analysis(const fsn_fast_cfg* cfg, int look_ahead, void* state, size_t state_bytes,
+                                             int capacity, const int* slots, int n, const float* hops, const float* prime,
+                                             const int* frame_no, int n_fft, int hop, const float* window, float* mag,
+                                             void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_pool_call(cfg, look_ahead, state, state_bytes, capacity, slots, n));
+    FSN_TRY(check_pool_fft(cfg, n_fft, hop));
+    FSN_REQUIRE(hops && frame_no && window && mag, "NULL pointer argument");
+    return fsn_launch_pool_analysis(state, fsn_fast_pool_transform_layout(pool_layout(cfg, look_ahead)), capacity, slots, n, hops,
+                                    prime, frame_no, window, mag, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fsn_fast_stream_pool_synthesis(const fsn_fast_cfg* cfg, int look_ahead, void* state, size_t state_bytes,
+                                              int capacity, const int* slots, int n, const float* crm, int k,
+                                              const int* first_frame, const int* tail_samples, int n_fft, int hop,
+                                              const float* window, float* out, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_pool_call(cfg, look_ahead, state, state_bytes, capacity, slots, n));
+    FSN_TRY(check_pool_fft(cfg, n_fft, hop));
+    FSN_REQUIRE(crm && first_frame && tail_samples && window && out && workspace, "NULL pointer argument");
+    FSN_REQUIRE(k >= 1 && k <= 4096, "fast streaming pool: frames %d out of range", k);
+    if (workspace_bytes < (size_t)n * k * n_fft * sizeof(float)) {
+        fsn_set_error("fast streaming pool: synthesis workspace too small (n k n_fft floats)");
+        return FSN_ERR_WORKSPACE;
+    }
+    return fsn_launch_pool_synthesis(state, fsn_fast_pool_transform_layout(pool_layout(cfg, look_ahead)), capacity, slots, n, crm,
+                                     k, first_frame, tail_samples, window, static_cast<float*>(workspace), out,
+                                     static_cast<hipStream_t>(stream));
+}
+
+// test hook (host only): where the fields of one record lie, from the function the entries lay it out with
+extern "C" int fsn_debug_fast_stream_pool_layout(const fsn_fast_cfg* cfg, int look_ahead, long* out, int n) {
+    if (!out || n < 28 || check_pool(cfg, look_ahead, 1) != FSN_OK) return -1;
+    const FsnFastPoolLayout L = pool_layout(cfg, look_ahead);
+    for (int a = 0; a < 8; ++a) out[a] = (long)L.pair[a];
+    for (int l = 0; l < 2; ++l)
+        for (int a = 0; a < 2; ++a) out[8 + 2 * l + a] = l < L.layers ? (long)L.bn[l][a] : -1;
+    const size_t rest[10] = {L.mel_sum, L.unit_sum, L.partial, L.held, L.steps, L.in_tail, L.ola_tail, L.ring_re, L.ring_im, L.slot_bytes};
+    for (int i = 0; i < 10; ++i) out[12 + i] = (long)rest[i];
+    const int dims[6] = {L.F, L.FP, L.R, L.H, L.layers, L.W};
+    for (int i = 0; i < 6; ++i) out[22 + i] = dims[i];
+    return 0;
+}

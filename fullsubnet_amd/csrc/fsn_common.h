@@ -567,6 +567,90 @@ int fsn_launch_fast_stream_units(const float* mel, const float* enc, long ld_enc
 int fsn_launch_fast_stream_decoder_input(const float* enc, long ld_enc, const float* slow, float* held, float* out,
                                          const FsnFastStream& a, hipStream_t s);
 
+// ---- streaming pool for Fast FullSubNet (fsn_fast_stream_pool_*, fast_stream_pool_kernels.hip) -------------------------------
+// `capacity` records of slot_bytes each; all zeros is a fresh slot.  Byte offsets into a record (every array 256-byte
+// aligned, slot_bytes a multiple of 256): what ONE stream of fsn_fast_stream_step carries -
+//   pair[a]          a = 2 layer + (0 h | 1 c), layer = encoder.0 [384], encoder.1 [320], decoder_lstm.0 [512], decoder_lstm.1 [512]
+//   bn[l][0 h | 1 c] the bottleneck's layer l, [64][H]
+//   mel_sum          the mel norm's fp64 sum;  unit_sum  the unit norm's 64 fp64 sums
+//   partial          the open block's sum [64][W];  held  the held bottleneck output [64]
+// - then the slot's own step count and the four transform fields as in FsnPoolLayout.
+__host__ __device__ __forceinline__ int fsn_fast_pair_h(int layer) { return layer == 0 ? 384 : layer == 1 ? 320 : 512; }
+struct FsnFastPoolLayout {
+    size_t pair[8], bn[2][2], mel_sum, unit_sum, partial, held, steps, in_tail, ola_tail, ring_re, ring_im, slot_bytes;
+    int F, FP, R, H, layers, W;
+};
+static inline FsnFastPoolLayout fsn_fast_pool_layout(int F, int bn_hidden, int bn_layers, int W, int look_ahead) {
+    FsnFastPoolLayout L{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        const size_t r = o;
+        o = fsn_round_up_sz(o + bytes, 256);
+        return r;
+    };
+    L.F = F;
+    L.FP = fsn_fpad(F);
+    L.R = look_ahead + 1;
+    L.H = bn_hidden;
+    L.layers = bn_layers;
+    L.W = W;
+    for (int a = 0; a < 8; ++a) L.pair[a] = take((size_t)fsn_fast_pair_h(a / 2) * sizeof(float));
+    for (int l = 0; l < bn_layers; ++l)
+        for (int a = 0; a < 2; ++a) L.bn[l][a] = take((size_t)64 * bn_hidden * sizeof(float));
+    L.mel_sum = take(sizeof(double));
+    L.unit_sum = take(64 * sizeof(double));
+    L.partial = take((size_t)64 * W * sizeof(float));
+    L.held = take(64 * sizeof(float));
+    L.steps = take(sizeof(int));
+    L.in_tail = take(256 * sizeof(float));
+    L.ola_tail = take(256 * sizeof(float));
+    L.ring_re = take((size_t)L.R * L.FP * sizeof(float));
+    L.ring_im = take((size_t)L.R * L.FP * sizeof(float));
+    L.slot_bytes = o;
+    return L;
+}
+// What fft_kernels.hip's pool kernels (and the reset kernel) read of a layout: the transform fields, F, FP, R, slot_bytes
+static inline FsnPoolLayout fsn_fast_pool_transform_layout(const FsnFastPoolLayout& f) {
+    FsnPoolLayout L{};
+    L.in_tail = f.in_tail;
+    L.ola_tail = f.ola_tail;
+    L.ring_re = f.ring_re;
+    L.ring_im = f.ring_im;
+    L.slot_bytes = f.slot_bytes;
+    L.F = f.F;
+    L.FP = f.FP;
+    L.R = f.R;
+    return L;
+}
+// One call on the n listed slots, k steps each from the slot's own count: every slot completes lo = k / shrink or hi =
+// ceil(k / shrink) low-rate frames, and rows [0, n_long) of `slots` are the ones that complete hi (status: raised by the order
+// check when they are not; every kernel that writes a record then leaves it alone).  Tensors are time-major with Bp =
+// round_up(n, 16) rows per step; the bottleneck's rows are n 64 per low-rate frame ordinal (Np), of ordinal lo the first
+// n_long 64.
+struct FsnFastPool {
+    char* state;
+    FsnFastPoolLayout L;
+    const int* slots;
+    unsigned* status;
+    int capacity, n, n_long, k, Bp, Np, shrink, n_mel, n_enc, W, Wp, lo, hi;
+};
+// (h, c) tiles of a call: pair[a] [Bp][fsn_fast_pair_h(a / 2)], bn[l][0 h | 1 c] [Np][H]
+struct FsnFastPoolTiles {
+    float *pair[8], *bn[2][2];
+};
+int fsn_launch_fast_pool_check(const FsnFastPool& a, hipStream_t s);
+int fsn_launch_fast_pool_gather_pairs(const FsnFastPool& a, const FsnFastPoolTiles& t, hipStream_t s);
+// the last launch of a step: it also advances the listed slots' step counts by k
+int fsn_launch_fast_pool_scatter_pairs(const FsnFastPool& a, const FsnFastPoolTiles& t, hipStream_t s);
+// the bottleneck rows of the first `slots_run` listed slots
+int fsn_launch_fast_pool_gather_bn(const FsnFastPool& a, const FsnFastPoolTiles& t, int slots_run, hipStream_t s);
+int fsn_launch_fast_pool_scatter_bn(const FsnFastPool& a, const FsnFastPoolTiles& t, int slots_run, hipStream_t s);
+// the three state-touching stages of fast_stream_kernels.hip with t0 and the state taken from each row's record
+int fsn_launch_fast_pool_mel_norm(const float* mel, float* out, const FsnFastPool& a, hipStream_t s);
+int fsn_launch_fast_pool_units(const float* mel, const float* enc, long ld_enc, float* units, const FsnFastPool& a, hipStream_t s);
+int fsn_launch_fast_pool_decoder_input(const float* enc, long ld_enc, const float* slow, float* out, const FsnFastPool& a,
+                                       hipStream_t s);
+
 size_t fsn_lstm2_group_bptt_flag_words(int clusters);  // lstm_group_bptt_kernels.hip
 int fsn_lstm2_group_bptt_clusters(int tiles);
 int fsn_launch_lstm2_group_bptt(const float* dh1, const float* whh1T_p, const float* wih1T_p, const float* whh0T_p,

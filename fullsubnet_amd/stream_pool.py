@@ -3,7 +3,7 @@
 ``StreamingEnhancer`` runs a fixed batch in lockstep; a server that enhances calls has sessions that arrive and hang up
 at any time, whose hops are not phase-aligned and of which only some have a frame ready on a given 16 ms tick:
 
-    pool = StreamPool(model, capacity=64)      # fused FullSubNet config, norm_type == "cumulative_laplace_norm"
+    pool = StreamPool(model, capacity=64)      # fused FullSubNet config or Fast FullSubNet, norm_type == "cumulative_laplace_norm"
     sid  = pool.open()                         # raises when the pool is full
     pool.push(sid, chunk)                      # 1-D samples, any length >= 0, host or device
     out  = pool.step()                         # {sid: samples}: ONE frame for every session that has one ready
@@ -25,6 +25,11 @@ carry their state (``stream_resample.StreamResampler``), so the model sees, bit 
 utterance; ``close()`` flushes both and trims to ``out_length(n, input_sr, output_sr)`` samples in all.  The conversion adds
 H / u samples of delay each way (0.625 ms at 48 <-> 16 kHz with "scipy", 2 ms with "sharp").  With the default arguments
 no resampler exists and nothing here runs differently.
+
+A ``fast_fullsubnet.Model`` (cumulative norm, LSTM cells) is served the same way through ``fsn_fast_stream_pool_*``: its sessions
+stand at different phases of a down-sampling block, so the bottleneck runs on the rows that are due on a tick.  The entry wants
+those rows listed first (``fast_pool_order``, on a host mirror of the slots' step counts); what differs between the two models
+sits behind one small object (``_FullSubNetCalls`` / ``_FastCalls``), everything else here is shared.
 
 ``SessionBook`` is the host book-keeping (which frame is next, who is ready, model steps versus output frames, the
 look-ahead drop); it makes no device call, so it is tested without a GPU.
@@ -188,15 +193,100 @@ def _check_slots(slots, capacity):
     return ids
 
 
+def fast_pool_order(steps, k, shrink):
+    """The row order ``fsn_fast_stream_pool_step`` asks for.  A slot that has taken t0 steps completes, in k more, as many
+    low-rate frames as [t0, t0 + k) holds multiples of ``shrink``: lo = k // shrink or hi = ceil(k / shrink).  Returns
+    (perm, n_long): the rows that complete hi first, each group in the caller's order (a stable sort), and how many they
+    are - all of them when shrink divides k."""
+    k, s = int(k), int(shrink)
+    if k < 1 or s < 1:
+        raise ValueError(f"fast_pool_order: k {k} and shrink {s} must be >= 1")
+    hi = -(-k // s)
+    long_rows, short_rows = [], []
+    for i, t0 in enumerate(steps):
+        t0 = int(t0)
+        if t0 < 0:
+            raise ValueError(f"fast_pool_order: negative step count {t0}")
+        done = (t0 + k - 1) // s - ((t0 - 1) // s if t0 > 0 else -1)
+        (long_rows if done == hi else short_rows).append(i)
+    return long_rows + short_rows, len(long_rows)
+
+
+class _FullSubNetCalls:
+    """What StreamPool needs of the fused FullSubNet configuration: the cfg, the state size, the packed weights, the four C
+    entries and the row order (any)."""
+
+    def __init__(self, model):
+        if not getattr(model, "_fused", False):
+            raise NotImplementedError("StreamPool runs the fused FullSubNet configuration and Fast FullSubNet only "
+                                      "(model._fused is false: use one StreamingEnhancer per stream for composed configurations)")
+        self.model = model
+        self.head = (ctypes.byref(model._cfg),)  # what every entry takes in front of the state
+        L = _lib.lib()
+        self.analysis, self.synthesis = L.fsn_stream_pool_analysis, L.fsn_stream_pool_synthesis
+        self.step, self.reset = L.fsn_fullsubnet_stream_pool_step, L.fsn_fullsubnet_stream_pool_reset
+
+    def state_bytes(self, capacity):
+        nbytes = _lib.lib().fsn_fullsubnet_stream_pool_state_bytes(*self.head, capacity)
+        if nbytes == 0:
+            raise _lib.FsnError(_lib.lib().fsn_last_error().decode())
+        return nbytes
+
+    def workspace_bytes(self, n, k):
+        return _lib.lib().fsn_fullsubnet_stream_pool_workspace_bytes(*self.head, n, k)
+
+    def packed(self):
+        return self.model.packed_weights()
+
+    def order(self, steps, k):
+        return None  # rows in any order
+
+    def rows(self, n, n_long):
+        return (n,)
+
+
+class _FastCalls:
+    """... of a ``fast_fullsubnet.Model``: ``fsn_fast_stream_pool_*``, which take the look-ahead beside the cfg and want the
+    rows that complete the larger number of low-rate frames first (``fast_pool_order``)."""
+
+    def __init__(self, model):
+        if any(b.cell != "LSTM" for b in (*model.encoder, model.bottleneck, *model.decoder_lstm)):
+            raise NotImplementedError("StreamPool runs Fast FullSubNet with LSTM cells (fsn_fast_stream_pool_step)")
+        self.model = model
+        self._cfg = model.stream_cfg()
+        self.shrink = int(model.shrink_size)
+        self.head = (ctypes.byref(self._cfg), int(model.look_ahead))
+        L = _lib.lib()
+        self.analysis, self.synthesis = L.fsn_fast_stream_pool_analysis, L.fsn_fast_stream_pool_synthesis
+        self.step, self.reset = L.fsn_fast_stream_pool_step, L.fsn_fast_stream_pool_reset
+
+    def state_bytes(self, capacity):
+        nbytes = _lib.lib().fsn_fast_stream_pool_state_bytes(*self.head, capacity)
+        if nbytes == 0:  # a configuration (or a capacity) the C entry refuses
+            raise NotImplementedError(_lib.lib().fsn_last_error().decode())
+        return nbytes
+
+    def workspace_bytes(self, n, k):
+        return _lib.lib().fsn_fast_stream_pool_workspace_bytes(self.head[0], n, k)
+
+    def packed(self):
+        return self.model.stream_packed_weights()
+
+    def order(self, steps, k):
+        return fast_pool_order(steps, k, self.shrink)
+
+    def rows(self, n, n_long):
+        return (n, n_long)
+
+
 class StreamPool:
     def __init__(self, model, capacity=64, poison_buffers=False, input_sr=None, output_sr="model", resample_design="scipy",
                  record_model_rate=False):
-        if not getattr(model, "_fused", False):
-            raise NotImplementedError("StreamPool runs the fused FullSubNet configuration only (model._fused is false: "
-                                      "use one StreamingEnhancer per stream for composed configurations)")
-        if model.norm_type != "cumulative_laplace_norm":
+        from .fast_fullsubnet import Model as FastModel
+        if model.norm_type != "cumulative_laplace_norm" and (isinstance(model, FastModel) or getattr(model, "_fused", False)):
             raise ValueError("streaming needs a causal norm: build the model with norm_type = 'cumulative_laplace_norm' "
                              "(fullsubnet/train_cumulativeLaplaceNorm.toml)")
+        self._calls = _FastCalls(model) if isinstance(model, FastModel) else _FullSubNetCalls(model)
         self.model = model.eval()
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
@@ -204,12 +294,10 @@ class StreamPool:
         if model.num_freqs != N_FFT // 2 + 1:
             raise NotImplementedError(f"StreamPool is built for the 512 / 256 transform (num_freqs 257, got {model.num_freqs})")
         self.capacity = int(capacity)
-        self._cfg = model._cfg
-        nbytes = _lib.lib().fsn_fullsubnet_stream_pool_state_bytes(ctypes.byref(self._cfg), self.capacity)
-        if nbytes == 0:
-            raise _lib.FsnError(_lib.lib().fsn_last_error().decode())
+        nbytes = self._calls.state_bytes(self.capacity)
         self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self.slot_bytes = nbytes // self.capacity
+        self._steps = [0] * self.capacity  # host mirror of the slots' step counts: model_step advances, reset_slots clears
         self.book = SessionBook(self.capacity, model.look_ahead)
         self._window = torch.hann_window(N_FFT, device=self.device)
         self.poison_buffers = bool(poison_buffers)  # debugging: NaN-fill every workspace and output before its call
@@ -243,38 +331,49 @@ class StreamPool:
         return torch.tensor(rows, dtype=torch.int32, device=self.device)
 
     def _state_args(self):
-        return ctypes.byref(self._cfg), self.state.data_ptr(), self.state.numel(), self.capacity
+        return (*self._calls.head, self.state.data_ptr(), self.state.numel(), self.capacity)
 
     def analysis(self, slots_dev, n, hops, prime, frame_no_dev):
         """hops [n, hop] (and prime [n, hop] = samples 1 .. hop of the sessions at frame 0, or None) -> mag [n, 1, F, 1]."""
         mag = torch.empty((n, 1, self.model.num_freqs, 1), dtype=torch.float32, device=self.device)
         if self.poison_buffers:
             mag.fill_(float("nan"))
-        _lib.check(_lib.lib().fsn_stream_pool_analysis(
+        _lib.check(self._calls.analysis(
             *self._state_args(), slots_dev.data_ptr(), n, _lib.dev_ptr(hops, "hops"),
             _lib.dev_ptr(prime, "prime", allow_none=True), frame_no_dev.data_ptr(), N_FFT, HOP, _lib.dev_ptr(self._window),
             _lib.dev_ptr(mag), _lib.stream_ptr(self.device)))
         return mag
 
     def model_step(self, slots, mag, slots_dev=None):
-        """Advance the listed slots (distinct ids in [0, capacity)) by the k frames of mag [n, 1, F, k], each from its
-        own step count -> compressed cIRM [n, 2, F, k]."""
+        """Advance the listed slots (distinct ids in [0, capacity), any order) by the k frames of mag [n, 1, F, k], each
+        from its own step count -> compressed cIRM [n, 2, F, k], rows in the caller's order."""
         ids = _check_slots(slots, self.capacity)
         n, k = len(ids), mag.shape[-1]
         if tuple(mag.shape) != (n, 1, self.model.num_freqs, k) or k < 1:
             raise ValueError(f"mag {tuple(mag.shape)}: need [{n}, 1, {self.model.num_freqs}, k >= 1]")
+        # Fast FullSubNet: the rows that complete the larger number of low-rate frames go first (a stable sort on the host
+        # mirror of the counts); the rows come back in the caller's order
+        order, perm, n_long = self._calls.order([self._steps[i] for i in ids], k), None, n
+        if order is not None:
+            n_long = order[1]
+            if order[0] != list(range(n)):
+                perm = torch.tensor(order[0], dtype=torch.long, device=self.device)
+                mag, slots_dev = mag.index_select(0, perm), self._ints([ids[i] for i in order[0]])
         if slots_dev is None:
             slots_dev = self._ints(ids)
-        L = _lib.lib()
         crm = torch.empty((n, 2, self.model.num_freqs, k), dtype=torch.float32, device=self.device)
-        ws = _lib.workspace(L.fsn_fullsubnet_stream_pool_workspace_bytes(ctypes.byref(self._cfg), n, k), self.device)
+        ws = _lib.workspace(self._calls.workspace_bytes(n, k), self.device)
         if self.poison_buffers:
             ws.view(torch.float32).fill_(float("nan"))
             crm.fill_(float("nan"))
-        _lib.check(L.fsn_fullsubnet_stream_pool_step(
-            ctypes.byref(self._cfg), self.model.packed_weights().data_ptr(), self.state.data_ptr(), self.state.numel(),
-            self.capacity, slots_dev.data_ptr(), n, _lib.dev_ptr(mag.contiguous(), "mag"), k, _lib.dev_ptr(crm),
-            ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device)))
+        _lib.check(self._calls.step(
+            *self._calls.head, self._calls.packed().data_ptr(), self.state.data_ptr(), self.state.numel(),
+            self.capacity, slots_dev.data_ptr(), *self._calls.rows(n, n_long), _lib.dev_ptr(mag.contiguous(), "mag"), k,
+            _lib.dev_ptr(crm), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device)))
+        for i in ids:
+            self._steps[i] += k
+        if perm is not None:
+            crm = torch.empty_like(crm).index_copy_(0, perm, crm)
         return crm
 
     def synthesis(self, slots_dev, n, crm, first_frame_dev, tail_dev):
@@ -285,7 +384,7 @@ class StreamPool:
         if self.poison_buffers:
             ws.view(torch.float32).fill_(float("nan"))
             out.fill_(float("nan"))
-        _lib.check(_lib.lib().fsn_stream_pool_synthesis(
+        _lib.check(self._calls.synthesis(
             *self._state_args(), slots_dev.data_ptr(), n, _lib.dev_ptr(crm, "crm"), k, first_frame_dev.data_ptr(),
             tail_dev.data_ptr(), N_FFT, HOP, _lib.dev_ptr(self._window), _lib.dev_ptr(out), ws.data_ptr(), ws.numel(),
             _lib.stream_ptr(self.device)))
@@ -293,8 +392,9 @@ class StreamPool:
 
     def reset_slots(self, slots):
         ids = _check_slots(slots, self.capacity)
-        _lib.check(_lib.lib().fsn_fullsubnet_stream_pool_reset(*self._state_args(), self._ints(ids).data_ptr(), len(ids),
-                                                               _lib.stream_ptr(self.device)))
+        _lib.check(self._calls.reset(*self._state_args(), self._ints(ids).data_ptr(), len(ids), _lib.stream_ptr(self.device)))
+        for i in ids:
+            self._steps[i] = 0
 
     # ---- sessions -----------------------------------------------------------------------------
     def open(self):
@@ -375,6 +475,9 @@ class StreamPool:
     def _tick(self, sids):
         """One frame of each listed session (all have one complete): {sid: samples}."""
         n = len(sids)
+        order = self._calls.order([self._steps[self.book.slot(sid)] for sid in sids], 1)
+        if order is not None:  # Fast FullSubNet: list the sessions in the order the model step wants, so that it moves no rows
+            sids = [sids[i] for i in order[0]]
         hops, primes, rows = [], [], [[], [], [], []]  # slots, frame numbers, first output frames, tail samples
         counts, any_first = [], False
         for sid in sids:

@@ -1145,6 +1145,57 @@ int fsn_fast_stream_step(const fsn_fast_cfg* cfg, const void* packed, void* stat
                          void* stream);
 int fsn_debug_fast_stream_state_layout(const fsn_fast_cfg* cfg, int B, long* out, int n);
 
+/* ---- Fast FullSubNet, streaming pool: sessions at their own block phases ------------------------------------------------
+ * fsn_fast_stream_step for streams that are NOT in lockstep, as fsn_fullsubnet_stream_pool_step is for FullSubNet.  `state`
+ * is a pool of `capacity` slots (1 .. 4096), fsn_fast_stream_pool_state_bytes(cfg, look_ahead, capacity) bytes = capacity
+ * equal records, slot s at byte s * (state_bytes / capacity), each 256-byte aligned.  A record holds what ONE stream of
+ * fsn_fast_stream_step carries ((h, c) of the five blocks, both norms' fp64 sums, the open block's partial sum, the held
+ * bottleneck output), the slot's own step count (on the device: the kernels read and advance it) and the transform state of
+ * the two transform entries (look_ahead, 0 .. 64, sizes its ring of spectra; fsn_fast_cfg has no such field).  All zeros is
+ * a fresh pool; fsn_fast_stream_pool_reset returns the n listed slots to that state (stream-ordered).
+ *
+ * fsn_fast_stream_pool_step advances the n listed slots (`slots`: device memory, n DISTINCT ids, 1 <= n <= capacity) by k
+ * model steps, each from its own step count: row i of mag [n, 1, F, k] and crm_out [n, 2, F, k] belongs to slots[i] and is
+ * what fsn_fast_stream_step gives a batch of one with the same history (to the rounding of the recurrent kernels, which
+ * are chosen by the call's row count; the same calls on a fresh pool give the same bits).  A window of k steps holds lo =
+ * k / shrink or hi = ceil(k / shrink) multiples of shrink, so a slot completes lo or hi low-rate frames, as its count
+ * decides.  ORDER: the slots that complete hi frames come first and n_long says how many they are (all n when shrink
+ * divides k: anything else is refused); the bottleneck then runs lo steps on all rows and one more on the first n_long 64.
+ * With lo == 0 and n_long == 0 it does not run and no bottleneck field of a listed record is written.  The call checks the
+ * order on the device against the records' own counts: on a mismatch (or a count that would pass 2^31 - 1) crm_out is all
+ * NaN, the stream's status record is raised (fsn_stream_status; fsn_stream_status_clear), the return value is still FSN_OK
+ * - the host does not wait for the device - and the listed records are unspecified: a caller's error, like a repeated id.
+ * Nothing is read or written outside the blob and the workspace either way.  Slots that are not listed are not written.
+ * A row whose id is outside [0, capacity) is skipped on either side of n_long (its crm_out row is finite, no state is
+ * touched).  FSN_ERR_ARG: what fsn_fast_stream_step refuses (configuration; n, k outside 1 .. 4096), capacity outside
+ * 1 .. 4096, n outside 1 .. capacity, n_long outside 0 .. n, look_ahead outside 0 .. 64; the size queries need no device and
+ * return 0 then.
+ *
+ * fsn_fast_stream_pool_analysis / _synthesis: fsn_stream_pool_analysis / _synthesis (same arguments, same kernels) on the
+ * transform fields of these records.
+ *
+ * fsn_debug_fast_stream_pool_layout (test hook, no device): out[0..28) (n >= 28): byte offsets into a record of 0 - 7 h, c
+ * of encoder.0 [384], encoder.1 [320], decoder_lstm.0 [512], decoder_lstm.1 [512]; 8 - 11 h, c of the bottleneck's layer 0
+ * and 1 [64][bn_hidden] (-1: no such layer); 12 the mel norm's sum (double), 13 the unit norm's sums [64] doubles, 14 the
+ * open block's partial sum [64][W], 15 the held output [64], 16 the step count (int), 17 in_tail [256], 18 ola_tail [256],
+ * 19 / 20 ring_re / ring_im [look_ahead + 1][FP]; 21 the record's size; 22 F, 23 FP, 24 look_ahead + 1, 25 bn_hidden, 26
+ * bn_layers, 27 W.  -1 on bad arguments.  Additive entries (no new FSN_ABI_VERSION). */
+size_t fsn_fast_stream_pool_state_bytes(const fsn_fast_cfg* cfg, int look_ahead, int capacity);
+size_t fsn_fast_stream_pool_workspace_bytes(const fsn_fast_cfg* cfg, int n, int k);
+int fsn_fast_stream_pool_reset(const fsn_fast_cfg* cfg, int look_ahead, void* state, size_t state_bytes, int capacity,
+                               const int* slots, int n, void* stream);
+int fsn_fast_stream_pool_step(const fsn_fast_cfg* cfg, int look_ahead, const void* packed, void* state, size_t state_bytes,
+                              int capacity, const int* slots, int n, int n_long, const float* mag, int k, float* crm_out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int fsn_fast_stream_pool_analysis(const fsn_fast_cfg* cfg, int look_ahead, void* state, size_t state_bytes, int capacity,
+                                  const int* slots, int n, const float* hops, const float* prime, const int* frame_no,
+                                  int n_fft, int hop, const float* window, float* mag, void* stream);
+int fsn_fast_stream_pool_synthesis(const fsn_fast_cfg* cfg, int look_ahead, void* state, size_t state_bytes, int capacity,
+                                   const int* slots, int n, const float* crm, int k, const int* first_frame,
+                                   const int* tail_samples, int n_fft, int hop, const float* window, float* out,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+int fsn_debug_fast_stream_pool_layout(const fsn_fast_cfg* cfg, int look_ahead, long* out, int n);
+
 int fsn_profile_num_stages(void);
 const char* fsn_profile_stage_name(int stage);
 int fsn_profile_read(void* stream, float* ms_per_stage, int n);
