@@ -110,6 +110,24 @@ class FastParams(ctypes.Structure):  # fsn_fast_params
     _fields_ = [(n, _f32p) for n in FAST_PARAM_FIELDS]
 
 
+IMPROVED_MAX_SECTIONS = 8  # FSN_IMPROVED_MAX_SECTIONS
+IMPROVED_BLOCK_FIELDS = tuple(f"{n}_l{l}" for l in (0, 1) for n in _LAYER) + ("fc_w", "fc_b")  # one block of fsn_improved_params
+
+
+class ImprovedSection(ctypes.Structure):  # fsn_improved_section
+    _fields_ = [(n, ctypes.c_int) for n in ("lower", "upper", "sb_center", "sb_neighbors", "fb_center", "fb_neighbors")]
+
+
+class ImprovedCfg(ctypes.Structure):  # fsn_improved_cfg
+    _fields_ = [("F", ctypes.c_int), ("fdrc", ctypes.c_float), ("num_sections", ctypes.c_int), ("fb_hidden", ctypes.c_int),
+                ("sb_hidden", ctypes.c_int), ("cell", ctypes.c_int), ("fb_activation", ctypes.c_int),
+                ("sb_activation", ctypes.c_int), ("sec", ImprovedSection * IMPROVED_MAX_SECTIONS)]
+
+
+class ImprovedParams(ctypes.Structure):  # fsn_improved_params
+    _fields_ = [("fb", _f32p * 10), ("sb", (_f32p * 10) * IMPROVED_MAX_SECTIONS)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/fsn_hip.h
 _c = ctypes
 SIGNATURES = {
@@ -376,6 +394,14 @@ SIGNATURES = {
                                                   _f32p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _f32p, _f32p,
                                                   _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "fsn_debug_fast_stream_pool_layout": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
+    "fsn_improved_stream_packed_bytes": (_c.c_size_t, [_c.c_void_p]),
+    "fsn_improved_stream_pack": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_improved_stream_state_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int]),
+    "fsn_improved_stream_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int, _c.c_int]),
+    "fsn_improved_stream_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_long, _f32p, _c.c_int,
+                                            _c.c_int, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_debug_improved_stream_state_layout": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
+    "fsn_debug_improved_stream_form": (_c.c_int, [_c.c_int]),
     "fsn_profile_num_stages": (_c.c_int, []),
     "fsn_profile_stage_name": (_c.c_char_p, [_c.c_int]),
     "fsn_profile_read": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_float), _c.c_int]),
@@ -391,7 +417,10 @@ ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr", "fsn_resam
                 "fsn_fast_stream_workspace_bytes", "fsn_fast_stream_step", "fsn_debug_fast_stream_state_layout",
                 "fsn_fast_stream_pool_state_bytes", "fsn_fast_stream_pool_workspace_bytes", "fsn_fast_stream_pool_reset",
                 "fsn_fast_stream_pool_step", "fsn_fast_stream_pool_analysis", "fsn_fast_stream_pool_synthesis",
-                "fsn_debug_fast_stream_pool_layout")
+                "fsn_debug_fast_stream_pool_layout",
+                "fsn_improved_stream_packed_bytes", "fsn_improved_stream_pack", "fsn_improved_stream_state_bytes",
+                "fsn_improved_stream_workspace_bytes", "fsn_improved_stream_step", "fsn_debug_improved_stream_state_layout",
+                "fsn_debug_improved_stream_form")
 
 
 def lib():
@@ -598,6 +627,18 @@ def fast_stream_state_layout(cfg, B):
     if lib().fsn_debug_fast_stream_state_layout(ctypes.byref(cfg), B, buf, len(buf)) != 0:
         raise FsnError("fsn_debug_fast_stream_state_layout: bad arguments")
     return dict(zip(FAST_STREAM_STATE_LAYOUT, list(buf)))
+
+
+def improved_stream_state_layout(cfg, B):
+    """Byte offsets of the fields of fsn_improved_stream_step's state blob at batch B: ``fb`` [h0, c0, h1, c1], ``sb`` the same
+    per section, ``fb_sum``, ``sb_sum`` [sections][B] and ``steps`` [B]; ``rows`` / ``sb_rows`` the padded row counts and
+    ``bytes`` its size (fsn_debug_improved_stream_state_layout)."""
+    buf = (ctypes.c_long * 50)()
+    if lib().fsn_debug_improved_stream_state_layout(ctypes.byref(cfg), B, buf, len(buf)) != 0:
+        raise FsnError("fsn_debug_improved_stream_state_layout: bad arguments")
+    v, n = list(buf), buf[48]
+    return {"fb": v[0:4], "sb": [v[4 + 4 * i:8 + 4 * i] for i in range(n)], "fb_sum": v[36], "sb_sum": v[37], "steps": v[38],
+            "rows": v[39], "sb_rows": v[40:40 + n], "sections": n, "bytes": v[49]}
 
 
 FAST_STREAM_POOL_LAYOUT = ("enc0_h", "enc0_c", "enc1_h", "enc1_c", "dec0_h", "dec0_c", "dec1_h", "dec1_c", "bn_h0", "bn_c0", "bn_h1",

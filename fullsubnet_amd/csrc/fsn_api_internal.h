@@ -305,3 +305,16 @@ bool lstm2_on_chain(int T, int N, int H);  // two stacked layers of N rows that 
 // dst [T][left][K] (one 2-D copy when the rows are exactly K wide, one per step otherwise); and the inverse.
 int gather_step_rows(float* dst, const float* src, long ld, int T, int N, int row0, int left, int K, hipStream_t s);
 int scatter_step_rows(float* dst, long ld, const float* src, int T, int N, int row0, int left, int K, hipStream_t s);
+// the blob of fsn_lstm_layer_pack: W_ih and W_hh as MFMA fragments, b_ih + b_hh
+struct LayerPacked {
+    size_t wih, whh, bias, total;  // float offsets
+};
+inline LayerPacked layer_packed_layout(int I, int H) {
+    LayerPacked p;
+    const size_t Ipad = fsn_round_up(I, 16);
+    p.wih = 0;
+    p.whh = fsn_round_up_sz(4 * (size_t)H * Ipad, 64);
+    p.bias = p.whh + fsn_round_up_sz(4 * (size_t)H * H, 64);
+    p.total = p.bias + fsn_round_up_sz(4 * (size_t)H, 64);
+    return p;
+}

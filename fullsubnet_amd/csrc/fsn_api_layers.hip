@@ -405,19 +405,8 @@ extern "C" int fsn_lstm2_forward(const float* x, long ldx, const float* w_ih0, c
 
 // Streaming form (frame-by-frame / chunked inference with carried state): T more steps from the state
 // (h, c) [N][H], which is updated in place.  Always on the per-step kernels.  The weights are re-tiled
-// once (fsn_lstm_layer_pack) - a per-frame caller must not pay three pack launches per layer per call.
-struct LayerPacked {
-    size_t wih, whh, bias, total;  // float offsets
-};
-static LayerPacked layer_packed_layout(int I, int H) {
-    LayerPacked p;
-    const size_t Ipad = fsn_round_up(I, 16);
-    p.wih = 0;
-    p.whh = fsn_round_up_sz(4 * (size_t)H * Ipad, 64);
-    p.bias = p.whh + fsn_round_up_sz(4 * (size_t)H * H, 64);
-    p.total = p.bias + fsn_round_up_sz(4 * (size_t)H, 64);
-    return p;
-}
+// once (fsn_lstm_layer_pack; layer_packed_layout in fsn_api_internal.h) - a per-frame caller must not pay three pack
+// launches per layer per call.
 // ---- Improved FullSubNet: the normalised input of one band section, in the LSTM entries' layout ------------------------
 extern "C" size_t fsn_improved_section_input_workspace_bytes(int B, int F) {
     if (B < 1 || F < 2) return 0;

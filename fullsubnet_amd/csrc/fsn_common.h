@@ -567,6 +567,38 @@ int fsn_launch_fast_stream_units(const float* mel, const float* enc, long ld_enc
 int fsn_launch_fast_stream_decoder_input(const float* enc, long ld_enc, const float* slow, float* held, float* out,
                                          const FsnFastStream& a, hipStream_t s);
 
+// improved_stream_kernels.hip: the stateful glue of fsn_improved_stream_step, time-major.  One call advances B streams by k
+// model steps t0 .. t0 + k - 1 on Fm = F - 1 bins (rows of FmP = round_up(Fm, 16) floats).
+struct FsnImprovedSection {
+    int lower, units, sc, sn, fc, fn;  // the band's first bin, its units, centre / neighbours of the noisy and the fb window
+    int W, Np, Ip;                     // sc + 2 sn + fc + 2 fn; the section's padded rows (B units) and columns
+    float* x;                          // [k][Np][Ip]: the section's normalised input
+    const float* o;                    // [k][Np][2 sc]: its output layer's rows
+};
+struct FsnImprovedStream {
+    int B, Bp, F, Fm, FmP, k, sqrt_mode, n;
+    long t0;
+    FsnImprovedSection s[8];
+};
+// (a) comp [k][Bp][FmP] = mag[b][f][t] ** fdrc without the last bin; fb_in = comp / (float(the stream's sum so far /
+// (Fm (t0 + t + 1))) + EPSILON), zero in the padding; fb_sum [B] carries the sum, steps [B] becomes t0 + k
+int fsn_launch_improved_stream_front(const float* mag, float* comp, float* fb_in, double* fb_sum, long* steps,
+                                     const FsnImprovedStream& a, hipStream_t s);
+// (c) every section's windows of comp and fb_out [k][Bp][ld_fb] (reflection at both spectrum ends), divided by the running
+// mean of the section's units x W entries over the frames so far; sb_sum [n][B] carries the sums
+int fsn_launch_improved_stream_sections(const float* comp, const float* fb_out, long ld_fb, double* sb_sum,
+                                        const FsnImprovedStream& a, hipStream_t s);
+// dst[j][0 .. count[j]) = src[j][..] for n <= 8 pairs in one launch: the sections' last h into the state
+struct FsnImprovedKeep {
+    float* dst[8];
+    const float* src[8];
+    long count[8];
+    int n;
+};
+int fsn_launch_improved_stream_keep(const FsnImprovedKeep& a, hipStream_t s);
+// (e) the sections' rows in bin order as the mask [B][2][F][k]; the last bin is zero
+int fsn_launch_improved_stream_mask(float* mask, const FsnImprovedStream& a, hipStream_t s);
+
 // ---- streaming pool for Fast FullSubNet (fsn_fast_stream_pool_*, fast_stream_pool_kernels.hip) -------------------------------
 // `capacity` records of slot_bytes each; all zeros is a fresh slot.  Byte offsets into a record (every array 256-byte
 // aligned, slot_bytes a multiple of 256): what ONE stream of fsn_fast_stream_step carries -
@@ -860,6 +892,19 @@ int fsn_launch_lstm_step_cu(const float* gx, const float* whh_p, const float* h_
 int fsn_launch_lstm_step_train(const float* gx, const float* whh_p, const float* h_prev, float* h_out,
                                const float* c_prev, float* c_out, float* gates_out, long gx_rt0, int row_tiles, int H,
                                int first, hipStream_t s);
+// several independent layers of one hidden size per step launch (lstm_step_multi_kernel): set j is the arguments of
+// fsn_launch_lstm_step for its own rows, which are the launch's row tiles [tile0, tile0 + tiles)
+struct FsnStepSet {
+    const float *gx, *whh_p, *h_prev;
+    float *h_out, *c;
+    long gx_rt0;
+    int tile0, tiles;
+};
+struct FsnStepSets {
+    FsnStepSet s[8];
+    int n;
+};
+int fsn_launch_lstm_step_multi(const FsnStepSets& sets, int H, hipStream_t s);
 // xin == NULL: accumulators start from the precomputed projection gx; otherwise the (K = 2nb+2)
 // input projection of the sub-band model's first layer is computed inside the kernel from xin.
 int fsn_launch_lstm_rec(const float* gx, const FsnSbInput* xin, const float* whh_p, float* hseq, int Tp, int Npad,

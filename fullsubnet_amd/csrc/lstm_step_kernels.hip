@@ -27,11 +27,11 @@ template <int RTS>
 __device__ __forceinline__ void lstm_step_body(const float* __restrict__ gx, const float* __restrict__ whh_p,
                                                const float* __restrict__ h_prev, float* __restrict__ h_out,
                                                const float* c_prev, float* c, float* __restrict__ gates_out,
-                                               long gx_rt0, int row_tiles, int H, int first) {
+                                               long gx_rt0, int row_tiles, int H, int first, int rtile0) {
     __shared__ f32x4 red[4][RTS][4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 15, lq = lane >> 4;
-    const int ug = blockIdx.x, rtile0 = blockIdx.y * RTS;
+    const int ug = blockIdx.x;
     const int KC = H >> 4, CT = 4 * KC;
     f32x4 acc[RTS][4];
 #pragma unroll
@@ -122,7 +122,19 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(const float* __restrict_
                                                         float* __restrict__ h_out, const float* c_prev,
                                                         float* c, float* __restrict__ gates_out, long gx_rt0,
                                                         int row_tiles, int H, int first) {
-    lstm_step_body<RTS>(gx, whh_p, h_prev, h_out, c_prev, c, gates_out, gx_rt0, row_tiles, H, first);
+    lstm_step_body<RTS>(gx, whh_p, h_prev, h_out, c_prev, c, gates_out, gx_rt0, row_tiles, H, first, blockIdx.y * RTS);
+}
+
+// The same step for several weight sets in one launch (fsn_launch_lstm_step_multi): grid.y runs over the row tiles of all
+// sets, each workgroup looks up its set and is lstm_step_kernel<1>'s workgroup of that set's tile.  A row's products are
+// summed in the order of lstm_step_kernel<1 | 2> (the K split over the four waves and the order of the partials do not
+// depend on RTS): the same bits as one launch per set below 64 row tiles.
+__global__ __launch_bounds__(256) void lstm_step_multi_kernel(const FsnStepSets sets, int H) {
+    const int y = blockIdx.y;
+    int j = 0;
+    while (j + 1 < sets.n && y >= sets.s[j + 1].tile0) ++j;
+    const FsnStepSet& q = sets.s[j];
+    lstm_step_body<1>(q.gx, q.whh_p, q.h_prev, q.h_out, q.c, q.c, nullptr, q.gx_rt0, q.tiles, H, 0, y - q.tile0);
 }
 
 // Many rows (the training step's 129 row tiles and more): no split-K at all.  A workgroup takes RW * 4 row
@@ -557,6 +569,26 @@ int fsn_launch_lstm_step(const float* gx, const float* whh_p, const float* h_pre
         return fsn_check_launch("lstm_step1_kernel");
     }
     return fsn_launch_lstm_step_train(gx, whh_p, h_prev, h_out, c, c, nullptr, gx_rt0, row_tiles, H, first, s);
+}
+
+// One step of up to 8 independent layers of the same H, each on its own weights, rows and state: set j owns grid rows
+// [tile0, tile0 + tiles) (tile0 ascending from 0, no gaps) and below 64 tiles each, the regime in which
+// fsn_launch_lstm_step runs lstm_step_kernel - the launch is bit for bit that launch per set.
+int fsn_launch_lstm_step_multi(const FsnStepSets& sets, int H, hipStream_t s) {
+    fsn_trace(FSN_TR_LSTM_STEP);
+    int next = 0;
+    bool ok = H >= 64 && H % 64 == 0 && sets.n >= 1 && sets.n <= 8;
+    for (int j = 0; ok && j < sets.n; ++j) {
+        const FsnStepSet& q = sets.s[j];
+        ok = q.gx && q.whh_p && q.h_prev && q.h_out && q.c && q.gx_rt0 >= 0 && q.tile0 == next && q.tiles >= 1 && q.tiles < 64;
+        next += q.tiles;
+    }
+    if (!ok) {
+        fsn_set_error("lstm_step_multi: 1 .. 8 sets of 1 .. 63 row tiles in order without gaps, H %d a multiple of 64", H);
+        return FSN_ERR_ARG;
+    }
+    hipLaunchKernelGGL(lstm_step_multi_kernel, dim3(H / 16, next), dim3(256), 0, s, sets, H);
+    return fsn_check_launch("lstm_step_multi_kernel");
 }
 
 // One step on row_tiles (a multiple of 4) tiles with the one-workgroup-per-CU kernel; picks the unit groups per

@@ -112,8 +112,15 @@ class SubbandModel(BaseModel):
         self.sb_num_neighbor_freqs = sb_num_neighbor_freqs
         self.fb_num_center_freqs = fb_num_center_freqs
         self.fb_num_neighbor_freqs = fb_num_neighbor_freqs
-        self.norm = self.norm_wrapper(norm_type)
+        # the reference's cumulative norm unpacks four sizes and cannot take a section's 5-D input: its causal form here
+        self.norm = self._cumulative_section_norm if norm_type == "cumulative_laplace_norm" else self.norm_wrapper(norm_type)
         self.norm_type = norm_type
+
+    def _cumulative_section_norm(self, x):
+        """The causal counterpart of the sections' offline norm (one mean per utterance and section over all units and
+        window columns, over the frames so far): [B, N, 1, W, T] through cumulative_laplace_norm as [B, 1, N W, T]."""
+        B, N, C, W, T = x.shape
+        return self.cumulative_laplace_norm(x.reshape(B, 1, N * C * W, T)).reshape(B, N, C, W, T)
 
     @staticmethod
     def _freq_unfold(input, lower_cutoff_freq=0, upper_cutoff_freq=20, num_center_freqs=1, num_neighbor_freqs=15):
@@ -372,12 +379,24 @@ class Model(BaseModel):
                  sb_num_center_freqs=[1, 4, 8], sb_num_neighbor_freqs=[15, 15, 15], fb_num_center_freqs=[1, 4, 8],
                  fb_num_neighbor_freqs=[15, 15, 15], fb_hidden_size=512, sb_hidden_size=384, sequence_model="LSTM",
                  fb_output_activate_function=False, sb_output_activate_function=False,
-                 norm_type="offline_laplace_norm"):
+                 norm_type="offline_laplace_norm", sb_norm_type=None):
+        """``sb_norm_type``: the norm in front of the band sections.  None is the reference's behaviour (model.py:528-537
+        builds the sub-band model without ``norm_type``: the sections always take the offline Laplace norm);
+        "cumulative_laplace_norm" gives them its causal counterpart (``SubbandModel._cumulative_section_norm``), which
+        with ``norm_type`` = "cumulative_laplace_norm" makes the whole model causal (``StreamingEnhancer``).  Norms have no
+        parameters: a checkpoint loads under either."""
         super().__init__()
+        if sb_norm_type not in (None, "offline_laplace_norm", "cumulative_laplace_norm"):
+            raise NotImplementedError(f"sb_norm_type {sb_norm_type!r}: the sections take None (the reference's offline Laplace norm) "
+                                      "or 'cumulative_laplace_norm'")
         self.n_fft = n_fft
         self.hop_length = hop_length
         self.win_length = win_length
         self.fdrc = fdrc
+        self.num_freqs = num_freqs
+        self.look_ahead = 0  # the model has none; code shared with the other models asks
+        self.norm_type = norm_type
+        self.sb_norm_type = sb_norm_type
         self.fb_model = SequenceModel(input_size=num_freqs - 1, output_size=num_freqs - 1, hidden_size=fb_hidden_size,
                                       num_layers=2, bidirectional=False, sequence_model=sequence_model,
                                       output_activate_function=fb_output_activate_function)
@@ -385,8 +404,56 @@ class Model(BaseModel):
                                      sb_num_neighbor_freqs=sb_num_neighbor_freqs,
                                      fb_num_center_freqs=fb_num_center_freqs,
                                      fb_num_neighbor_freqs=fb_num_neighbor_freqs, hidden_size=sb_hidden_size,
-                                     sequence_model=sequence_model, activate_function=sb_output_activate_function)
+                                     sequence_model=sequence_model, activate_function=sb_output_activate_function,
+                                     norm_type=sb_norm_type or "offline_laplace_norm")
         self.norm = self.norm_wrapper(norm_type)
+
+    def stream_cfg(self):
+        """``fsn_improved_cfg`` of this model: hidden sizes as the stateful layer entry runs them (padded to 64); a cell or
+        an output activation the step does not take is passed on as a value the C entry refuses."""
+        from . import _lib
+        from .sequence_model import _round_up
+        sb = self.sb_model
+        Fm = self.fb_model.input_size
+        acts = {None: 0, False: 0, "": 0, "ReLU": 1}
+        cfg = _lib.ImprovedCfg(Fm + 1, float(self.fdrc), len(sb.sb_models), _round_up(self.fb_model.hidden_size, 64),
+                               _round_up(sb.sb_models[0].hidden_size, 64),
+                               0 if all(m.cell == "LSTM" for m in (self.fb_model, *sb.sb_models)) else 1,
+                               acts.get(self.fb_model.output_activate_function, -1),
+                               acts.get(sb.sb_models[0].output_activate_function, -1))
+        for i in range(min(len(sb.sb_models), _lib.IMPROVED_MAX_SECTIONS)):
+            lower, upper = sb._band(i, Fm)
+            cfg.sec[i] = _lib.ImprovedSection(lower, upper, sb.sb_num_center_freqs[i], sb.sb_num_neighbor_freqs[i],
+                                              sb.fb_num_center_freqs[i], sb.fb_num_neighbor_freqs[i])
+        return cfg
+
+    def stream_packed_weights(self):
+        """The weights as fsn_improved_stream_step takes them (MFMA-fragment copies of the padded layer tensors, one blob),
+        rebuilt only when a parameter changed."""
+        import ctypes
+        from . import _lib
+        blocks = (self.fb_model, *self.sb_model.sb_models)
+        padded = [b._inference_weights() for b in blocks]  # ((w_ih, w_hh, b_ih, b_hh) per layer, fc); hidden sizes padded to 64
+        key = tuple(b._padded_key for b in blocks)
+        cached = getattr(self, "_stream_packed", None)
+        if cached is None or cached[0] != key:
+            L = _lib.lib()
+            cfg = self.stream_cfg()
+            nbytes = L.fsn_improved_stream_packed_bytes(ctypes.byref(cfg))
+            if nbytes == 0:
+                raise NotImplementedError(L.fsn_last_error().decode())
+            prm = _lib.ImprovedParams()
+            for j, (layers, fc) in enumerate(padded):
+                dst = prm.fb if j == 0 else prm.sb[j - 1]
+                for n, t in enumerate((*layers[0], *layers[1], *fc)):
+                    dst[n] = _lib.dev_ptr(t, _lib.IMPROVED_BLOCK_FIELDS[n])
+            dev = padded[0][0][0][0].device
+            buf = _lib.workspace(nbytes, dev)
+            _lib.check(L.fsn_improved_stream_pack(ctypes.byref(cfg), ctypes.byref(prm), buf.data_ptr(), buf.numel(),
+                                                  _lib.stream_ptr(dev)))
+            cached = (key, buf)
+            self._stream_packed = cached
+        return cached[1]
 
     def _persistent_chunk(self, B, T):
         """The largest batch <= B whose band sections run as one persistent launch (sequence_model.multi_plan), or None

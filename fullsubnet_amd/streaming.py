@@ -20,6 +20,11 @@ run the same steps from the per-layer stateful entry (``fsn_lstm_layer_forward_s
 A ``fast_fullsubnet.Model`` (built with the cumulative norm) streams the same way: only ``reset`` and ``_model_steps`` differ -
 they hold the state blob of ``fsn_fast_stream_step`` ((h, c) of the five blocks, both norms' sums, the open down-sampling
 block's sum, the held bottleneck output) and call that entry; tests/test_gpu_fast_stream.py checks chunked == whole-utterance.
+
+An ``improved_fullsubnet.Model`` built with ``norm_type`` = ``sb_norm_type`` = "cumulative_laplace_norm" streams through
+``fsn_improved_stream_step`` (state: (h, c) of the full-band layers and of every section's, the full-band norm's sum and one
+sum per section); n_fft / hop come from the model (960 / 480 at 48 kHz) and ``_emit`` multiplies real and imaginary parts by
+the two mask planes, as that model does; tests/test_gpu_improved_stream.py checks chunked == whole-utterance.
 """
 import ctypes
 
@@ -97,7 +102,24 @@ def _new_state(block, batch, device):
 
 
 class StreamingEnhancer:
-    def __init__(self, model, batch_size=1, n_fft=512, hop_length=256):
+    def __init__(self, model, batch_size=1, n_fft=None, hop_length=None):
+        from .improved_fullsubnet import Model as ImprovedModel
+        self._improved = isinstance(model, ImprovedModel)
+        if self._improved:  # the transform is the model's own unless the caller names one
+            for key in ("norm_type", "sb_norm_type"):
+                if getattr(model, key) != "cumulative_laplace_norm":
+                    raise ValueError(f"streaming needs a causal norm in front of the full-band model and of the band sections: "
+                                     f"build the model with {key} = 'cumulative_laplace_norm'")
+            n_fft = model.n_fft if n_fft is None else n_fft
+            hop_length = model.hop_length if hop_length is None else hop_length
+            if n_fft // 2 + 1 != model.num_freqs:
+                raise ValueError(f"n_fft {n_fft} gives {n_fft // 2 + 1} bins, the model is built for {model.num_freqs}")
+            if hop_length * 2 != n_fft or model.win_length != n_fft:
+                raise NotImplementedError(
+                    f"streaming overlap-add is written for hop = n_fft / 2 = win_length / 2 (960 / 480 at 48 kHz), not for "
+                    f"{n_fft} / {hop_length} / {model.win_length}: the model's 16 kHz default of 512 / 128 does not stream")
+        n_fft = 512 if n_fft is None else n_fft
+        hop_length = 256 if hop_length is None else hop_length
         if model.norm_type != "cumulative_laplace_norm":
             raise ValueError("streaming needs a causal norm: build the model with norm_type = 'cumulative_laplace_norm' "
                              "(fullsubnet/train_cumulativeLaplaceNorm.toml)")
@@ -124,7 +146,14 @@ class StreamingEnhancer:
         self._n_in = 0          # samples received
         self._t_next = 0        # next STFT frame to compute
         self._tau = 0           # model steps done (input frames incl. the look-ahead zeros at the end)
-        if self._fast:  # (h, c) of the five blocks, both norms' sums, the open block's sum, the held bottleneck output
+        if self._improved:  # (h, c) of the full-band layers and of every section's, the norms' sums
+            L = _lib.lib()
+            self._improved_cfg = m.stream_cfg()
+            nbytes = L.fsn_improved_stream_state_bytes(ctypes.byref(self._improved_cfg), B)
+            if nbytes == 0:  # a configuration the C entry refuses
+                raise NotImplementedError(L.fsn_last_error().decode())
+            self._state = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        elif self._fast:  # (h, c) of the five blocks, both norms' sums, the open block's sum, the held bottleneck output
             L = _lib.lib()
             self._fast_cfg = m.stream_cfg()
             nbytes = L.fsn_fast_stream_state_bytes(ctypes.byref(self._fast_cfg), B)
@@ -153,6 +182,17 @@ class StreamingEnhancer:
         """mag [B, F, k] -> compressed cIRM of model steps tau .. tau + k - 1, [B, 2, F, k]."""
         m = self.model
         B, F, k = mag.shape
+        if self._improved:  # the mask itself, not a compressed cIRM (``_emit``)
+            L = _lib.lib()
+            x = mag.contiguous()
+            cfg = ctypes.byref(self._improved_cfg)
+            out = torch.empty((B, 2, F, k), dtype=torch.float32, device=x.device)
+            ws = _lib.workspace(L.fsn_improved_stream_workspace_bytes(cfg, B, k), x.device)
+            _lib.check(L.fsn_improved_stream_step(
+                cfg, m.stream_packed_weights().data_ptr(), self._state.data_ptr(), self._state.numel(), self._tau,
+                _lib.dev_ptr(x, "mag"), B, k, _lib.dev_ptr(out), ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device)))
+            self._tau += k
+            return out
         if self._fast:
             L = _lib.lib()
             x = mag.contiguous()
@@ -218,9 +258,12 @@ class StreamingEnhancer:
         re = torch.cat([s[0] for s in self._spec[:k]], dim=-1)
         im = torch.cat([s[1] for s in self._spec[:k]], dim=-1)
         del self._spec[:k]
-        dm = decompress_cIRM(crm.permute(0, 2, 3, 1).contiguous())
-        er = dm[..., 0] * re - dm[..., 1] * im
-        ei = dm[..., 1] * re + dm[..., 0] * im
+        if self._improved:  # improved_fullsubnet/model.py:575-577: no decompression, no complex product
+            er, ei = crm[:, 0] * re, crm[:, 1] * im
+        else:
+            dm = decompress_cIRM(crm.permute(0, 2, 3, 1).contiguous())
+            er = dm[..., 0] * re - dm[..., 1] * im
+            ei = dm[..., 1] * re + dm[..., 0] * im
         y, self._prev = synthesis_slab(er, ei, self._prev, self._m_next, self._n_out, self.n_fft, self.hop, total_length)
         self._m_next += k
         if y is None:

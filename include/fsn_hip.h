@@ -1196,6 +1196,76 @@ int fsn_fast_stream_pool_synthesis(const fsn_fast_cfg* cfg, int look_ahead, void
                                    void* workspace, size_t workspace_bytes, void* stream);
 int fsn_debug_fast_stream_pool_layout(const fsn_fast_cfg* cfg, int look_ahead, long* out, int n);
 
+/* ---- Improved FullSubNet, streaming: the model on k more frames with carried state -----------------------------------
+ * fsn_fullsubnet_stream_step's contract for recipes/dns_interspeech_2020/improved_fullsubnet/model.py:541-591 with the
+ * cumulative norm in front of the full-band model AND in front of every band section (the reference hands its sections
+ * the offline norm whatever norm_type says; DESIGN "Improved FullSubNet as a stream" derives the causal counterpart: the
+ * section input [B, N, 1, W, T] normalised as cumulative_laplace_norm of [B, 1, N W, T], eps = fp32 epsilon).  The model
+ * has no look-ahead.  mag [B][F][k] are the next k frames of |STFT|, steps_done the number of frames passed in before
+ * this call, mask [B][2][F][k] the mask of exactly these frames: the sections' outputs in bin order, the last bin an
+ * exact zero; the caller multiplies real and imaginary parts by mask[:, 0] and mask[:, 1] (model.py:575-577: no
+ * decompression, no complex product).
+ * `state` (fsn_improved_stream_state_bytes, zero-filled for a new stream) carries (h, c) of the two full-band layers
+ * [rows = B padded to 16][fb_hidden], (h, c) of both layers of every section [B units_i padded to 16][sb_hidden], the fp64
+ * running sum of the full-band norm [B], one fp64 running sum per section and stream [sections][B], and the step count
+ * [B] (written by every call as steps_done + k; the argument, kept by the caller, is what the divisors are taken from).
+ * Any chunking of the same frames gives the same mask and the same final state bit for bit.
+ * Configuration: F bins of the transform (the model runs on F - 1 <= 4096 of them), fdrc 0.5 or 1, 2 .. 8 sections that
+ * tile [0, F - 1) in order, each with its centre and neighbour counts for the noisy and for the fb window (the two unit
+ * counts (upper - lower) / centre must be whole and equal; a window sb_center + 2 sb_neighbors + fb_center + 2
+ * fb_neighbors of at most 240 padded columns), hidden sizes that are multiples of 64 (pad with zero weights), cell 0
+ * (LSTM; 1, GRU, is refused), output activations 0 (none) or 1 (ReLU).  Anything else: FSN_ERR_ARG with fsn_last_error
+ * text; the size queries (which need no device) return 0, as they do for B or k outside 1 .. 4096.  A state or workspace
+ * buffer that is too small: FSN_ERR_WORKSPACE, nothing launched.
+ * Weights: fsn_improved_stream_pack copies them once into MFMA-fragment order (fsn_improved_stream_packed_bytes).  A block
+ * of fsn_improved_params is the ten tensors w_ih_l0 [4H][I], w_hh_l0 [4H][H], b_ih_l0, b_hh_l0, w_ih_l1 [4H][H], w_hh_l1,
+ * b_ih_l1, b_hh_l1, fc_w [O][H], fc_b [O] with H the (padded) hidden size: fb I = O = F - 1; section i I = its window,
+ * O = 2 sb_center.
+ * fsn_debug_improved_stream_state_layout (test hook, no device): out[0..50) (n >= 50): byte offsets of 0 - 3 the full-band
+ * h0, c0, h1, c1; 4 + 4 i + (0 .. 3) the same of section i (-1: no such section); 36 the full-band sums, 37 the sections'
+ * sums, 38 the step counts (longs); 39 the full-band row count, 40 + i section i's row count (-1: none), 48 the number of
+ * sections, 49 the size fsn_improved_stream_state_bytes returns.  -1 on bad arguments.
+ * Additive entries (no new FSN_ABI_VERSION; a binding looks them up by name). */
+#define FSN_IMPROVED_MAX_SECTIONS 8
+typedef struct fsn_improved_section {
+    int lower;         /* first bin of the band */
+    int upper;         /* one past its last bin */
+    int sb_center;     /* sb_num_center_freqs[i]: bins a unit predicts */
+    int sb_neighbors;  /* sb_num_neighbor_freqs[i] */
+    int fb_center;     /* fb_num_center_freqs[i] */
+    int fb_neighbors;  /* fb_num_neighbor_freqs[i] */
+} fsn_improved_section;
+typedef struct fsn_improved_cfg {
+    int F;              /* STFT bins, 481 at 48 kHz */
+    float fdrc;         /* 0.5 or 1 */
+    int num_sections;   /* 2 .. 8 */
+    int fb_hidden;      /* padded to a multiple of 64 */
+    int sb_hidden;
+    int cell;           /* 0 LSTM */
+    int fb_activation;  /* 0 none, 1 ReLU */
+    int sb_activation;
+    fsn_improved_section sec[FSN_IMPROVED_MAX_SECTIONS];
+} fsn_improved_cfg;
+typedef struct fsn_improved_params {
+    const float* fb[10];
+    const float* sb[FSN_IMPROVED_MAX_SECTIONS][10];
+} fsn_improved_params;
+size_t fsn_improved_stream_packed_bytes(const fsn_improved_cfg* cfg);
+int fsn_improved_stream_pack(const fsn_improved_cfg* cfg, const fsn_improved_params* w, void* packed, size_t packed_bytes,
+                             void* stream);
+size_t fsn_improved_stream_state_bytes(const fsn_improved_cfg* cfg, int B);
+size_t fsn_improved_stream_workspace_bytes(const fsn_improved_cfg* cfg, int B, int k);
+int fsn_improved_stream_step(const fsn_improved_cfg* cfg, const void* packed, void* state, size_t state_bytes, long steps_done,
+                             const float* mag, int B, int k, float* mask, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int fsn_debug_improved_stream_state_layout(const fsn_improved_cfg* cfg, int B, long* out, int n);
+/* Test hook: how fsn_improved_stream_step runs the sections' blocks.  0 (the default, the faster one as measured): a chain
+ * of stateful layer launches per section, odd sections on the stream record's auxiliary stream beside the even ones.  1:
+ * one step launch per layer and frame over the row tiles of all sections, each tile on its own section's weights (taken
+ * while every section has fewer than 64 row tiles; beyond that the call runs form 0).  Both give the same bits in mask and
+ * state.  0 or 1 selects a form for the whole process, any other value changes nothing; returns the form in use. */
+int fsn_debug_improved_stream_form(int form);
+
 int fsn_profile_num_stages(void);
 const char* fsn_profile_stage_name(int stage);
 int fsn_profile_read(void* stream, float* ms_per_stage, int n);
