@@ -382,6 +382,17 @@ SIGNATURES = {
     "fsn_fast_stream_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _f32p, _c.c_int,
                                         _c.c_int, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "fsn_debug_fast_stream_state_layout": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
+    "fsn_fast_segment_state_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int]),
+    "fsn_fast_segment_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int, _c.c_int]),
+    "fsn_fast_segment_stats": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _f32p, _c.c_int, _c.c_int, _f32p,
+                                          _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_fast_segment_encoder": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _f32p,
+                                            _c.c_int, _c.c_int, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_fast_segment_decoder": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _f32p,
+                                            _f32p, _c.c_int, _c.c_int, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_fast_segment_divisors": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_int, _f32p, _f32p,
+                                             _c.c_void_p]),
+    "fsn_debug_fast_segment_state_layout": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
     "fsn_fast_stream_pool_state_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int, _c.c_int]),
     "fsn_fast_stream_pool_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int, _c.c_int]),
     "fsn_fast_stream_pool_reset": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int,
@@ -418,6 +429,9 @@ ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr", "fsn_resam
                 "fsn_fast_stream_pool_state_bytes", "fsn_fast_stream_pool_workspace_bytes", "fsn_fast_stream_pool_reset",
                 "fsn_fast_stream_pool_step", "fsn_fast_stream_pool_analysis", "fsn_fast_stream_pool_synthesis",
                 "fsn_debug_fast_stream_pool_layout",
+                "fsn_fast_segment_state_bytes", "fsn_fast_segment_workspace_bytes", "fsn_fast_segment_stats",
+                "fsn_fast_segment_encoder", "fsn_fast_segment_decoder", "fsn_fast_segment_divisors",
+                "fsn_debug_fast_segment_state_layout",
                 "fsn_improved_stream_packed_bytes", "fsn_improved_stream_pack", "fsn_improved_stream_state_bytes",
                 "fsn_improved_stream_workspace_bytes", "fsn_improved_stream_step", "fsn_debug_improved_stream_state_layout",
                 "fsn_debug_improved_stream_form")
@@ -627,6 +641,20 @@ def fast_stream_state_layout(cfg, B):
     if lib().fsn_debug_fast_stream_state_layout(ctypes.byref(cfg), B, buf, len(buf)) != 0:
         raise FsnError("fsn_debug_fast_stream_state_layout: bad arguments")
     return dict(zip(FAST_STREAM_STATE_LAYOUT, list(buf)))
+
+
+FAST_SEGMENT_STATE_LAYOUT = FAST_STREAM_STATE_LAYOUT[:16] + ("acc_mel", "acc_unit", "stat_partial", "stream_end", "rows", "bn_rows",
+                                                             "enc1_hidden", "unit_width", "bytes")
+
+
+def fast_segment_state_layout(cfg, B):
+    """Byte offsets of the fields of the fsn_fast_segment_* state blob at batch B: fsn_fast_stream_step's fields, then the two
+    fp64 accumulators and the statistic pass's block sum; ``stream_end`` is where the stream step's fields end
+    (fsn_debug_fast_segment_state_layout)."""
+    buf = (ctypes.c_long * len(FAST_SEGMENT_STATE_LAYOUT))()
+    if lib().fsn_debug_fast_segment_state_layout(ctypes.byref(cfg), B, buf, len(buf)) != 0:
+        raise FsnError("fsn_debug_fast_segment_state_layout: bad arguments")
+    return dict(zip(FAST_SEGMENT_STATE_LAYOUT, list(buf)))
 
 
 def improved_stream_state_layout(cfg, B):

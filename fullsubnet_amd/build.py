@@ -24,6 +24,7 @@ SOURCES = ["fft_kernels.hip", "dft_kernels.hip", "elementwise_kernels.hip", "gem
            "norm_kernels.hip", "section_kernels.hip", "train_glue_kernels.hip", "fast_glue_kernels.hip",
            "stream_pool_kernels.hip", "mix_kernels.hip", "stoi_kernels.hip", "resample_kernels.hip",
            "resample_stream_kernels.hip", "fast_stream_kernels.hip", "fast_stream_pool_kernels.hip",
+           "fast_segment_kernels.hip",
            "improved_stream_kernels.hip",
            "fsn_api.hip", "fsn_api_fast_stream.hip", "fsn_api_improved_stream.hip", "fsn_api_mix.hip", "fsn_api_metrics.hip", "fsn_api_resample.hip", "fsn_api_fullsubnet.hip", "fsn_api_layers.hip", "fsn_api_gru.hip", "fsn_api_birnn.hip", "fsn_api_train.hip"]
 # -ffp-contract=off: elementwise code follows the reference's mul/add rounding sequence; fused

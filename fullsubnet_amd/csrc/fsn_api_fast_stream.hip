@@ -3,6 +3,8 @@
 // is causal).  The recurrences run on the stateful layer entry (fsn_lstm_layer_forward_state on weights packed once by
 // fsn_lstm_layer_pack), the mel product and the output layers on the linear GEMM, the ends on fast_glue_kernels.hip's
 // spec_rows / mask_out with look-ahead 0, and everything that touches the state between them on fast_stream_kernels.hip.
+// The same stages under the offline norm, as three passes over the segments of a recording of any length
+// (fsn_fast_segment_*), follow the step; their state-touching glue is fast_segment_kernels.hip.
 #include "fsn_api_internal.h"
 
 namespace {
@@ -11,9 +13,8 @@ constexpr int kEnc0H = 384, kEnc1H = 320, kDecH = 512;  // the reference's liter
 
 int unit_width(const fsn_fast_cfg* c) { return 2 * c->mel_neighbors + 1 + 2 * c->enc_neighbors + 1; }
 
-int check_cfg(const fsn_fast_cfg* c) {
-    FSN_REQUIRE(c, "NULL configuration");
-    FSN_REQUIRE(c->norm == FSN_NORM_CUMULATIVE_LAPLACE, "streaming needs the causal norm (FSN_NORM_CUMULATIVE_LAPLACE)");
+// what every entry of this file asks of a configuration, whatever its norm
+int check_shape(const fsn_fast_cfg* c) {
     FSN_REQUIRE(c->F == 257 && c->num_mels == 64, "fast stream: F %d / num_mels %d, the step takes 257 / 64 (the reference's block widths)",
                 c->F, c->num_mels);
     FSN_REQUIRE(c->shrink >= 1, "fast stream: shrink %d must be >= 1", c->shrink);
@@ -23,6 +24,11 @@ int check_cfg(const fsn_fast_cfg* c) {
                 "fast stream: bottleneck %d x %d, the step takes 128, 256, 384 or 512 units with 1 or 2 layers", c->bn_hidden,
                 c->bn_layers);
     return FSN_OK;
+}
+int check_cfg(const fsn_fast_cfg* c) {
+    FSN_REQUIRE(c, "NULL configuration");
+    FSN_REQUIRE(c->norm == FSN_NORM_CUMULATIVE_LAPLACE, "streaming needs the causal norm (FSN_NORM_CUMULATIVE_LAPLACE)");
+    return check_shape(c);
 }
 int check_stream(const fsn_fast_cfg* c, int B, int k) {
     FSN_TRY(check_cfg(c));
@@ -283,6 +289,193 @@ extern "C" int fsn_fast_stream_step(const fsn_fast_cfg* cfg, const void* packed,
     FSN_TRY(run_linear(p.dec_fc, pk, w.hseq_b, kDecH, w.out, k * Bp, false, s));
     // 7. the mask of all k steps (model.py:200-202 without the look-ahead slice)
     return fsn_fast_mask_out(w.out, 2L * F, k, B, Bp, F, 0, crm_out, stream);
+}
+
+// ---- recordings of any length under the offline norm: three passes over the segments -------------------------------------
+// include/fsn_hip.h states the contract, DESIGN "Fast FullSubNet: recordings of any length" why three passes.  The state
+// begins with fsn_fast_stream_step's layout: pass 2 carries the encoder pair's (h, c) there, pass 3 the bottleneck's and the
+// decoder pair's, the open block's partial sum and the held output.  Behind it lie the two fp64 accumulators and the block
+// sum of pass 2's statistic, a field of its own, so no field is cleared between the passes.
+namespace {
+
+struct SegState {
+    State st;
+    double *acc_mel, *acc_unit;
+    float* stat_partial;
+};
+SegState seg_state_carve(Carver& cv, const fsn_fast_cfg* c, int B) {
+    SegState g{};
+    g.st = state_carve(cv, c, B);
+    g.acc_mel = cv.take<double>((size_t)B);
+    g.acc_unit = cv.take<double>((size_t)B);
+    g.stat_partial = cv.take<float>((size_t)B * c->num_mels * unit_width(c));
+    return g;
+}
+int check_segment(const fsn_fast_cfg* c, int B, int k) {
+    FSN_REQUIRE(c, "NULL configuration");
+    FSN_REQUIRE(c->norm == FSN_NORM_OFFLINE_LAPLACE,
+                "fast segment: these entries are the offline norm's three passes (FSN_NORM_OFFLINE_LAPLACE); the causal norm "
+                "needs one pass of fsn_fast_stream_step over the same segments");
+    FSN_TRY(check_shape(c));
+    FSN_REQUIRE(B >= 1 && B <= 4096 && k >= 1 && k <= 4096, "fast segment: batch %d / frames %d out of range", B, k);
+    return FSN_OK;
+}
+size_t seg_state_bytes(const fsn_fast_cfg* c, int B) {
+    Carver cv(nullptr);
+    seg_state_carve(cv, c, B);
+    return fsn_round_up_sz(cv.off, 256);
+}
+size_t seg_workspace_bytes(const fsn_fast_cfg* c, int B, int k) {
+    Carver cv(nullptr);
+    ws_carve(cv, c, B, k);  // the stream step's buffers: every pass uses a subset of them
+    return fsn_round_up_sz(cv.off, 256);
+}
+int check_segment_call(const fsn_fast_cfg* c, int B, int k, const void* state, size_t state_bytes, int frames_done,
+                       bool needs_workspace, const void* workspace, size_t workspace_bytes) {
+    FSN_TRY(check_segment(c, B, k));
+    FSN_REQUIRE(state && frames_done >= 0 && (!needs_workspace || workspace), "NULL pointer argument / negative step count");
+    FSN_REQUIRE((long)frames_done + k <= 2147483647L, "fast segment: step count beyond 2^31 - 1");
+    if (state_bytes < seg_state_bytes(c, B) || (needs_workspace && workspace_bytes < seg_workspace_bytes(c, B, k))) {
+        fsn_set_error("fast segment: state / workspace buffer too small");
+        return FSN_ERR_WORKSPACE;
+    }
+    return FSN_OK;
+}
+FsnFastStream seg_geometry(const fsn_fast_cfg* c, int B, int k, int frames_done) {
+    FsnFastStream g{};
+    g.B = B;
+    g.Bp = fsn_round_up(B, 16);
+    g.M = c->num_mels;
+    g.k = k;
+    g.t0 = frames_done;
+    g.shrink = c->shrink;
+    g.n_mel = c->mel_neighbors;
+    g.n_enc = c->enc_neighbors;
+    g.W = unit_width(c);
+    g.Wp = fsn_round_up(g.W, 16);
+    g.Np = B * c->num_mels;
+    g.n_low = fsn_fast_stream_low_frames(frames_done, k, c->shrink);
+    return g;
+}
+
+}  // namespace
+
+extern "C" size_t fsn_fast_segment_state_bytes(const fsn_fast_cfg* cfg, int B) {
+    if (check_segment(cfg, B, 1) != FSN_OK) return 0;
+    return seg_state_bytes(cfg, B);
+}
+
+extern "C" size_t fsn_fast_segment_workspace_bytes(const fsn_fast_cfg* cfg, int B, int k) {
+    if (check_segment(cfg, B, k) != FSN_OK) return 0;
+    return seg_workspace_bytes(cfg, B, k);
+}
+
+extern "C" int fsn_debug_fast_segment_state_layout(const fsn_fast_cfg* cfg, int B, long* out, int n) {
+    if (!out || n < 25 || check_segment(cfg, B, 1) != FSN_OK) return -1;
+    char* const base = reinterpret_cast<char*>((uintptr_t)1 << 20);  // never dereferenced: only differences are taken
+    Carver cv(base);
+    const SegState g = seg_state_carve(cv, cfg, B);
+    const State& st = g.st;
+    const void* fields[19] = {st.enc0_h,  st.enc0_c,  st.enc1_h,  st.enc1_c,  st.dec0_h,  st.dec0_c,   st.dec1_h,
+                              st.dec1_c,  st.bn_h[0], st.bn_c[0], st.bn_h[1], st.bn_c[1], st.mel_sum,  st.unit_sum,
+                              st.partial, st.held,    g.acc_mel,  g.acc_unit, g.stat_partial};
+    for (int i = 0; i < 19; ++i) out[i] = fields[i] ? (long)(static_cast<const char*>(fields[i]) - base) : -1;
+    Carver stream_only(nullptr);
+    state_carve(stream_only, cfg, B);
+    out[19] = (long)stream_only.off;  // where fsn_fast_stream_step's fields end
+    out[20] = fsn_round_up(B, 16);
+    out[21] = (long)B * cfg->num_mels;
+    out[22] = kEnc1H;
+    out[23] = unit_width(cfg);
+    out[24] = (long)fsn_round_up_sz(cv.off, 256);
+    return 0;
+}
+
+// pass 1: the mel spectrum of the segment into the caller's plane, its frames' sums into the accumulator
+extern "C" int fsn_fast_segment_stats(const fsn_fast_cfg* cfg, const void* packed, void* state, size_t state_bytes, const float* mag,
+                                      int B, int k, float* mel_out, void* workspace, size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_segment_call(cfg, B, k, state, state_bytes, 0, true, workspace, workspace_bytes));
+    FSN_REQUIRE(packed && mag && mel_out, "NULL pointer argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int F = cfg->F, Fp = fsn_fpad(F), Bp = fsn_round_up(B, 16);
+    const Packed p = packed_layout(cfg);
+    const float* pk = static_cast<const float*>(packed);
+    Carver cs(state), cw(workspace);
+    const SegState st = seg_state_carve(cs, cfg, B);
+    const Ws w = ws_carve(cw, cfg, B, k);
+    const FsnFastStream g = seg_geometry(cfg, B, k, 0);
+    // rows beyond B and columns beyond F are zeros, so the padding rows of mel_out are
+    FSN_TRY(fsn_fast_spec_rows(mag, B, F, k, 0, w.rows, Bp, Fp, stream));
+    FSN_TRY(run_linear(p.mel, pk, w.rows, Fp, mel_out, k * Bp, false, s));
+    return fsn_launch_fast_segment_mel_stat(mel_out, st.acc_mel, g, s);
+}
+
+// pass 2: the encoder pair on the normalised mel spectrum, and the statistic of the down-sampled unit tensor
+extern "C" int fsn_fast_segment_encoder(const fsn_fast_cfg* cfg, const void* packed, void* state, size_t state_bytes,
+                                        int frames_done, const int* total_frames, const float* mel, int B, int k, float* enc_out,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_segment_call(cfg, B, k, state, state_bytes, frames_done, true, workspace, workspace_bytes));
+    FSN_REQUIRE(packed && total_frames && mel && enc_out, "NULL pointer argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int M = cfg->num_mels, Bp = fsn_round_up(B, 16);
+    const Packed p = packed_layout(cfg);
+    const float* pk = static_cast<const float*>(packed);
+    Carver cs(state), cw(workspace);
+    const SegState g = seg_state_carve(cs, cfg, B);
+    const State& st = g.st;
+    const Ws w = ws_carve(cw, cfg, B, k);
+    const FsnFastStream a = seg_geometry(cfg, B, k, frames_done);
+    FSN_TRY(fsn_launch_fast_segment_mel_norm(mel, w.enc_in, g.acc_mel, total_frames, a, s));
+    FSN_TRY(run_layer(p.enc0, pk, w.enc_in, M, k, Bp, w.hseq_a, st.enc0_h, st.enc0_c, w.gx, stream));
+    FSN_TRY(run_layer(p.enc1, pk, w.hseq_a, kEnc0H, k, Bp, w.hseq_b, st.enc1_h, st.enc1_c, w.gx, stream));
+    FSN_TRY(run_linear(p.enc_fc, pk, w.hseq_b, kEnc1H, enc_out, k * Bp, true, s));
+    return fsn_launch_fast_segment_units(false, mel, enc_out, M, g.stat_partial, g.acc_unit, total_frames, nullptr, a, s);
+}
+
+// pass 3: fsn_fast_stream_step from its stage 3 on, with the one divisor of the finished statistic
+extern "C" int fsn_fast_segment_decoder(const fsn_fast_cfg* cfg, const void* packed, void* state, size_t state_bytes,
+                                        int frames_done, const int* total_frames, const float* mel, const float* enc, int B, int k,
+                                        float* crm_out, void* workspace, size_t workspace_bytes, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_segment_call(cfg, B, k, state, state_bytes, frames_done, true, workspace, workspace_bytes));
+    FSN_REQUIRE(packed && total_frames && mel && enc && crm_out, "NULL pointer argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int F = cfg->F, M = cfg->num_mels, Bp = fsn_round_up(B, 16), N = B * M;
+    const Packed p = packed_layout(cfg);
+    const float* pk = static_cast<const float*>(packed);
+    Carver cs(state), cw(workspace);
+    const SegState g = seg_state_carve(cs, cfg, B);
+    const State& st = g.st;
+    const Ws w = ws_carve(cw, cfg, B, k);
+    const FsnFastStream a = seg_geometry(cfg, B, k, frames_done);
+    FSN_TRY(fsn_launch_fast_segment_units(true, mel, enc, M, st.partial, g.acc_unit, total_frames, w.units, a, s));
+    if (a.n_low > 0) {
+        FSN_TRY(run_layer(p.bn[0], pk, w.units, a.Wp, a.n_low, N, w.bn_a, st.bn_h[0], st.bn_c[0], w.gx, stream));
+        const float* top = w.bn_a;
+        if (cfg->bn_layers == 2) {
+            FSN_TRY(run_layer(p.bn[1], pk, w.bn_a, cfg->bn_hidden, a.n_low, N, w.bn_b, st.bn_h[1], st.bn_c[1], w.gx, stream));
+            top = w.bn_b;
+        }
+        FSN_TRY(run_linear(p.bn_fc, pk, top, cfg->bn_hidden, w.slow, a.n_low * N, true, s));
+    }
+    FSN_TRY(fsn_launch_fast_stream_decoder_input(enc, M, w.slow, st.held, w.dec_in, a, s));
+    FSN_TRY(run_layer(p.dec0, pk, w.dec_in, 2 * M, k, Bp, w.hseq_a, st.dec0_h, st.dec0_c, w.gx, stream));
+    FSN_TRY(run_layer(p.dec1, pk, w.hseq_a, kDecH, k, Bp, w.hseq_b, st.dec1_h, st.dec1_c, w.gx, stream));
+    FSN_TRY(run_linear(p.dec_fc, pk, w.hseq_b, kDecH, w.out, k * Bp, false, s));
+    return fsn_fast_mask_out(w.out, 2L * F, k, B, Bp, F, 0, crm_out, stream);
+}
+
+extern "C" int fsn_fast_segment_divisors(const fsn_fast_cfg* cfg, const void* state, size_t state_bytes, const int* total_frames,
+                                         int B, float* den_mel, float* den_unit, void* stream) {
+    CallScope scope(stream);
+    FSN_TRY(check_segment_call(cfg, B, 1, state, state_bytes, 0, false, nullptr, 0));
+    FSN_REQUIRE(total_frames && den_mel && den_unit, "NULL pointer argument");
+    Carver cs(const_cast<void*>(state));
+    const SegState g = seg_state_carve(cs, cfg, B);
+    return fsn_launch_fast_segment_divisors(g.acc_mel, g.acc_unit, total_frames, den_mel, den_unit, B, cfg->shrink, unit_width(cfg),
+                                            static_cast<hipStream_t>(stream));
 }
 
 // ---- streaming pool: the same step over a subset of the slots of a pool, each slot at its own block phase ---------------------

@@ -567,6 +567,21 @@ int fsn_launch_fast_stream_units(const float* mel, const float* enc, long ld_enc
 int fsn_launch_fast_stream_decoder_input(const float* enc, long ld_enc, const float* slow, float* held, float* out,
                                          const FsnFastStream& a, hipStream_t s);
 
+// fast_segment_kernels.hip: the same glue under the offline norm, for fsn_fast_segment_*.  acc_mel / acc_unit [B]: the fp64
+// accumulators of the two utterance means; total [B] (device): row b's own step count T_b + look_ahead.
+// acc_mel[b] += the 64-band sums of mel [k][Bp][64], frame by frame
+int fsn_launch_fast_segment_mel_stat(const float* mel, double* acc_mel, const FsnFastStream& a, hipStream_t s);
+// out[t][b] = mel[t][b] / (float(acc_mel[b] / (64 total[b])) + 1e-5f), rows beyond B zero
+int fsn_launch_fast_segment_mel_norm(const float* mel, float* out, const double* acc_mel, const int* total, const FsnFastStream& a,
+                                     hipStream_t s);
+// unit windows and block accumulation from t0's phase (partial [B][M][W]).  emit false: every low-rate frame of row b that
+// completes at a step < total[b], its closing short block included, joins acc_unit[b]; units is not touched.  emit true: the
+// n_low whole blocks as units [n_low][Np][Wp], divided by float(acc_unit[b] / (64 W Ts_b)) + 1e-5f
+int fsn_launch_fast_segment_units(bool emit, const float* mel, const float* enc, long ld_enc, float* partial, double* acc_unit,
+                                  const int* total, float* units, const FsnFastStream& a, hipStream_t s);
+int fsn_launch_fast_segment_divisors(const double* acc_mel, const double* acc_unit, const int* total, float* den_mel,
+                                     float* den_unit, int B, int shrink, int W, hipStream_t s);
+
 // improved_stream_kernels.hip: the stateful glue of fsn_improved_stream_step, time-major.  One call advances B streams by k
 // model steps t0 .. t0 + k - 1 on Fm = F - 1 bins (rows of FmP = round_up(Fm, 16) floats).
 struct FsnImprovedSection {

@@ -238,19 +238,23 @@ class Model(BaseModel):
         return _lib.FastCfg(self.num_freqs, self.num_mels, self.shrink_size, self.noisy_input_num_neighbors,
                             self.enc_output_num_neighbors, bn.hidden_size, bn.num_layers, _lib.NORM_TYPES.get(self.norm_type, -1))
 
-    def stream_packed_weights(self):
+    def stream_packed_weights(self, norm=None):
         """The weights as fsn_fast_stream_step takes them (MFMA-fragment copies of the padded layer tensors, one blob),
-        rebuilt only when a parameter or the filterbank changed."""
+        rebuilt only when a parameter or the filterbank changed.  ``norm``: the norm the blob is packed under instead of the
+        model's own (``enhance_long`` of an offline-norm model: the packing entry takes the causal norm only, and the blob's
+        layout does not depend on it)."""
         enc0, enc1 = self.encoder
         dec0, dec1 = self.decoder_lstm
         blocks = (enc0, enc1, self.bottleneck, dec0, dec1)
         padded = [b._inference_weights() for b in blocks]  # ((w_ih, w_hh, b_ih, b_hh) per layer, fc); hidden sizes padded to 64
         w_mel, _ = self.mel_scale.linear_weights()
-        key = (tuple(b._padded_key for b in blocks), self.mel_scale._w_key)
+        key = (tuple(b._padded_key for b in blocks), self.mel_scale._w_key, norm)
         cached = getattr(self, "_stream_packed", None)
         if cached is None or cached[0] != key:
             L = _lib.lib()
             cfg = self.stream_cfg()
+            if norm is not None:
+                cfg.norm = norm
             (l_e0, _), (l_e1, fc_e1), (l_bn, fc_bn), (l_d0, _), (l_d1, fc_d1) = padded
             second = l_bn[1] if len(l_bn) > 1 else (None,) * 4
             tensors = [w_mel, *l_e0[0], *l_e1[0], *fc_e1, *l_bn[0], *second, *fc_bn, *l_d0[0], *l_d1[0], *fc_d1]
@@ -362,3 +366,25 @@ class Model(BaseModel):
             if return_crm:
                 crm[b, :, :, :c.shape[-1]] = c[0]
         return (out, crm) if return_crm else out
+
+    def enhance_long(self, noisy, lengths=None, segment_frames=None, workspace_limit=4 << 30, return_crm=False, poison=False,
+                     n_fft=512, hop_length=256, slab_frames=4096):
+        """``enhance`` for recordings of any length: noisy [B, L] -> enhanced [B, L] (and the compressed mask with
+        ``return_crm``), with the signature and the meaning of FullSubNet's ``Model.enhance_long``.
+
+        ``enhance`` refuses more than 65 535 frames (17.5 minutes at hop 256 / 16 kHz) and its memory grows with the recording
+        at hidden-state width.  Here the model runs in segments of ``segment_frames`` model steps (1 .. 4096; ``None``: the
+        largest whose workspace stays under ``workspace_limit`` bytes) with carried LSTM state.  Under the shipped
+        ``offline_laplace_norm`` that is three passes over the segments (libfsn_hip ``fsn_fast_segment_*``: the model divides
+        by two utterance means, each needed before the next stage starts); under ``cumulative_laplace_norm`` one pass of
+        ``fsn_fast_stream_step``.  The transforms run in slabs of ``slab_frames`` frames.  What grows with the recording are
+        planes of F floats per frame (magnitude, spectrum, mask) and, under the offline norm, two planes of 64 floats per step
+        (mel spectrum, encoder output); ``fast_long_form.FastLongPlan`` lists every allocation without making one.
+
+        ``lengths``: a ragged batch, as in ``enhance``.  The result agrees with ``enhance`` within fp32 rounding (other
+        recurrent kernels), and any two values of ``segment_frames`` give the same mask bit for bit.  ``poison`` (test hook):
+        every buffer starts as NaN.  LSTM cells, n_fft 512 / hop 256 and a model on a ROCm device only: anything else is an
+        ``FsnError`` that names ``Model.enhance``."""
+        from .fast_long_form import enhance_long
+        return enhance_long(self, noisy, lengths, segment_frames, workspace_limit, return_crm, poison, n_fft, hop_length,
+                            slab_frames)

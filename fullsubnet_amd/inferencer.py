@@ -92,7 +92,7 @@ class Inferencer:
             if not hasattr(model, "enhance_long"):
                 from ._lib import FsnError
                 raise FsnError(f"[inferencer] segment_frames: {type(model).__module__}.Model has no enhance_long (FullSubNet's "
-                               "fused configurations only); remove the key for this model")
+                               "fused configurations and Fast FullSubNet have one); remove the key for this model")
             return model.enhance_long(noisy, segment_frames=self.segment_frames, n_fft=self.n_fft,
                                       hop_length=self.hop_length).detach().squeeze(0).cpu().numpy()
         if (self.fused_call and noisy.dim() == 2 and noisy.shape[0] == 1 and getattr(model, "_fused", False)

@@ -1145,6 +1145,66 @@ int fsn_fast_stream_step(const fsn_fast_cfg* cfg, const void* packed, void* stat
                          void* stream);
 int fsn_debug_fast_stream_state_layout(const fsn_fast_cfg* cfg, int B, long* out, int n);
 
+/* ---- Fast FullSubNet, recordings of any length: the model in segments under the offline norm ---------------------------
+ * The fsn_fullsubnet_segment_* contract for Fast FullSubNet with norm = FSN_NORM_OFFLINE_LAPLACE (the shipped norm).  The
+ * one-call path stops at 65 535 frames and its memory grows with the recording at hidden-state width; here the model runs
+ * on k (1 .. 4096) steps at a time.  What lives for the whole recording is the caller's: planes of F floats per frame
+ * (magnitude, mask) and two time-major planes of num_mels floats per step, mel and enc [Tp][Bp][64] (Bp = B rounded up to
+ * 16, Tp = T_max + look_ahead), of which a segment is the contiguous slice [k][Bp][64] at step frames_done.  Everything of
+ * hidden-size width is inside `workspace` (fsn_fast_segment_workspace_bytes(cfg, B, k), one size for all passes).
+ *
+ * offline_laplace_norm divides by ONE mean per utterance and the model applies it twice (model.py:170,187): to the mel
+ * spectrum and to the down-sampled unit tensor.  A recording therefore takes three passes over its segments, each pass in
+ * frame order over the T_max + look_ahead model steps (the caller appends the look_ahead zero frames of model.py:161), one
+ * pass finished before the next begins:
+ *   1. fsn_fast_segment_stats: mag [B, 1, F, k] -> mel_out [k][Bp][64] (the filterbank product, padding rows zero); every
+ *      frame's 64-band sum is added to an fp64 accumulator [B], in frame order.
+ *   2. fsn_fast_segment_encoder: mel / den_mel[b], den_mel[b] = float(sum / (64 total_frames[b])) + 1e-5f, through the
+ *      encoder pair from the carried (h, c) -> enc_out [k][Bp][64].  The unit windows of mel and enc_out are down-sampled
+ *      as a running block sum that continues across segment edges, and every low-rate frame of row b that completes at a
+ *      step t < total_frames[b] adds the fp64 sum of its 64 W fp32 values to a second accumulator [B].  The closing block
+ *      counts: when (total_frames[b] - 1) % shrink != 0 the reference averages the last, shorter block over the frames it
+ *      has (model.py:117-127) and that low-rate frame enters the utterance mean, although up-sampling never reads it.
+ *      Steps at or beyond total_frames[b] add nothing.
+ *   3. fsn_fast_segment_decoder: the low-rate frames of whole blocks that complete in the segment, divided by den_unit[b] =
+ *      float(sum / (64 W Ts_b)) + 1e-5f with Ts_b = 1 + ceil((total_frames[b] - 1) / shrink), through the bottleneck from
+ *      the carried (h, c); the held output joined to enc, the decoder pair -> crm_out [B, 2, F, k].  Step s is the
+ *      compressed mask of frame s - look_ahead, as in fsn_fast_stream_step.
+ * frames_done: model steps passed to THIS pass before the call.  total_frames (device memory, [B]): row b's own
+ * T_b + look_ahead >= 2.  In a ragged batch every row runs to the longest row's end; a row's mag must be zero from its frame
+ * T_b on (its mel is then exactly zero there), and only the divisors and the second sum depend on total_frames.
+ * The order of every sum depends on the frames alone: two segmentations of one recording give the same divisors, the same
+ * masks and the same state bit for bit.
+ *
+ * `state` (fsn_fast_segment_state_bytes(cfg, B), caller-owned, all zeros for a fresh recording) begins with
+ * fsn_fast_stream_step's layout (pass 2 carries the encoder pair's (h, c) there, pass 3 the bottleneck's and the decoder
+ * pair's, the open block's partial sum and the held output); behind it lie the two fp64 accumulators [B] each and the block
+ * sum [B][num_mels][W] of pass 2's statistic, a field of its own: nothing is cleared between the passes.  `packed`:
+ * fsn_fast_stream_pack's blob (its layout does not depend on the norm).  fsn_fast_segment_divisors writes den_mel and
+ * den_unit (device memory, [B] each) as the passes form them; call it after pass 2 for den_unit.
+ * FSN_ERR_ARG with fsn_last_error text (the size queries, which need no device, return 0): what fsn_fast_stream_step refuses
+ * of a configuration, B or k outside 1 .. 4096, and any norm but FSN_NORM_OFFLINE_LAPLACE - the causal norm needs no passes:
+ * run fsn_fast_stream_step over the same segments.  FSN_ERR_WORKSPACE for a short state or workspace buffer, before anything
+ * is launched.
+ * fsn_debug_fast_segment_state_layout (test hook, no device): out[0..25) (n >= 25): 0 - 15 as
+ * fsn_debug_fast_stream_state_layout, 16 / 17 the byte offsets of the mel and the unit accumulator [B] doubles, 18 of the
+ * statistic's block sum [B][num_mels][W] floats, 19 where fsn_fast_stream_step's fields end, 20 the padded row count of
+ * 0 - 7, 21 the bottleneck's row count, 22 encoder.1's padded hidden size, 23 W, 24 the size fsn_fast_segment_state_bytes
+ * returns.  -1 on bad arguments.  Additive entries (no new FSN_ABI_VERSION; a binding looks them up by name). */
+size_t fsn_fast_segment_state_bytes(const fsn_fast_cfg* cfg, int B);
+size_t fsn_fast_segment_workspace_bytes(const fsn_fast_cfg* cfg, int B, int k);
+int fsn_fast_segment_stats(const fsn_fast_cfg* cfg, const void* packed, void* state, size_t state_bytes, const float* mag, int B,
+                           int k, float* mel_out, void* workspace, size_t workspace_bytes, void* stream);
+int fsn_fast_segment_encoder(const fsn_fast_cfg* cfg, const void* packed, void* state, size_t state_bytes, int frames_done,
+                             const int* total_frames, const float* mel, int B, int k, float* enc_out, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int fsn_fast_segment_decoder(const fsn_fast_cfg* cfg, const void* packed, void* state, size_t state_bytes, int frames_done,
+                             const int* total_frames, const float* mel, const float* enc, int B, int k, float* crm_out,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int fsn_fast_segment_divisors(const fsn_fast_cfg* cfg, const void* state, size_t state_bytes, const int* total_frames, int B,
+                              float* den_mel, float* den_unit, void* stream);
+int fsn_debug_fast_segment_state_layout(const fsn_fast_cfg* cfg, int B, long* out, int n);
+
 /* ---- Fast FullSubNet, streaming pool: sessions at their own block phases ------------------------------------------------
  * fsn_fast_stream_step for streams that are NOT in lockstep, as fsn_fullsubnet_stream_pool_step is for FullSubNet.  `state`
  * is a pool of `capacity` slots (1 .. 4096), fsn_fast_stream_pool_state_bytes(cfg, look_ahead, capacity) bytes = capacity
