@@ -413,6 +413,15 @@ SIGNATURES = {
                                             _c.c_int, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "fsn_debug_improved_stream_state_layout": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
     "fsn_debug_improved_stream_form": (_c.c_int, [_c.c_int]),
+    "fsn_improved_segment_stats": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_long, _c.c_void_p, _f32p, _c.c_int,
+                                              _c.c_int, _c.c_void_p]),
+    "fsn_improved_segment_fullband": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_long,
+                                                 _c.c_void_p, _f32p, _c.c_int, _c.c_int, _f32p, _c.c_void_p, _c.c_size_t,
+                                                 _c.c_void_p]),
+    "fsn_improved_segment_sections": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_long, _c.c_void_p,
+                                                 _f32p, _f32p, _c.c_int, _c.c_int, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_improved_segment_divisors": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_int, _f32p, _f32p,
+                                                 _c.c_void_p]),
     "fsn_profile_num_stages": (_c.c_int, []),
     "fsn_profile_stage_name": (_c.c_char_p, [_c.c_int]),
     "fsn_profile_read": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_float), _c.c_int]),
@@ -434,7 +443,9 @@ ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr", "fsn_resam
                 "fsn_debug_fast_segment_state_layout",
                 "fsn_improved_stream_packed_bytes", "fsn_improved_stream_pack", "fsn_improved_stream_state_bytes",
                 "fsn_improved_stream_workspace_bytes", "fsn_improved_stream_step", "fsn_debug_improved_stream_state_layout",
-                "fsn_debug_improved_stream_form")
+                "fsn_debug_improved_stream_form",
+                "fsn_improved_segment_stats", "fsn_improved_segment_fullband", "fsn_improved_segment_sections",
+                "fsn_improved_segment_divisors")
 
 
 def lib():

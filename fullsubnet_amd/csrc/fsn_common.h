@@ -584,6 +584,7 @@ int fsn_launch_fast_segment_divisors(const double* acc_mel, const double* acc_un
 
 // improved_stream_kernels.hip: the stateful glue of fsn_improved_stream_step, time-major.  One call advances B streams by k
 // model steps t0 .. t0 + k - 1 on Fm = F - 1 bins (rows of FmP = round_up(Fm, 16) floats).
+constexpr int kFsnImprovedMaxBins = 4096;  // Fm the sections kernels stage per frame (two rows of it in LDS)
 struct FsnImprovedSection {
     int lower, units, sc, sn, fc, fn;  // the band's first bin, its units, centre / neighbours of the noisy and the fb window
     int W, Np, Ip;                     // sc + 2 sn + fc + 2 fn; the section's padded rows (B units) and columns
@@ -613,6 +614,24 @@ struct FsnImprovedKeep {
 int fsn_launch_improved_stream_keep(const FsnImprovedKeep& a, hipStream_t s);
 // (e) the sections' rows in bin order as the mask [B][2][F][k]; the last bin is zero
 int fsn_launch_improved_stream_mask(float* mask, const FsnImprovedStream& a, hipStream_t s);
+
+// improved_segment_kernels.hip: the same glue under the offline norms, for fsn_improved_segment_*.  total [B] (device): row
+// b's own frame count T_b; a frame at or past it adds nothing to a sum and its compressed magnitude counts as zero.
+// fb_sum[b] += the frames' sums of mag ** fdrc over the first Fm bins, frame by frame
+int fsn_launch_improved_segment_stat(const float* mag, double* fb_sum, const int* total, const FsnImprovedStream& a, hipStream_t s);
+// comp [k][Bp][FmP] and fb_in = comp / den.  mode 0: den = float(fb_sum[b] / (Fm T_b)) + EPSILON; 1: the running mean of
+// fsn_launch_improved_stream_front, fb_sum carried here; 2: comp alone (fb_in, fb_sum, steps untouched).  0, 1: steps = t0 + k
+int fsn_launch_improved_segment_front(int mode, const float* mag, float* comp, float* fb_in, double* fb_sum, long* steps,
+                                      const int* total, const FsnImprovedStream& a, hipStream_t s);
+// sb_sum[i][b] += every frame's sum over section i's windows of comp and fb_ws [k][Bp][ld_fb]; fb_out [k][B][Fm] = fb_ws
+int fsn_launch_improved_segment_sums(const float* comp, const float* fb_ws, long ld_fb, float* fb_out, double* sb_sum,
+                                     const int* total, const FsnImprovedStream& a, hipStream_t s);
+// every section's windows of comp and fb_out [k][B][Fm] divided by float(sb_sum[i][b] / (units_i W_i T_b)) + EPSILON
+int fsn_launch_improved_segment_sections(const float* comp, const float* fb_out, const double* sb_sum, const int* total,
+                                         const FsnImprovedStream& a, hipStream_t s);
+// den_fb [B], den_sb [n][B]: the divisors as the two kernels above form them
+int fsn_launch_improved_segment_divisors(const double* fb_sum, const double* sb_sum, const int* total, float* den_fb, float* den_sb,
+                                         const FsnImprovedStream& a, hipStream_t s);
 
 // ---- streaming pool for Fast FullSubNet (fsn_fast_stream_pool_*, fast_stream_pool_kernels.hip) -------------------------------
 // `capacity` records of slot_bytes each; all zeros is a fresh slot.  Byte offsets into a record (every array 256-byte

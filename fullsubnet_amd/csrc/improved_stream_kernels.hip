@@ -12,26 +12,11 @@
 // its entries in index order, a butterfly per wave, the four waves in order), so nothing depends on where a call begins or
 // ends and two chunkings of a stream give the same bits.  One workgroup owns a state field: none is read by one workgroup and
 // written by another.
-#include "fsn_common.h"
+#include "improved_glue.h"
+
+using namespace fsn_improved_glue;
 
 namespace {
-
-constexpr int kMaxBins = 4096;  // Fm the sections kernel stages per frame (two rows of it in LDS)
-
-__device__ __forceinline__ int bin_reflect(int j, int Fm) {
-    j = j < 0 ? -j : j;
-    return j > Fm - 1 ? 2 * (Fm - 1) - j : j;
-}
-
-// The workgroup's sum of one double per thread, in a fixed order; valid in thread 0 (call from all 256 threads).
-__device__ __forceinline__ double block_sum(double v, double* part) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if (lane == 0) part[wave] = v;
-    __syncthreads();
-    return (part[0] + part[1]) + (part[2] + part[3]);
-}
 
 // One workgroup per (padded) row b; the frames in turn.
 __global__ __launch_bounds__(256) void improved_stream_front_kernel(const float* __restrict__ mag, float* __restrict__ comp,
@@ -77,17 +62,11 @@ __global__ __launch_bounds__(256) void improved_stream_front_kernel(const float*
     }
 }
 
-__device__ __forceinline__ float section_entry(const float* bins, const FsnImprovedSection& q, int Fm, int e) {
-    const int u = e / q.W, w = e - u * q.W, w_sb = q.sc + 2 * q.sn;
-    if (w < w_sb) return bins[bin_reflect(q.lower + u * q.sc - q.sn + w, Fm)];
-    return bins[Fm + bin_reflect(q.lower + u * q.fc - q.fn + (w - w_sb), Fm)];
-}
-
 // One workgroup per (stream b, section i); the frames in turn, a frame's two spectra staged in LDS.
 __global__ __launch_bounds__(256) void improved_stream_sections_kernel(const float* __restrict__ comp,
                                                                        const float* __restrict__ fb_out, long ld_fb,
                                                                        double* __restrict__ sb_sum, const FsnImprovedStream a) {
-    __shared__ float bins[2 * kMaxBins];
+    __shared__ float bins[2 * kFsnImprovedMaxBins];
     __shared__ double part[4];
     __shared__ float den_s;
     const int b = blockIdx.x, i = blockIdx.y;
@@ -156,23 +135,6 @@ __global__ __launch_bounds__(256) void improved_stream_keep_kernel(const FsnImpr
     float4* dst = reinterpret_cast<float4*>(a.dst[j]);
     const long n4 = a.count[j] / 4;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) dst[i] = src[i];
-}
-
-int check_geometry(const FsnImprovedStream& a, const char* what) {
-    bool ok = a.B >= 1 && a.Bp >= a.B && a.F >= 2 && a.Fm == a.F - 1 && a.Fm <= kMaxBins && a.FmP >= a.Fm && a.k >= 1 &&
-              a.t0 >= 0 && a.n >= 1 && a.n <= 8 && (a.sqrt_mode == 0 || a.sqrt_mode == 1);
-    for (int i = 0; ok && i < a.n; ++i) {
-        const FsnImprovedSection& q = a.s[i];
-        ok = q.lower >= 0 && q.units >= 1 && q.sc >= 1 && q.fc >= 1 && (long)q.lower + (long)q.units * q.sc <= a.Fm &&
-             (long)q.lower + (long)q.units * q.fc <= a.Fm && q.sn >= 0 && q.fn >= 0 && q.sn <= a.Fm - 1 && q.fn <= a.Fm - 1 &&
-             q.W == q.sc + 2 * q.sn + q.fc + 2 * q.fn && q.Ip >= q.W && (long)q.Np >= (long)a.B * q.units && q.x && q.o;
-    }
-    if (!ok) {
-        fsn_set_error("%s: geometry outside the kernel (at most %d bins, 1 .. 8 sections inside them, padded sizes not below the sizes)",
-                      what, kMaxBins);
-        return FSN_ERR_ARG;
-    }
-    return FSN_OK;
 }
 
 }  // namespace

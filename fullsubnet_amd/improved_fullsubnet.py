@@ -455,6 +455,30 @@ class Model(BaseModel):
             self._stream_packed = cached
         return cached[1]
 
+    def enhance_long(self, noisy, lengths=None, segment_frames=None, workspace_limit=4 << 30, return_crm=False, poison=False,
+                     n_fft=None, hop_length=None, slab_frames=4096):
+        """``model(y)`` for recordings of any length: noisy [B, L] (host or device) -> enhanced [B, L] on the device (and the
+        mask [B, 2, F, T] with ``return_crm``), with the signature and the meaning of FullSubNet's ``Model.enhance_long``.
+
+        ``model(y)`` keeps gate planes of hidden-state width for every frame: a minute at 48 kHz costs gigabytes.  Here the
+        model runs in segments of ``segment_frames`` frames (1 .. 4096; ``None``: the largest whose workspace stays under
+        ``workspace_limit`` bytes) with carried LSTM state.  Under the reference's norms (one mean per utterance in front of
+        the full-band model and one per section) that is three passes over the segments (libfsn_hip
+        ``fsn_improved_segment_*``); with ``norm_type = "cumulative_laplace_norm"`` two (the reference's sections stay
+        offline), and one pass of ``fsn_improved_stream_step`` when ``sb_norm_type`` is cumulative as well.  The transforms
+        run in slabs of ``slab_frames`` frames with the model's own n_fft and hop (``n_fft`` / ``hop_length``: None, or the
+        model's).  What grows with the recording are planes of F floats per frame (magnitude, spectrum, mask, full-band
+        output); ``improved_long_form.ImprovedLongPlan`` lists every allocation without making one.
+
+        ``lengths``: a ragged batch, as in ``forward``; output and mask are zero past a row's end.  The result agrees with
+        ``model(y)`` within fp32 rounding (other recurrent kernels), and any two values of ``segment_frames`` give the same
+        mask bit for bit.  ``poison`` (test hook): every buffer starts as NaN.  LSTM cells, hop = n_fft / 2 = win_length / 2,
+        offline / offline, cumulative / offline or cumulative / cumulative norms and a model on a ROCm device only: anything
+        else is an ``FsnError`` that names ``model(y)``."""
+        from .improved_long_form import enhance_long
+        return enhance_long(self, noisy, lengths, segment_frames, workspace_limit, return_crm, poison, n_fft, hop_length,
+                            slab_frames)
+
     def _persistent_chunk(self, B, T):
         """The largest batch <= B whose band sections run as one persistent launch (sequence_model.multi_plan), or None
         when B itself does / no batch in reach does."""

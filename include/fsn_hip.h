@@ -1326,6 +1326,57 @@ int fsn_debug_improved_stream_state_layout(const fsn_improved_cfg* cfg, int B, l
  * state.  0 or 1 selects a form for the whole process, any other value changes nothing; returns the form in use. */
 int fsn_debug_improved_stream_form(int form);
 
+/* ---- Improved FullSubNet, recordings of any length: the model in segments under the offline norms ----------------------
+ * The fsn_fast_segment_* contract for Improved FullSubNet with the reference's norms.  The one-call path keeps gate planes
+ * of hidden-state width for every frame of the recording; here the model runs on k (1 .. 4096) frames at a time.  What
+ * lives for the whole recording is the caller's: planes of F floats per frame (magnitude, mask) and, between passes 2 and
+ * 3, the full-band model's output fb_out [T][B][F - 1], time-major and unpadded in B, of which a segment is the contiguous
+ * slice [k][B][F - 1] at frame frames_done.  Everything of hidden-size width is inside `workspace`
+ * (fsn_improved_stream_workspace_bytes(cfg, B, k), one size for all passes).
+ *
+ * offline_laplace_norm divides by ONE mean per utterance and the model applies it twice (model.py:124-150, 565-567 in front
+ * of the full-band model; :402-440 in front of every band section, over the section's unfolded windows of the noisy
+ * magnitude AND of the full-band output).  A recording therefore takes three passes over its segments, each pass in frame
+ * order, one pass finished before the next begins:
+ *   1. fsn_improved_segment_stats: fb_sum[b] += the sum of mag ** fdrc over the first F - 1 bins of this call's frames
+ *      inside row b, frame by frame (fp64).
+ *   2. fsn_improved_segment_fullband: (mag ** fdrc) / den through the full-band block from its carried (h, c) -> fb_out
+ *      [k][B][F - 1].  fb_norm 0 (offline): den = float(fb_sum[b] / ((F - 1) total_frames[b])) + eps from the finished sum
+ *      of pass 1, eps the fp32 epsilon.  fb_norm 1 (cumulative; what the reference does under norm_type =
+ *      "cumulative_laplace_norm", whose sections stay offline): the running mean exactly as fsn_improved_stream_step forms
+ *      it, fb_sum carried by this pass itself - pass 1 is not run.  Any other fb_norm: FSN_ERR_ARG.  Every section's sum
+ *      over all units and all window columns - the noisy window and the fb_out window, mirrored at both ends of the
+ *      spectrum - of the frames inside the row is added to sb_sum[i][b] (fp64), frame by frame.
+ *   3. fsn_improved_segment_sections: every section's input divided by float(sb_sum[i][b] / (N_i W_i total_frames[b])) +
+ *      eps, through the sections' blocks from their carried (h, c) (in whichever form fsn_debug_improved_stream_form
+ *      selects) -> mask [B][2][F][k], the last bin an exact zero.
+ * frames_done: frames passed to THIS pass before the call.  total_frames (device memory, [B]): row b's own frame count
+ * T_b (values below 1 count as 1).  In a ragged batch every row runs to the longest row's end.  A frame at or past T_b adds
+ * nothing to any sum, its magnitude is not read and counts as zero wherever it is an input; what the blocks produce there
+ * is finite and to be ignored.
+ * A frame's own sum has a fixed shape and the fp64 carries advance frame by frame: two segmentations of one recording give
+ * the same fb_out, the same masks, the same divisors and the same state bit for bit.
+ *
+ * `state`: the blob of fsn_improved_stream_state_bytes(cfg, B) in fsn_improved_stream_step's layout
+ * (fsn_debug_improved_stream_state_layout), caller-owned, all zeros for a fresh recording: pass 2 carries the full-band
+ * block's (h, c) and writes the step count (frames_done + k), pass 3 carries the sections'; fb_sum and sb_sum hold the sums
+ * above.  `packed`: fsn_improved_stream_pack's blob.  fsn_improved_segment_divisors writes den_fb [B] and den_sb
+ * [sections][B] (device memory) as passes 2 (fb_norm 0) and 3 form them: call it after pass 1 for den_fb, after pass 2 for
+ * den_sb.
+ * FSN_ERR_ARG with fsn_last_error text: what fsn_improved_stream_step refuses of a configuration, B or k outside 1 ..
+ * 4096, a negative frames_done, a NULL pointer.  FSN_ERR_WORKSPACE for a short state or workspace buffer, before anything is
+ * launched.  Additive entries (no new FSN_ABI_VERSION; a binding looks them up by name). */
+int fsn_improved_segment_stats(const fsn_improved_cfg* cfg, void* state, size_t state_bytes, long frames_done,
+                               const int* total_frames, const float* mag, int B, int k, void* stream);
+int fsn_improved_segment_fullband(const fsn_improved_cfg* cfg, const void* packed, void* state, size_t state_bytes, int fb_norm,
+                                  long frames_done, const int* total_frames, const float* mag, int B, int k, float* fb_out,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int fsn_improved_segment_sections(const fsn_improved_cfg* cfg, const void* packed, void* state, size_t state_bytes,
+                                  long frames_done, const int* total_frames, const float* mag, const float* fb_out, int B, int k,
+                                  float* mask, void* workspace, size_t workspace_bytes, void* stream);
+int fsn_improved_segment_divisors(const fsn_improved_cfg* cfg, const void* state, size_t state_bytes, const int* total_frames,
+                                  int B, float* den_fb, float* den_sb, void* stream);
+
 int fsn_profile_num_stages(void);
 const char* fsn_profile_stage_name(int stage);
 int fsn_profile_read(void* stream, float* ms_per_stage, int n);
