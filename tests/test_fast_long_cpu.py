@@ -283,7 +283,8 @@ def test_enhance_long_refuses_on_the_host_and_names_enhance():
 def test_the_driver_shares_the_slab_helpers():
     import inspect
 
-    from fullsubnet_amd import fast_long_form, slabs
-    assert fast_long_form.analysis_slab is slabs.analysis_slab and fast_long_form.synthesis_slab is slabs.synthesis_slab
+    from fullsubnet_amd import fast_long_form, long_form, slabs
+    assert fast_long_form.run_segments is long_form.run_segments  # the one driver, which calls the slab helpers of slabs.py
+    assert long_form.analysis_slab is slabs.analysis_slab and long_form.synthesis_slab is slabs.synthesis_slab
     src = inspect.getsource(fast_long_form)
     assert "istft(" not in src and " stft(" not in src  # the transforms themselves are called in slabs.py only

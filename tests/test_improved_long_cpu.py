@@ -263,8 +263,9 @@ def test_norms_decide_the_passes():
 def test_the_driver_shares_the_slab_helpers():
     import inspect
 
-    from fullsubnet_amd import improved_long_form, slabs
-    assert improved_long_form.analysis_slab is slabs.analysis_slab and improved_long_form.synthesis_slab is slabs.synthesis_slab
+    from fullsubnet_amd import improved_long_form, long_form, slabs
+    assert improved_long_form.run_segments is long_form.run_segments  # the one driver, which calls the slab helpers of slabs.py
+    assert long_form.analysis_slab is slabs.analysis_slab and long_form.synthesis_slab is slabs.synthesis_slab
     src = inspect.getsource(improved_long_form)
     assert "istft(" not in src and " stft(" not in src  # the transforms themselves are called in slabs.py only
 

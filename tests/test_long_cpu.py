@@ -154,3 +154,29 @@ def test_streaming_enhancer_and_enhance_long_share_the_slab_helpers():
         assert mod.analysis_slab is slabs.analysis_slab and mod.synthesis_slab is slabs.synthesis_slab
         src = inspect.getsource(mod)
         assert "istft(" not in src and " stft(" not in src  # the transforms themselves are called in slabs.py only
+
+
+def test_the_three_plans_share_one_base_and_its_segments_and_slabs():
+    import improved_stream_reference as R
+    from fullsubnet_amd.fast_long_form import FastLongPlan
+    from fullsubnet_amd.improved_fullsubnet import Model as ImprovedModel
+    from fullsubnet_amd.improved_long_form import ImprovedLongPlan
+    from fullsubnet_amd.long_form import SegmentPlan
+    for cls in (LongPlan, FastLongPlan, ImprovedLongPlan):
+        assert issubclass(cls, SegmentPlan) and cls is not SegmentPlan
+        assert "slabs_of" not in vars(cls) and cls.slabs_of is SegmentPlan.slabs_of
+    fast_cfg = _lib.FastCfg(F=F, num_mels=64, shrink=2, mel_neighbors=5, enc_neighbors=0, bn_hidden=384, bn_layers=2, norm=0)
+    samples = 37 * HOP + 165  # T = 38 at 512 / 256
+    a = LongPlan(cfg(), 2, samples, segment_frames=19, slab_frames=5)
+    b = FastLongPlan(fast_cfg, LA, 2, samples, segment_frames=19, slab_frames=5)
+    assert (a.frames, a.steps) == (b.frames, b.steps) == (38, 40)
+    assert a.segments == b.segments == [(0, 19), (19, 19), (38, 2)]
+    assert len(a.slabs) == 8 and a.slabs == b.slabs
+    # Improved FullSubNet has no look-ahead and its own transform (960 / 480): 40 frames are the same 40 steps
+    k48 = ImprovedModel(**R.as_dict(R.K48)).stream_cfg()
+    c = ImprovedLongPlan(k48, 960, "offline", 2, 39 * 480 + 100, segment_frames=19)
+    assert (c.frames, c.steps) == (40, 40) and c.segments == a.segments
+    # ... and without a look-ahead the 38 frames are 38 steps on every plan
+    d = FastLongPlan(fast_cfg, 0, 2, samples, segment_frames=19)
+    e = ImprovedLongPlan(k48, 960, "offline", 2, 37 * 480 + 165, segment_frames=19)
+    assert d.steps == e.steps == 38 and d.segments == e.segments == [(0, 19), (19, 19)]

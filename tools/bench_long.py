@@ -11,77 +11,39 @@ device synchronise at both ends; recordings of up to two minutes take the median
 timed call (every buffer of the path comes from its allocator), the recording itself ([1, L] floats on the device) included.
 The parent never opens the device and stops at the first child that fails.  ``--write`` puts the table into
 profiles/long_recording.md."""
-import argparse
 import datetime
-import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import long_bench
+
 HOP, SR = 256, 16000
-CHILD_LIMIT_S = 380
 
 
-def measure(minutes, segment_frames):
-    """segment_frames: 0 = Model.enhance, -1 = enhance_long at its default workspace limit, else enhance_long at that k."""
+def build():
     import torch
     import fullsubnet_amd
-    from fullsubnet_amd.long_form import LongPlan
-    from fsn_synthetic import make_noisy, make_params
-
+    from fsn_synthetic import make_params
     model = fullsubnet_amd.Model(num_freqs=257, look_ahead=2, sequence_model="LSTM", fb_num_neighbors=0,
                                  sb_num_neighbors=15, fb_output_activate_function="ReLU",
                                  sb_output_activate_function=False, fb_model_hidden_size=512, sb_model_hidden_size=384,
                                  norm_type="offline_laplace_norm", num_groups_in_drop_band=1, weight_init=False)
     model.load_state_dict({k: torch.from_numpy(v) for k, v in make_params(seed=3).items()})
-    model = model.cuda().eval()
-    L = int(minutes * 60 * SR)
-    # one seeded minute, repeated (an hour of fresh noise is minutes of host time): the model's cost does not depend on the samples
-    base = torch.from_numpy(make_noisy(1, min(L, 60 * SR), seed=1))
-    noisy = base.repeat(1, -(-L // base.shape[1]))[:, :L].contiguous().cuda()
-    k = None if segment_frames < 0 else segment_frames
-    run = (lambda x: model.enhance(x)) if segment_frames == 0 else (lambda x: model.enhance_long(x, segment_frames=k))
-    # warm-up: the recording itself up to ten minutes (kernels loaded AND the allocator holding the call's buffers - the one
-    # call's 100 GB workspace at ten minutes costs seconds to allocate the first time), a 20-second one beyond
-    run(noisy if minutes <= 10 else noisy[:, :20 * SR])
-    torch.cuda.synchronize()
-    times = []
-    torch.cuda.reset_peak_memory_stats()
-    for _ in range(3 if minutes <= 2 else 1):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = run(noisy)
-        torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
-    peak = torch.cuda.max_memory_allocated()
-    assert out.shape == noisy.shape and bool(torch.isfinite(out).all())
-    frames = 1 + L // HOP
-    used = 0 if segment_frames == 0 else LongPlan(model._cfg, 1, L, k).segment_frames
-    return {"minutes": minutes, "frames": frames, "segment_frames": used, "default_k": segment_frames < 0,
-            "seconds": sorted(times)[len(times) // 2], "calls": len(times), "peak_bytes": peak}
+    return model.cuda().eval()
 
 
-def table(rows, commit):
+def used(model, L, k):
+    from fullsubnet_amd.long_form import LongPlan
+    return LongPlan(model._cfg, 1, L, k).segment_frames
+
+
+def table(rows, args):
     out = ["# Long recordings: time per frame and peak memory, B = 1", "",
-           f"{datetime.date.today().isoformat()}, commit {commit}, one MI355X; `tools/bench_long.py`: the shipped FullSubNet "
+           f"{datetime.date.today().isoformat()}, commit {args.commit}, one MI355X; `tools/bench_long.py`: the shipped FullSubNet "
            "configuration (offline_laplace_norm, fp32), 16 kHz, hop 256.  Host clock around the whole call with a device "
            "synchronise at both ends, after one warm-up call (on the recording itself up to ten minutes, on a 20-second one "
            "beyond); up to two minutes the median of three calls, longer recordings one call.  Peak memory: PyTorch's peak allocated bytes over the call, the recording on the device "
            "included.", "",
-           "| recording | frames | path | seconds | us per frame | x real time | vs one call | peak memory (MB) | MB per 1000 frames |",
-           "|---|---|---|---|---|---|---|---|---|"]
-    one_call = {r["minutes"]: r["seconds"] for r in rows if r["segment_frames"] == 0}
-    for r in rows:
-        path = "`enhance` (one call)" if r["segment_frames"] == 0 else (
-            f"`enhance_long`, segment_frames {r['segment_frames']}" + (" (default: 4 GiB workspace limit)" if r["default_k"] else ""))
-        ref = one_call.get(r["minutes"])
-        rel = "-" if r["segment_frames"] == 0 or ref is None else f"{r['seconds'] / ref:.2f} x"
-        out.append(f"| {r['minutes']:g} min | {r['frames']} | {path} | {r['seconds']:.3f} | {r['seconds'] / r['frames'] * 1e6:.1f} | "
-                   f"{r['minutes'] * 60 / r['seconds']:.0f} | {rel} | {r['peak_bytes'] / 1e6:.0f} | "
-                   f"{r['peak_bytes'] / 1e6 / r['frames'] * 1000:.1f} |")
+           *long_bench.rows_table(rows, "enhance")]
     out += ["",
             "`vs one call`: the segment path's time over `enhance` on the same recording (above 1: slower, below 1: faster).  "
             "This table is B = 1 only: there both paths run the recurrences as per-step launches; at larger batches the one "
@@ -91,44 +53,7 @@ def table(rows, commit):
     return "\n".join(out) + "\n"
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--minutes", type=float, nargs="+", default=[2, 10])
-    ap.add_argument("--segments", type=int, nargs="+", default=[256, 1024, 4096])
-    ap.add_argument("--long-minutes", type=float, default=60)
-    ap.add_argument("--commit", default="unknown")
-    ap.add_argument("--write", action="store_true", help="write profiles/long_recording.md")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "long_recording.md"))
-    ap.add_argument("--one", type=float, nargs=2, metavar=("MINUTES", "SEGMENT"), help="(child) one run, one JSON line")
-    args = ap.parse_args()
-    if args.one:
-        print("RESULT " + json.dumps(measure(args.one[0], int(args.one[1]))), flush=True)
-        return 0
-    runs = [(m, k) for m in args.minutes for k in [0] + args.segments]
-    if args.long_minutes > 0:
-        runs.append((args.long_minutes, -1))
-    rows = []
-    for m, k in runs:
-        try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", str(m), str(k)], capture_output=True,
-                               text=True, timeout=CHILD_LIMIT_S)
-        except subprocess.TimeoutExpired:
-            print(f"{m} min / {k}: no result within {CHILD_LIMIT_S} s; stopping", file=sys.stderr)
-            return 1
-        res = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
-        if p.returncode != 0 or not res:
-            print(f"{m} min / {k}: child failed ({p.returncode}); stopping\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}", file=sys.stderr)
-            return 1
-        rows.append(json.loads(res[-1][len("RESULT "):]))
-        print(rows[-1], flush=True)
-    text = table(rows, args.commit)
-    print(text)
-    if args.write:
-        os.makedirs(os.path.dirname(args.out), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
-    return 0
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(long_bench.main(__file__, table, "long_recording.md", [2, 10], [60], sr=SR, hop=HOP, build=build, used=used,
+                             one_call=lambda model, x: model.enhance(x),
+                             long_call=lambda model, x, k: model.enhance_long(x, segment_frames=k)))
