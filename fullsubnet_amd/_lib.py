@@ -422,6 +422,17 @@ SIGNATURES = {
                                                  _f32p, _f32p, _c.c_int, _c.c_int, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "fsn_improved_segment_divisors": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_int, _f32p, _f32p,
                                                  _c.c_void_p]),
+    "fsn_improved_stream_pool_state_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int]),
+    "fsn_improved_stream_pool_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int, _c.c_int]),
+    "fsn_improved_stream_pool_reset": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int,
+                                                  _c.c_void_p]),
+    "fsn_improved_stream_pool_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p,
+                                                 _c.c_int, _f32p, _c.c_int, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_improved_stream_pool_analysis": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int, _f32p,
+                                                     _f32p, _c.c_void_p, _c.c_int, _c.c_int, _f32p, _f32p, _c.c_void_p]),
+    "fsn_improved_stream_pool_synthesis": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int,
+                                                      _f32p, _c.c_void_p, _c.c_int, _c.c_int, _f32p, _f32p, _c.c_void_p]),
+    "fsn_debug_improved_stream_pool_layout": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int]),
     "fsn_profile_num_stages": (_c.c_int, []),
     "fsn_profile_stage_name": (_c.c_char_p, [_c.c_int]),
     "fsn_profile_read": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_float), _c.c_int]),
@@ -445,7 +456,10 @@ ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr", "fsn_resam
                 "fsn_improved_stream_workspace_bytes", "fsn_improved_stream_step", "fsn_debug_improved_stream_state_layout",
                 "fsn_debug_improved_stream_form",
                 "fsn_improved_segment_stats", "fsn_improved_segment_fullband", "fsn_improved_segment_sections",
-                "fsn_improved_segment_divisors")
+                "fsn_improved_segment_divisors",
+                "fsn_improved_stream_pool_state_bytes", "fsn_improved_stream_pool_workspace_bytes",
+                "fsn_improved_stream_pool_reset", "fsn_improved_stream_pool_step", "fsn_improved_stream_pool_analysis",
+                "fsn_improved_stream_pool_synthesis", "fsn_debug_improved_stream_pool_layout")
 
 
 def lib():
@@ -692,6 +706,21 @@ def fast_stream_pool_layout(cfg, look_ahead):
     if lib().fsn_debug_fast_stream_pool_layout(ctypes.byref(cfg), look_ahead, buf, len(buf)) != 0:
         raise FsnError("fsn_debug_fast_stream_pool_layout: bad arguments")
     return dict(zip(FAST_STREAM_POOL_LAYOUT, list(buf)))
+
+
+def improved_stream_pool_layout(cfg):
+    """Byte offsets into one record of Improved FullSubNet's streaming pool: ``fb`` [h0, c0, h1, c1], ``sb`` the same per
+    section, ``fb_sum``, ``sb_sum`` (8 doubles), ``steps`` (a long), the transform fields ``in_tail`` / ``ola_tail`` [hop],
+    ``spec_re`` / ``spec_im`` [F] and ``frame`` (an int); ``slot_bytes`` its size, and its dimensions
+    (fsn_debug_improved_stream_pool_layout)."""
+    buf = (ctypes.c_long * 58)()
+    if lib().fsn_debug_improved_stream_pool_layout(ctypes.byref(cfg), buf, len(buf)) != 0:
+        raise FsnError("fsn_debug_improved_stream_pool_layout: bad arguments")
+    v, n = list(buf), buf[49]
+    out = {"fb": v[0:4], "sb": [v[4 + 4 * i:8 + 4 * i] for i in range(n)], "sections": n, "units": v[50:50 + n]}
+    out.update(zip(("fb_sum", "sb_sum", "steps", "in_tail", "ola_tail", "spec_re", "spec_im", "frame", "slot_bytes", "F", "hop",
+                    "fb_hidden", "sb_hidden"), v[36:49]))
+    return out
 
 
 def profile_read(device=None):

@@ -25,8 +25,9 @@ SOURCES = ["fft_kernels.hip", "dft_kernels.hip", "elementwise_kernels.hip", "gem
            "stream_pool_kernels.hip", "mix_kernels.hip", "stoi_kernels.hip", "resample_kernels.hip",
            "resample_stream_kernels.hip", "fast_stream_kernels.hip", "fast_stream_pool_kernels.hip",
            "fast_segment_kernels.hip",
-           "improved_stream_kernels.hip", "improved_segment_kernels.hip",
-           "fsn_api.hip", "fsn_api_fast_stream.hip", "fsn_api_improved_stream.hip", "fsn_api_improved_segment.hip", "fsn_api_mix.hip", "fsn_api_metrics.hip", "fsn_api_resample.hip", "fsn_api_fullsubnet.hip", "fsn_api_layers.hip", "fsn_api_gru.hip", "fsn_api_birnn.hip", "fsn_api_train.hip"]
+           "improved_stream_kernels.hip", "improved_segment_kernels.hip", "improved_stream_pool_kernels.hip",
+           "fsn_api.hip", "fsn_api_fast_stream.hip", "fsn_api_improved_stream.hip", "fsn_api_improved_segment.hip",
+           "fsn_api_improved_stream_pool.hip", "fsn_api_mix.hip", "fsn_api_metrics.hip", "fsn_api_resample.hip", "fsn_api_fullsubnet.hip", "fsn_api_layers.hip", "fsn_api_gru.hip", "fsn_api_birnn.hip", "fsn_api_train.hip"]
 # -ffp-contract=off: elementwise code follows the reference's mul/add rounding sequence; fused
 # multiply-adds are written explicitly (fma / MFMA) where they are wanted.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-pass-failed",

@@ -595,6 +595,9 @@ struct FsnImprovedStream {
     int B, Bp, F, Fm, FmP, k, sqrt_mode, n;
     long t0;
     FsnImprovedSection s[8];
+    // NULL: every row stands at t0 (the lockstep entry).  Else [B] on the device, row b's own count (the streaming pool, whose
+    // sessions are not in lockstep); a negative one marks a row that belongs to no session: its magnitudes count as zeros
+    const long* t0_rows;
 };
 // (a) comp [k][Bp][FmP] = mag[b][f][t] ** fdrc without the last bin; fb_in = comp / (float(the stream's sum so far /
 // (Fm (t0 + t + 1))) + EPSILON), zero in the padding; fb_sum [B] carries the sum, steps [B] becomes t0 + k
@@ -632,6 +635,74 @@ int fsn_launch_improved_segment_sections(const float* comp, const float* fb_out,
 // den_fb [B], den_sb [n][B]: the divisors as the two kernels above form them
 int fsn_launch_improved_segment_divisors(const double* fb_sum, const double* sb_sum, const int* total, float* den_fb, float* den_sb,
                                          const FsnImprovedStream& a, hipStream_t s);
+
+// ---- streaming pool for Improved FullSubNet (fsn_improved_stream_pool_*, improved_stream_pool_kernels.hip) ------------------
+// `capacity` records of slot_bytes each; all zeros is a fresh slot.  Byte offsets into a record (every array 256-byte
+// aligned, slot_bytes a multiple of 256): what ONE stream of fsn_improved_stream_step carries at B = 1, without row padding -
+//   fb[a]           a = h0, c0, h1, c1 of the full-band block [fb_hidden]
+//   sb[i][a]        the same of section i [units_i][sb_hidden]
+//   fb_sum, sb_sum  the full-band norm's fp64 sum; one fp64 sum per section [8]
+//   steps           model steps this slot has taken (long; read and advanced on the device)
+// - and the transform state at hop = F - 1, n_fft = 2 hop:
+//   in_tail         the last hop of input [hop];  ola_tail  second half of the last synthesised frame [hop]
+//   spec_re/_im     the spectrum [F] of the one frame that waits for its mask (the model has no look-ahead)
+//   frame           that frame's number in its session (int; written by the analysis, read by the synthesis)
+struct FsnImprovedPoolLayout {
+    size_t fb[4], sb[8][4], fb_sum, sb_sum, steps, in_tail, ola_tail, spec_re, spec_im, frame, slot_bytes;
+    int F, hop, Hf, Hs, n, units[8];
+};
+static inline FsnImprovedPoolLayout fsn_improved_pool_layout(int F, int Hf, int Hs, int sections, const int* units) {
+    FsnImprovedPoolLayout L{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        const size_t r = o;
+        o = fsn_round_up_sz(o + bytes, 256);
+        return r;
+    };
+    L.F = F;
+    L.hop = F - 1;
+    L.Hf = Hf;
+    L.Hs = Hs;
+    L.n = sections;
+    for (int a = 0; a < 4; ++a) L.fb[a] = take((size_t)Hf * sizeof(float));
+    for (int i = 0; i < sections; ++i) {
+        L.units[i] = units[i];
+        for (int a = 0; a < 4; ++a) L.sb[i][a] = take((size_t)units[i] * Hs * sizeof(float));
+    }
+    L.fb_sum = take(sizeof(double));
+    L.sb_sum = take(8 * sizeof(double));
+    L.steps = take(sizeof(long));
+    L.in_tail = take((size_t)L.hop * sizeof(float));
+    L.ola_tail = take((size_t)L.hop * sizeof(float));
+    L.spec_re = take((size_t)F * sizeof(float));
+    L.spec_im = take((size_t)F * sizeof(float));
+    L.frame = take(sizeof(int));
+    L.slot_bytes = o;
+    return L;
+}
+// One call on the n listed slots.  The compact batch is a state in fsn_improved_stream_step's layout at B = n: tile[0][a]
+// [Bp][Hf] the full-band block's arrays, tile[1 + i][a] [rows[1 + i]][Hs] section i's (row b units_i + u), fb_sum [n], sb_sum
+// [sections][n], and t0 [n] each row's own count (-1: the row's id is outside the pool).
+struct FsnImprovedPool {
+    char* state;
+    FsnImprovedPoolLayout L;
+    const int* slots;
+    int capacity, n, k;
+    float* tile[9][4];
+    int rows[9];
+    double *fb_sum, *sb_sum;
+    long* t0;
+};
+// the listed records' rows, sums and counts into the compact batch; pad rows and rows of an id outside the pool are zeros
+int fsn_launch_improved_pool_gather(const FsnImprovedPool& a, hipStream_t s);
+// ... and back to the listed, valid records, their counts advanced by k: the last launch of a step
+int fsn_launch_improved_pool_scatter(const FsnImprovedPool& a, hipStream_t s);
+// one analysis / synthesis frame per listed slot at n_fft = 2 hop = 2 (F - 1) (see the kernels)
+int fsn_launch_improved_pool_analysis(void* state, const FsnImprovedPoolLayout& L, int capacity, const int* slots, int n,
+                                      const float* hops, const float* prime, const int* frame_no, const float* window, float* mag,
+                                      hipStream_t s);
+int fsn_launch_improved_pool_synthesis(void* state, const FsnImprovedPoolLayout& L, int capacity, const int* slots, int n,
+                                       const float* mask, const int* tail_samples, const float* window, float* out, hipStream_t s);
 
 // ---- streaming pool for Fast FullSubNet (fsn_fast_stream_pool_*, fast_stream_pool_kernels.hip) -------------------------------
 // `capacity` records of slot_bytes each; all zeros is a fresh slot.  Byte offsets into a record (every array 256-byte

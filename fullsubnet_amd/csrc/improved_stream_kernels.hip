@@ -10,7 +10,8 @@
 //   mask      model.py:443-449, 575: the sections' output rows in bin order as the mask [B][2][F][k], last bin zero
 // The running sums are fp64 and continue frame by frame from the state; a frame's own sum has a fixed shape (every thread adds
 // its entries in index order, a butterfly per wave, the four waves in order), so nothing depends on where a call begins or
-// ends and two chunkings of a stream give the same bits.  One workgroup owns a state field: none is read by one workgroup and
+// ends and two chunkings of a stream give the same bits.  The count the divisors start from is t0 for all rows, or each
+// row's own (FsnImprovedStream::t0_rows: the streaming pool, fsn_api_improved_stream_pool.hip).  One workgroup owns a state field: none is read by one workgroup and
 // written by another.
 #include "improved_glue.h"
 
@@ -34,12 +35,15 @@ __global__ __launch_bounds__(256) void improved_stream_front_kernel(const float*
             }
         return;
     }
+    const long t0_row = a.t0_rows ? a.t0_rows[b] : a.t0;  // uniform over the workgroup
+    const bool idle = t0_row < 0;                          // a pool row of no session: zeros in, a fresh stream's count
+    const long t0 = idle ? 0 : t0_row;
     double run = fb_sum[b];
     for (int t = 0; t < a.k; ++t) {
         const size_t row = ((size_t)t * a.Bp + b) * a.FmP;
         double s = 0.0;
         for (int f = threadIdx.x; f < a.Fm; f += 256) {
-            const float m = mag[((size_t)b * a.F + f) * a.k + t];
+            const float m = idle ? 0.f : mag[((size_t)b * a.F + f) * a.k + t];
             const float v = a.sqrt_mode ? sqrtf(m) : m;
             comp[row + f] = v;
             s += (double)v;
@@ -47,7 +51,7 @@ __global__ __launch_bounds__(256) void improved_stream_front_kernel(const float*
         s = block_sum(s, part);
         if (threadIdx.x == 0) {
             run += s;
-            den_s = (float)(run / ((double)a.Fm * ((double)a.t0 + t + 1.0))) + kFsnEpsilon;
+            den_s = (float)(run / ((double)a.Fm * ((double)t0 + t + 1.0))) + kFsnEpsilon;
         }
         __syncthreads();
         const float den = den_s;
@@ -58,7 +62,7 @@ __global__ __launch_bounds__(256) void improved_stream_front_kernel(const float*
     }
     if (threadIdx.x == 0) {
         fb_sum[b] = run;
-        steps[b] = a.t0 + a.k;
+        steps[b] = t0 + a.k;
     }
 }
 
@@ -73,6 +77,8 @@ __global__ __launch_bounds__(256) void improved_stream_sections_kernel(const flo
     const FsnImprovedSection& q = a.s[i];
     const int E = q.units * q.W, pad = q.Ip - q.W;
     const size_t row0 = (size_t)b * q.units;
+    const long t0_row = a.t0_rows ? a.t0_rows[b] : a.t0;
+    const long t0 = t0_row < 0 ? 0 : t0_row;
     double run = sb_sum[(size_t)i * a.B + b];
     for (int t = 0; t < a.k; ++t) {
         __syncthreads();  // the frame before is read
@@ -87,7 +93,7 @@ __global__ __launch_bounds__(256) void improved_stream_sections_kernel(const flo
         s = block_sum(s, part);
         if (threadIdx.x == 0) {
             run += s;
-            den_s = (float)(run / ((double)E * ((double)a.t0 + t + 1.0))) + kFsnEpsilon;
+            den_s = (float)(run / ((double)E * ((double)t0 + t + 1.0))) + kFsnEpsilon;
         }
         __syncthreads();
         const float den = den_s;

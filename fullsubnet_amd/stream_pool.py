@@ -3,7 +3,7 @@
 ``StreamingEnhancer`` runs a fixed batch in lockstep; a server that enhances calls has sessions that arrive and hang up
 at any time, whose hops are not phase-aligned and of which only some have a frame ready on a given 16 ms tick:
 
-    pool = StreamPool(model, capacity=64)      # fused FullSubNet config or Fast FullSubNet, norm_type == "cumulative_laplace_norm"
+    pool = StreamPool(model, capacity=64)      # fused FullSubNet config, Fast or Improved FullSubNet, cumulative norm(s)
     sid  = pool.open()                         # raises when the pool is full
     pool.push(sid, chunk)                      # 1-D samples, any length >= 0, host or device
     out  = pool.step()                         # {sid: samples}: ONE frame for every session that has one ready
@@ -30,6 +30,10 @@ A ``fast_fullsubnet.Model`` (cumulative norm, LSTM cells) is served the same way
 stand at different phases of a down-sampling block, so the bottleneck runs on the rows that are due on a tick.  The entry wants
 those rows listed first (``fast_pool_order``, on a host mirror of the slots' step counts); what differs between the two models
 sits behind one small object (``_FullSubNetCalls`` / ``_FastCalls``), everything else here is shared.
+
+An ``improved_fullsubnet.Model`` (both norms cumulative, LSTM cells, hop = n_fft / 2: 960 / 480 at 48 kHz) is served through
+``fsn_improved_stream_pool_*`` (``_ImprovedCalls``): the pool's transform is then the model's own, the mask multiplies real and
+imaginary parts, there is no look-ahead and rows go in any order.  Rate conversion around this pool is not built.
 
 ``SessionBook`` is the host book-keeping (which frame is next, who is ready, model steps versus output frames, the
 look-ahead drop); it makes no device call, so it is tested without a GPU.
@@ -214,7 +218,8 @@ def fast_pool_order(steps, k, shrink):
 
 class _FullSubNetCalls:
     """What StreamPool needs of the fused FullSubNet configuration: the cfg, the state size, the packed weights, the four C
-    entries and the row order (any)."""
+    entries, the transform and the row order (any)."""
+    fft = (N_FFT, HOP)
 
     def __init__(self, model):
         if not getattr(model, "_fused", False):
@@ -248,6 +253,7 @@ class _FullSubNetCalls:
 class _FastCalls:
     """... of a ``fast_fullsubnet.Model``: ``fsn_fast_stream_pool_*``, which take the look-ahead beside the cfg and want the
     rows that complete the larger number of low-rate frames first (``fast_pool_order``)."""
+    fft = (N_FFT, HOP)
 
     def __init__(self, model):
         if any(b.cell != "LSTM" for b in (*model.encoder, model.bottleneck, *model.decoder_lstm)):
@@ -279,27 +285,76 @@ class _FastCalls:
         return (n, n_long)
 
 
+class _ImprovedCalls:
+    """... of an ``improved_fullsubnet.Model``: ``fsn_improved_stream_pool_*`` on the model's own transform.  Its synthesis entry
+    takes one frame per call and finds the frame's number in the record, so it has no k, no first frame and no workspace."""
+
+    def __init__(self, model):
+        for key in ("norm_type", "sb_norm_type"):
+            if getattr(model, key) != "cumulative_laplace_norm":
+                raise ValueError(f"streaming needs a causal norm in front of the full-band model and of the band sections: "
+                                 f"build the model with {key} = 'cumulative_laplace_norm'")
+        if model.n_fft // 2 + 1 != model.num_freqs or model.hop_length * 2 != model.n_fft or model.win_length != model.n_fft:
+            raise NotImplementedError(
+                f"the pool's overlap-add is written for hop = n_fft / 2 = win_length / 2 (960 / 480 at 48 kHz), not for "
+                f"{model.n_fft} / {model.hop_length} / {model.win_length}: set hop_length = n_fft / 2 (the model's 16 kHz default of "
+                f"512 / 128 is not served)")
+        self.model = model
+        self.fft = (int(model.n_fft), int(model.hop_length))
+        self._cfg = model.stream_cfg()
+        self.head = (ctypes.byref(self._cfg),)
+        L = _lib.lib()
+        self.analysis, self.synthesis = L.fsn_improved_stream_pool_analysis, L.fsn_improved_stream_pool_synthesis
+        self.step, self.reset = L.fsn_improved_stream_pool_step, L.fsn_improved_stream_pool_reset
+
+    def state_bytes(self, capacity):
+        nbytes = _lib.lib().fsn_improved_stream_pool_state_bytes(*self.head, capacity)
+        if nbytes == 0:  # a configuration (GRU cells: sequence_model = "LSTM" is the one served) or a capacity the C entry refuses
+            raise NotImplementedError(_lib.lib().fsn_last_error().decode())
+        return nbytes
+
+    def workspace_bytes(self, n, k):
+        return _lib.lib().fsn_improved_stream_pool_workspace_bytes(*self.head, n, k)
+
+    def packed(self):
+        return self.model.stream_packed_weights()
+
+    def order(self, steps, k):
+        return None  # rows in any order
+
+    def rows(self, n, n_long):
+        return (n,)
+
+
 class StreamPool:
     def __init__(self, model, capacity=64, poison_buffers=False, input_sr=None, output_sr="model", resample_design="scipy",
                  record_model_rate=False):
         from .fast_fullsubnet import Model as FastModel
+        from .improved_fullsubnet import Model as ImprovedModel
+        self._improved = isinstance(model, ImprovedModel)
+        if self._improved and (input_sr is not None or output_sr not in ("model", "input")):
+            raise NotImplementedError("StreamPool(improved model) runs at the model's own rate: the model carries no sample rate and "
+                                      "the rate conversion around this pool is not built (leave input_sr / output_sr at their defaults)")
         if model.norm_type != "cumulative_laplace_norm" and (isinstance(model, FastModel) or getattr(model, "_fused", False)):
             raise ValueError("streaming needs a causal norm: build the model with norm_type = 'cumulative_laplace_norm' "
                              "(fullsubnet/train_cumulativeLaplaceNorm.toml)")
-        self._calls = _FastCalls(model) if isinstance(model, FastModel) else _FullSubNetCalls(model)
+        self._calls = (_ImprovedCalls(model) if self._improved else _FastCalls(model) if isinstance(model, FastModel)
+                       else _FullSubNetCalls(model))
+        # the transform: the model's own for Improved FullSubNet, 512 / 256 otherwise
+        self.n_fft, self.hop = self._calls.fft
         self.model = model.eval()
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
             raise _lib.FsnError("StreamPool needs the model on a ROCm device; this path has no CPU implementation")
-        if model.num_freqs != N_FFT // 2 + 1:
+        if not self._improved and model.num_freqs != N_FFT // 2 + 1:
             raise NotImplementedError(f"StreamPool is built for the 512 / 256 transform (num_freqs 257, got {model.num_freqs})")
         self.capacity = int(capacity)
         nbytes = self._calls.state_bytes(self.capacity)
         self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self.slot_bytes = nbytes // self.capacity
         self._steps = [0] * self.capacity  # host mirror of the slots' step counts: model_step advances, reset_slots clears
-        self.book = SessionBook(self.capacity, model.look_ahead)
-        self._window = torch.hann_window(N_FFT, device=self.device)
+        self.book = SessionBook(self.capacity, model.look_ahead, self.hop)
+        self._window = torch.hann_window(self.n_fft, device=self.device)
         self.poison_buffers = bool(poison_buffers)  # debugging: NaN-fill every workspace and output before its call
         self._buf = {}   # sid -> (device samples from global index buf0 on, buf0)
         # Sessions at another rate than the model's (module docstring): two stateful resamplers around the tick.  With
@@ -340,7 +395,7 @@ class StreamPool:
             mag.fill_(float("nan"))
         _lib.check(self._calls.analysis(
             *self._state_args(), slots_dev.data_ptr(), n, _lib.dev_ptr(hops, "hops"),
-            _lib.dev_ptr(prime, "prime", allow_none=True), frame_no_dev.data_ptr(), N_FFT, HOP, _lib.dev_ptr(self._window),
+            _lib.dev_ptr(prime, "prime", allow_none=True), frame_no_dev.data_ptr(), self.n_fft, self.hop, _lib.dev_ptr(self._window),
             _lib.dev_ptr(mag), _lib.stream_ptr(self.device)))
         return mag
 
@@ -379,14 +434,21 @@ class StreamPool:
     def synthesis(self, slots_dev, n, crm, first_frame_dev, tail_dev):
         """crm [n, 2, F, k] -> out [n, (k + 1) hop]: the hop of every column that is an output frame >= 1, then the tail."""
         k = crm.shape[-1]
-        out = torch.empty((n, (k + 1) * HOP), dtype=torch.float32, device=self.device)
-        ws = _lib.workspace(n * k * N_FFT * 4, self.device)
+        out = torch.empty((n, (k + 1) * self.hop), dtype=torch.float32, device=self.device)
+        if self._improved:  # one frame per call (k = 1: no look-ahead), its number in the record, no workspace
+            if self.poison_buffers:
+                out.fill_(float("nan"))
+            _lib.check(self._calls.synthesis(
+                *self._state_args(), slots_dev.data_ptr(), n, _lib.dev_ptr(crm, "mask"), tail_dev.data_ptr(), self.n_fft, self.hop,
+                _lib.dev_ptr(self._window), _lib.dev_ptr(out), _lib.stream_ptr(self.device)))
+            return out
+        ws = _lib.workspace(n * k * self.n_fft * 4, self.device)
         if self.poison_buffers:
             ws.view(torch.float32).fill_(float("nan"))
             out.fill_(float("nan"))
         _lib.check(self._calls.synthesis(
             *self._state_args(), slots_dev.data_ptr(), n, _lib.dev_ptr(crm, "crm"), k, first_frame_dev.data_ptr(),
-            tail_dev.data_ptr(), N_FFT, HOP, _lib.dev_ptr(self._window), _lib.dev_ptr(out), ws.data_ptr(), ws.numel(),
+            tail_dev.data_ptr(), self.n_fft, self.hop, _lib.dev_ptr(self._window), _lib.dev_ptr(out), ws.data_ptr(), ws.numel(),
             _lib.stream_ptr(self.device)))
         return out
 
@@ -483,9 +545,9 @@ class StreamPool:
         for sid in sids:
             t, m, cnt = self.book.take_frame(sid)
             buf, b0 = self._buf[sid]
-            hop = buf[t * HOP - b0:(t + 1) * HOP - b0]
+            hop = buf[t * self.hop - b0:(t + 1) * self.hop - b0]
             hops.append(hop)
-            primes.append(buf[1 - b0:HOP + 1 - b0] if t == 0 else hop)  # only read for frame 0
+            primes.append(buf[1 - b0:self.hop + 1 - b0] if t == 0 else hop)  # only read for frame 0
             any_first |= t == 0
             rows[0].append(self.book.slot(sid))
             rows[1].append(t)
@@ -532,8 +594,8 @@ class StreamPool:
             return tail
         self.book.session(sid)
         n_model = out_length(r.n_in, self.input_sr, self.model_sr)
-        if n_model <= HOP:  # before anything is flushed: the session stays as it is, like the plain pool's
-            raise _lib.FsnError(f"session shorter than n_fft / 2 + 1 = {HOP + 1} samples at the model's rate (reflect padding), "
+        if n_model <= self.hop:  # before anything is flushed: the session stays as it is, like the plain pool's
+            raise _lib.FsnError(f"session shorter than n_fft / 2 + 1 = {self.hop + 1} samples at the model's rate (reflect padding), "
                                 f"like torch.stft: {r.n_in} samples at {self.input_sr} Hz are {n_model}")
         if self._down is not None:
             raw = torch.cat(r.pending) if r.pending else torch.zeros(0, dtype=torch.float32, device=self.device)
@@ -564,7 +626,7 @@ class StreamPool:
         L = self.book.session(sid).n_in
         t, m0, k, skip, tail, cnt = self.book.take_last(sid)
         buf, b0 = self._buf[sid]
-        j = torch.arange(t * HOP, (t + 1) * HOP, device=self.device)
+        j = torch.arange(t * self.hop, (t + 1) * self.hop, device=self.device)
         j = torch.where(j >= L, 2 * (L - 1) - j, j)  # torch.stft's reflect padding at the right edge
         hop = buf[j - b0][None]
         slot = self.book.slot(sid)
@@ -573,7 +635,7 @@ class StreamPool:
         mag = torch.cat([mag, mag.new_zeros(1, 1, mag.shape[2], k - 1)], dim=-1)  # fullsubnet/model.py:85
         crm = self.model_step([slot], mag, slots_dev=meta[0])
         out = self.synthesis(meta[0], 1, crm, meta[2], meta[3])
-        parts.append(out[0, skip * HOP:skip * HOP + cnt])
+        parts.append(out[0, skip * self.hop:skip * self.hop + cnt])
         self.reset_slots([slot])
         self.book.release(sid)
         del self._buf[sid]

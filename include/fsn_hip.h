@@ -1377,6 +1377,68 @@ int fsn_improved_segment_sections(const fsn_improved_cfg* cfg, const void* packe
 int fsn_improved_segment_divisors(const fsn_improved_cfg* cfg, const void* state, size_t state_bytes, const int* total_frames,
                                   int B, float* den_fb, float* den_sb, void* stream);
 
+/* ---- Improved FullSubNet, streaming pool: 48 kHz sessions share one step ------------------------------------------------
+ * fsn_improved_stream_step for streams that are NOT in lockstep, as fsn_fast_stream_pool_step is for Fast FullSubNet.
+ * `state` is a pool of `capacity` slots (1 .. 4096), fsn_improved_stream_pool_state_bytes(cfg, capacity) bytes = capacity
+ * equal records, slot s at byte s * (state_bytes / capacity), each 256-byte aligned.  A record holds what ONE stream of
+ * fsn_improved_stream_step carries at B = 1, without row padding ((h, c) of both full-band layers [fb_hidden], (h, c) of both
+ * layers of section i [units_i][sb_hidden], the full-band norm's fp64 sum, one fp64 sum per section), the slot's own step
+ * count (a long on the device: the kernels read and advance it) and the transform state of the two transform entries, sized
+ * for hop = F - 1: the last hop [hop], the overlap-add half frame [hop], the spectrum (re, im [F]) of the ONE frame that
+ * waits for its mask - the model has no look-ahead - and that frame's number.  All zeros is a fresh pool;
+ * fsn_improved_stream_pool_reset returns the n listed slots to that state (stream-ordered).
+ *
+ * fsn_improved_stream_pool_step advances the n listed slots (`slots`: device memory, n DISTINCT ids, 1 <= n <= capacity) by
+ * k (1 .. 4096) model steps, each from its own step count: row i of mag [n, 1, F, k] and mask_out [n, 2, F, k] belongs to
+ * slots[i] and is what fsn_improved_stream_step gives a batch of one with the same history (to the rounding of the recurrent
+ * kernels, which are chosen by the call's row count; the same calls on a fresh pool give the same bits, and so do two
+ * chunkings of a slot's frames in calls of the same n).  The last bin is an exact zero.  Rows go in any order.  The call
+ * gathers the listed records into a state of fsn_improved_stream_step's layout at B = n inside the workspace (pad rows and
+ * skipped rows zeros), runs that entry's sequence with every row's divisors taken from its own count and fp64 carry, and
+ * scatters (h, c), the sums and the counts + k back: its last kernel.  Slots that are not listed are not written.  A row
+ * whose id is outside [0, capacity) is skipped (its mask_out row is finite - its mag row is not read -, no state is touched);
+ * listing an id twice is the caller's error.  FSN_ERR_ARG with fsn_last_error text: what fsn_improved_stream_step refuses
+ * (configuration; n, k outside 1 .. 4096), capacity outside 1 .. 4096, n outside 1 .. capacity; the size queries need no
+ * device and return 0 then.  A state or workspace buffer that is too small: FSN_ERR_WORKSPACE, nothing launched.
+ *
+ * The transform around that step, one frame per listed slot and call: any even n_fft <= 4096 with hop = n_fft / 2 = F - 1 and
+ * a window of n_fft taps (960 / 480 at 48 kHz); anything else is FSN_ERR_ARG.  All int arrays are device memory, [n]; ids
+ * outside the pool are skipped (zeros out, no state touched).
+ * fsn_improved_stream_pool_analysis: fsn_stream_pool_analysis's contract.  frame = the slot's last hop ++ hops[i] (hops
+ * [n][hop]), windowed in fp32, its real DFT taken in fp64 from an exact twiddle table (fsn_stft's arithmetic at this size:
+ * two-level where n_fft splits, direct where not) and rounded once to fp32.  The spectrum and frame_no[i] (>= 0; a negative
+ * one skips the row) go to the record, the magnitude to mag [n, 1, F, 1], hops[i] becomes the slot's last hop.  Frame 0
+ * reads its left half backwards from prime[i] = y[1 .. hop] (prime [n][hop]; NULL only when no listed session is at frame 0:
+ * a frame 0 then takes the slot's carried hop, zeros on a fresh slot).
+ * fsn_improved_stream_pool_synthesis: mask [n, 2, F, 1] is the model's mask of the frame in the record.  The enhanced
+ * spectrum is mask[:, 0] re, mask[:, 1] im (model.py:575-577: no decompression, no complex product); then the inverse
+ * transform, the window and the overlap-add with the record's half frame, divided by the overlap-added squared window as
+ * fsn_istft / torch.istft do.  THE FRAME NUMBER m IS THE RECORD'S: the one the analysis call stored with the spectrum.  Frame
+ * m >= 1 gives the hop samples [(m - 1) hop, m hop) at out[i][0 .. hop); frame 0 gives none.  tail_samples[i] >= 0 marks
+ * the session's last frame: the samples [(T - 1) hop, L), tail_samples[i] <= hop of them, follow at out[i][hop ..] (pass -1
+ * otherwise).  out [n][2 hop] is written completely (zeros where there is no sample).
+ *
+ * fsn_debug_improved_stream_pool_layout (test hook, no device): out[0..58) (n >= 58): byte offsets into a record of 0 - 3 the
+ * full-band h0, c0, h1, c1; 4 + 4 i + (0 .. 3) the same of section i (-1: no such section); 36 the full-band sum (double),
+ * 37 the sections' sums [8] doubles, 38 the step count (long), 39 the last hop [hop], 40 the overlap-add half frame [hop],
+ * 41 / 42 the waiting spectrum's re / im [F], 43 its frame number (int); 44 the record's size; 45 F, 46 hop, 47 fb_hidden,
+ * 48 sb_hidden, 49 the number of sections, 50 + i section i's units (-1: none).  -1 on bad arguments.
+ * Additive entries (no new FSN_ABI_VERSION; a binding looks them up by name). */
+size_t fsn_improved_stream_pool_state_bytes(const fsn_improved_cfg* cfg, int capacity);
+size_t fsn_improved_stream_pool_workspace_bytes(const fsn_improved_cfg* cfg, int n, int k);
+int fsn_improved_stream_pool_reset(const fsn_improved_cfg* cfg, void* state, size_t state_bytes, int capacity, const int* slots,
+                                   int n, void* stream);
+int fsn_improved_stream_pool_step(const fsn_improved_cfg* cfg, const void* packed, void* state, size_t state_bytes, int capacity,
+                                  const int* slots, int n, const float* mag, int k, float* mask_out, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int fsn_improved_stream_pool_analysis(const fsn_improved_cfg* cfg, void* state, size_t state_bytes, int capacity,
+                                      const int* slots, int n, const float* hops, const float* prime, const int* frame_no,
+                                      int n_fft, int hop, const float* window, float* mag, void* stream);
+int fsn_improved_stream_pool_synthesis(const fsn_improved_cfg* cfg, void* state, size_t state_bytes, int capacity,
+                                       const int* slots, int n, const float* mask, const int* tail_samples, int n_fft, int hop,
+                                       const float* window, float* out, void* stream);
+int fsn_debug_improved_stream_pool_layout(const fsn_improved_cfg* cfg, long* out, int n);
+
 int fsn_profile_num_stages(void);
 const char* fsn_profile_stage_name(int stage);
 int fsn_profile_read(void* stream, float* ms_per_stage, int n);
