@@ -11,6 +11,7 @@ from .graphs import GraphedCall  # noqa: F401
 from .inferencer import Inferencer  # noqa: F401
 from .long_form import LongPlan  # noqa: F401
 from .mix import MixBank, MixConfig, MixItem, MixLoader, draw_item, mix_batch  # noqa: F401
+from .acoustics.rvb import reverberation_time_shortening  # noqa: F401
 from .model import Model  # noqa: F401
 from .optim import ClipAdam  # noqa: F401
 from .stream_pool import SessionBook, StreamPool, fast_pool_order  # noqa: F401

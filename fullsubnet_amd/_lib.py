@@ -337,6 +337,12 @@ SIGNATURES = {
     "fsn_mix_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
     "fsn_mix_pairs": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
                                  _c.c_int, _c.c_int, _c.c_float, _f32p, _f32p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "fsn_rir_shorten": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _f32p,
+                                   _c.c_int, _f32p, _c.c_void_p, _c.c_void_p]),
+    "fsn_mix_target_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "fsn_mix_pairs_target": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                        _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _f32p, _f32p, _f32p, _c.c_void_p,
+                                        _c.c_size_t, _c.c_void_p]),
     "fsn_stoi_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
     "fsn_stoi": (_c.c_int, [_f32p, _f32p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t,
                             _c.c_void_p]),
@@ -459,7 +465,8 @@ ADDED_IN_118 = ("fsn_stoi_workspace_bytes", "fsn_stoi", "fsn_si_sdr", "fsn_resam
                 "fsn_improved_segment_divisors",
                 "fsn_improved_stream_pool_state_bytes", "fsn_improved_stream_pool_workspace_bytes",
                 "fsn_improved_stream_pool_reset", "fsn_improved_stream_pool_step", "fsn_improved_stream_pool_analysis",
-                "fsn_improved_stream_pool_synthesis", "fsn_debug_improved_stream_pool_layout")
+                "fsn_improved_stream_pool_synthesis", "fsn_debug_improved_stream_pool_layout",
+                "fsn_rir_shorten", "fsn_mix_target_workspace_bytes", "fsn_mix_pairs_target")
 
 
 def lib():

@@ -1,4 +1,5 @@
-// C ABI of the on-device mixing of training pairs: fsn_conv_rows, fsn_mix_pairs and their size queries
+// C ABI of the on-device mixing of training pairs: fsn_conv_rows, fsn_mix_pairs, fsn_rir_shorten, fsn_mix_pairs_target
+// and their size queries
 // (include/fsn_hip.h "training pairs mixed on the device"; kernels: mix_kernels.hip).
 #include <stddef.h>
 
@@ -48,6 +49,14 @@ size_t conv_part_bytes(int B, int L, int max_h_len) {
 }
 
 size_t row_bytes(int B, int L) { return fsn_round_up_sz((size_t)B * L * sizeof(float), 256); }
+
+// fsn_mix_pairs_target on top of fsn_mix_pairs: the second convolution's row, the shortened taps ([B][tap_ld(L)]: taps
+// from L on reach no output, and the call - unlike the size query - is not told the longest response) and their Taps
+int tap_ld(int L) { return (L + 3) & ~3; }  // rows of whole 16-byte words
+size_t target_part_bytes(int B, int L) {
+    return row_bytes(B, L) + row_bytes(B, tap_ld(L)) + fsn_round_up_sz((size_t)B * sizeof(long), 256) +
+           fsn_round_up_sz((size_t)B * sizeof(int), 256);
+}
 
 int workspace_ok(const char* who, const void* workspace, size_t workspace_bytes, size_t least) {
     FSN_REQUIRE(workspace, "%s: NULL workspace", who);
@@ -114,4 +123,64 @@ extern "C" int fsn_mix_pairs(const void* clean_slab, const void* noise_slab, con
     FSN_TRY(fsn_launch_conv_rows(c0, B, L, rir_slab, slab_format, &items->rir_off, sizeof(fsn_mix_item), &items->rir_len,
                                  sizeof(fsn_mix_item), c1, planned ? Z : nullptr, live, logN, s));
     return fsn_launch_mix_level(c1, nz, items, B, L, eps, noisy, clean, s);
+}
+
+extern "C" int fsn_rir_shorten(const void* h_slab, int slab_format, const long* h_off, const int* h_len, int B, int max_h_len,
+                               const fsn_mix_target* targets, float* out, int ld, float* win, int* idx, void* stream) {
+    FSN_REQUIRE(B >= 1 && max_h_len >= 0, "fsn_rir_shorten: B = %d, longest response %d: B >= 1 and a length >= 0 are required",
+                B, max_h_len);
+    FSN_REQUIRE(slab_format == FSN_SLAB_F32 || slab_format == FSN_SLAB_I16, "fsn_rir_shorten: slab_format %d", slab_format);
+    FSN_REQUIRE(h_slab && h_off && h_len && targets && out, "fsn_rir_shorten: NULL pointer argument");
+    FSN_REQUIRE(ld >= max_h_len && ld >= 1, "fsn_rir_shorten: ld = %d is too small for the longest response of %d taps", ld,
+                max_h_len);
+    FSN_REQUIRE(out != win, "fsn_rir_shorten: out and win must be two arrays");
+    FsnCallScope scope(stream);
+    return fsn_launch_rir_shorten(h_slab, slab_format, h_off, sizeof(long), h_len, sizeof(int), B, targets, out, ld, win, idx,
+                                  nullptr, nullptr, static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t fsn_mix_target_workspace_bytes(int B, int L, int max_rir_len) {
+    if (!shape_ok("fsn_mix_target_workspace_bytes", B, L, max_rir_len)) return 0;
+    return 3 * row_bytes(B, L) + target_part_bytes(B, L) + conv_part_bytes(B, L, max_rir_len);
+}
+
+extern "C" int fsn_mix_pairs_target(const void* clean_slab, const void* noise_slab, const void* rir_slab, int slab_format,
+                                    const fsn_mix_item* items, const fsn_mix_seg* segs, int n_segs, int B, int L, float eps,
+                                    const fsn_mix_target* targets, float* noisy, float* clean, float* target, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    if (!shape_ok("fsn_mix_pairs_target", B, L, 0)) return FSN_ERR_ARG;
+    FSN_REQUIRE(slab_format == FSN_SLAB_F32 || slab_format == FSN_SLAB_I16, "fsn_mix_pairs_target: slab_format %d", slab_format);
+    FSN_REQUIRE(n_segs >= 0, "fsn_mix_pairs_target: n_segs = %d", n_segs);
+    FSN_REQUIRE(eps >= 0.f, "fsn_mix_pairs_target: eps = %g", (double)eps);
+    FSN_REQUIRE(clean_slab && noise_slab && items && targets && noisy && target && (segs || n_segs == 0),
+                "fsn_mix_pairs_target: NULL pointer argument");
+    FSN_REQUIRE(noisy != clean && noisy != target && clean != target,
+                "fsn_mix_pairs_target: noisy, clean and target must be three arrays");
+    FSN_TRY(workspace_ok("fsn_mix_pairs_target", workspace, workspace_bytes,
+                         3 * row_bytes(B, L) + target_part_bytes(B, L) + conv_part_bytes(B, L, 0)));
+    Carver ws(workspace);
+    float* c0 = ws.take<float>((size_t)B * L);
+    float* c1 = ws.take<float>((size_t)B * L);
+    float* nz = ws.take<float>((size_t)B * L);
+    float* c2 = ws.take<float>((size_t)B * L);
+    float* hs = ws.take<float>((size_t)B * tap_ld(L));
+    long* t_off = ws.take<long>(B);
+    int* t_len = ws.take<int>(B);
+    int* live = ws.take<int>(B);
+    char* Z = ws.take<char>(0);
+    int logN;
+    bool planned;
+    conv_plan(B, L, workspace_bytes - ws.off, &logN, &planned);
+    FSN_REQUIRE(rir_slab || !planned, "fsn_mix_pairs_target: NULL response slab with a workspace sized for responses");
+    FsnCallScope scope(stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FSN_TRY(fsn_launch_mix_gather(clean_slab, noise_slab, slab_format, items, segs, n_segs, B, L, c0, nz, s));
+    FSN_TRY(fsn_launch_conv_rows(c0, B, L, rir_slab, slab_format, &items->rir_off, sizeof(fsn_mix_item), &items->rir_len,
+                                 sizeof(fsn_mix_item), c1, planned ? Z : nullptr, live, logN, s));
+    // the same plan a second time, on the shortened taps (the transform and its flags are free again: same stream)
+    FSN_TRY(fsn_launch_rir_shorten(planned ? rir_slab : nullptr, slab_format, &items->rir_off, sizeof(fsn_mix_item), &items->rir_len,
+                                   sizeof(fsn_mix_item), B, targets, hs, tap_ld(L), nullptr, nullptr, t_off, t_len, s));
+    FSN_TRY(fsn_launch_conv_rows(c0, B, L, hs, FSN_SLAB_F32, t_off, sizeof(long), t_len, sizeof(int), c2,
+                                 planned ? Z : nullptr, live, logN, s));
+    return fsn_launch_mix_level_target(c1, nz, c2, t_len, items, B, L, eps, noisy, clean, target, s);
 }

@@ -392,6 +392,16 @@ int fsn_launch_mix_gather(const void* clean_slab, const void* noise_slab, int fm
                           const fsn_mix_seg* segs, int n_segs, int B, int L, float* c0, float* nz, hipStream_t s);
 int fsn_launch_mix_level(const float* c, const float* nz, const fsn_mix_item* items, int B, int L, float eps, float* noisy,
                          float* clean, hipStream_t s);
+// fsn_rir_shorten / fsn_mix_pairs_target.  One workgroup per response: out (and win, idx when not NULL) as the header
+// states them; t_off / t_len (both or neither): row b's place in `out` (b ld) and the taps a convolution with it takes
+// (min(h_len, ld), 0 for a row whose target is its reverberant row: no response, or mode 0) - the Taps of the second
+// convolution.  h_off / h_len with strides as in fsn_launch_conv_rows.
+int fsn_launch_rir_shorten(const void* h_slab, int fmt, const void* h_off, int off_stride, const void* h_len, int len_stride,
+                           int B, const fsn_mix_target* targets, float* out, int ld, float* win, int* idx, long* t_off,
+                           int* t_len, hipStream_t s);
+// the level kernel's three-row form: target = (t_len[b] > 0 ? c2 : c) under the clean row's scalars; clean may be NULL
+int fsn_launch_mix_level_target(const float* c, const float* nz, const float* c2, const int* t_len, const fsn_mix_item* items,
+                                int B, int L, float eps, float* noisy, float* clean, float* target, hipStream_t s);
 
 // stoi_kernels.hip (fsn_stoi / fsn_si_sdr).  The plan is host arithmetic on (B, L_max, sr) alone (fsn_api_metrics.hip);
 // every per-row count follows on the device from the row's own length.

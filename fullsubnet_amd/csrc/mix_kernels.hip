@@ -6,6 +6,7 @@
 //   conv_rows_kernel      row transforms, Hermitian split and product, inverse row transforms    Z     -> Z
 //   conv_cols_inv_kernel  inverse column transforms, real part, first L samples                  Z     -> y
 //   mix_level_kernel      the five reductions, the scalars of snr_mix, the clip branch, the write c, nz -> noisy, clean
+//   rir_shorten_kernel    arg-max of |h|, window, product (reverberation_time_shortening)         h     -> shortened h
 //
 // The FFT convolution (circular length N = N1 N2 = 2^k): the signal goes into the real part and the response into the
 // imaginary part of ONE complex transform; with n = N2 n1 + n2 and k = k1 + N1 k2
@@ -241,9 +242,15 @@ __device__ __forceinline__ double block_max(double v, double* scratch) {
 
 // One workgroup per row: max|c|, sum c^2, max|n|, sum n^2, sum c n in fp64 (fixed order), the scalars of snr_mix from
 // them, then noisy = (A c + G n) s3 and clean = A c s3, the clip check on max|noisy| and the single fp32 rounding.
+// TARGET: a third row under the clean row's scalars, target = A t s3 with t the clean row convolved with the shortened
+// response (c2), or the reverberant row itself where there is none (t_len[b] == 0); clean may then be NULL.  Every
+// scalar still comes from c and nz alone, so noisy and clean keep the bits of the two-row form.
+template <bool TARGET>
 __global__ __launch_bounds__(kLevelThreads) void mix_level_kernel(const float* __restrict__ c, const float* __restrict__ nz,
                                                                   const fsn_mix_item* __restrict__ items, int L, double eps,
-                                                                  float* __restrict__ noisy, float* __restrict__ clean) {
+                                                                  float* __restrict__ noisy, float* __restrict__ clean,
+                                                                  const float* __restrict__ c2, const int* __restrict__ t_len,
+                                                                  float* __restrict__ target) {
     __shared__ double scratch[kLevelThreads / 64];
     const int b = blockIdx.x;
     const fsn_mix_item it = items[b];
@@ -286,11 +293,148 @@ __global__ __launch_bounds__(kLevelThreads) void mix_level_kernel(const float* _
     peak = block_max(peak, scratch);
     const double d = peak > 0.999 ? (0.99 - eps) / peak : 1.0;
     float* yn = noisy + (long)b * L;
-    float* yc = clean + (long)b * L;
-    for (int i = threadIdx.x; i < L; i += kLevelThreads) {
-        const double cv = a3 * (double)cr[i];
-        yn[i] = (float)(fma(g3, (double)nr[i], cv) * d);
-        yc[i] = (float)(cv * d);
+    if (!TARGET) {
+        float* yc = clean + (long)b * L;
+        for (int i = threadIdx.x; i < L; i += kLevelThreads) {
+            const double cv = a3 * (double)cr[i];
+            yn[i] = (float)(fma(g3, (double)nr[i], cv) * d);
+            yc[i] = (float)(cv * d);
+        }
+    } else {
+        const float* tr = t_len[b] > 0 ? c2 + (long)b * L : cr;
+        float* yc = clean ? clean + (long)b * L : nullptr;
+        float* yt = target + (long)b * L;
+        for (int i = threadIdx.x; i < L; i += kLevelThreads) {
+            const double cv = a3 * (double)cr[i];
+            yn[i] = (float)(fma(g3, (double)nr[i], cv) * d);
+            if (yc) yc[i] = (float)(cv * d);
+            yt[i] = (float)(a3 * (double)tr[i] * d);
+        }
+    }
+}
+
+// ---- fsn_rir_shorten: audio_zen/acoustics/rvb.py (reverberation_time_shortening) on a table of responses ---------------
+constexpr int kShortenThreads = 1024;
+constexpr int kTapRun = 8;  // consecutive taps per thread and pass: 16 bytes of PCM, two 16-byte words of fp32
+
+// np.argmax(np.abs(h)): the larger value wins, among equal values the LOWER index - in any order of combination
+struct Peak {
+    float v;
+    int i;
+};
+__device__ __forceinline__ Peak higher(Peak a, Peak b) { return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a; }
+
+// taps [n, n + kTapRun) of a response of hl taps that starts at sample `at` of the slab, zeros from hl on; vec: the run's
+// first byte is 16-byte aligned (n is a multiple of kTapRun, so the row's first byte decides for the whole row)
+__device__ __forceinline__ void load_taps(const void* slab, int fmt, long at, int n, int hl, bool vec, float (&t)[kTapRun]) {
+    if (vec && n + kTapRun <= hl) {
+        if (fmt == FSN_SLAB_I16) {
+            const int4 r = *reinterpret_cast<const int4*>(static_cast<const short*>(slab) + at + n);
+            const int w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                t[2 * j] = (float)(short)(w[j] & 0xffff) * (1.0f / 32768.0f);
+                t[2 * j + 1] = (float)(short)(w[j] >> 16) * (1.0f / 32768.0f);
+            }
+        } else {
+            const float4* p = reinterpret_cast<const float4*>(static_cast<const float*>(slab) + at + n);
+            const float4 a = p[0], b = p[1];
+            t[0] = a.x, t[1] = a.y, t[2] = a.z, t[3] = a.w, t[4] = b.x, t[5] = b.y, t[6] = b.z, t[7] = b.w;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < kTapRun; ++j) t[j] = n + j < hl ? slab_sample(slab, fmt, at + n + j) : 0.f;
+    }
+}
+
+__device__ __forceinline__ void store_taps(float* row, int n, int ld, bool vec, const float (&t)[kTapRun]) {
+    if (vec && n + kTapRun <= ld) {
+        float4* p = reinterpret_cast<float4*>(row + n);
+        p[0] = float4{t[0], t[1], t[2], t[3]};
+        p[1] = float4{t[4], t[5], t[6], t[7]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < kTapRun; ++j)
+            if (n + j < ld) row[n + j] = t[j];
+    }
+}
+
+// grid (B): one workgroup per response.  Pass 1: the peak of |h| over the WHOLE response, per thread in rising index
+// order, then over the wave by shuffles and over the waves in LDS - a fixed tree, and `higher` makes the result the one
+// of np.argmax whatever the tree.  Pass 2: the window in fp64 (exp10 of x = -q (n - N1), one rounded product as numpy
+// forms it; an fp64 pow(10, x) costs about twice as much and most of this kernel's time), its fp32 rounding, and
+// out = h * win as one fp32 product, for the first ld taps.
+__global__ __launch_bounds__(kShortenThreads) void rir_shorten_kernel(const void* __restrict__ h_slab, int fmt, Taps taps,
+                                                                      const fsn_mix_target* __restrict__ targets,
+                                                                      float* __restrict__ out, int ld, float* __restrict__ win,
+                                                                      int* __restrict__ idx_out, long* __restrict__ t_off,
+                                                                      int* __restrict__ t_len) {
+    __shared__ Peak wave_peak[kShortenThreads / 64];
+    const int b = blockIdx.x;
+    const int len = taps.length(b);
+    const int hl = len > 0 && h_slab ? len : 0;  // no slab (a workspace without a transform): nothing is read
+    const long at = hl ? taps.offset(b) : 0;
+    const fsn_mix_target tg = targets[b];
+    const bool known = tg.mode >= 0 && tg.mode <= 2;
+    const bool windowed = tg.mode == 1 || tg.mode == 2;
+    const size_t sample = fmt == FSN_SLAB_I16 ? sizeof(short) : sizeof(float);
+    const bool src16 = ((reinterpret_cast<uintptr_t>(h_slab) + (size_t)at * sample) & 15) == 0;
+    float t[kTapRun];
+
+    int idx = 0;
+    if (windowed || idx_out) {
+        Peak pk{-1.f, 0x7fffffff};
+        for (int n = threadIdx.x * kTapRun; n < hl; n += kShortenThreads * kTapRun) {
+            load_taps(h_slab, fmt, at, n, hl, src16, t);
+#pragma unroll
+            for (int j = 0; j < kTapRun; ++j) {
+                const float a = fabsf(t[j]);
+                if (n + j < hl && a > pk.v) pk = Peak{a, n + j};
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) pk = higher(pk, Peak{__shfl_down(pk.v, o, 64), __shfl_down(pk.i, o, 64)});
+        if ((threadIdx.x & 63) == 0) wave_peak[threadIdx.x >> 6] = pk;
+        __syncthreads();
+        pk = wave_peak[0];
+        for (int w = 1; w < kShortenThreads / 64; ++w) pk = higher(pk, wave_peak[w]);
+        idx = pk.v < 0.f ? 0 : pk.i;  // an empty response, or one of NaNs alone
+    }
+    if (threadIdx.x == 0) {
+        if (idx_out) idx_out[b] = idx;
+        if (t_len) {
+            t_off[b] = (long)b * ld;
+            t_len[b] = tg.mode != 0 && len > 0 ? (len < ld ? len : ld) : 0;
+        }
+    }
+
+    // as the taps of a convolution (t_len given) only what it reads is written: nothing for a row without a shortened
+    // response, no zeros behind the others
+    if (t_len && (tg.mode == 0 || hl == 0)) return;
+    const int end = t_len && hl < ld ? hl : ld;
+    const long n1 = (long)idx + tg.after_max;
+    float* orow = out + (long)b * ld;
+    float* wrow = win ? win + (long)b * ld : nullptr;
+    const bool dst16 = ((reinterpret_cast<uintptr_t>(orow) | reinterpret_cast<uintptr_t>(wrow)) & 15) == 0;
+    for (int n = threadIdx.x * kTapRun; n < end; n += kShortenThreads * kTapRun) {
+        load_taps(h_slab, fmt, at, n, hl, src16, t);
+        float w[kTapRun];
+#pragma unroll
+        for (int j = 0; j < kTapRun; ++j) {
+            const long m = (long)n + j;
+            float wv = 0.f;
+            if (m < hl) {
+                if (!known)
+                    wv = __builtin_nanf("");
+                else if (!windowed || m < n1)
+                    wv = 1.f;
+                else if (tg.mode == 1)
+                    wv = (float)exp10(-tg.q * (double)(m - n1));
+            }
+            w[j] = wv;
+            t[j] = t[j] * wv;
+        }
+        store_taps(orow, n, ld, dst16, t);
+        if (wrow) store_taps(wrow, n, ld, dst16, w);
     }
 }
 
@@ -336,6 +480,23 @@ int fsn_launch_mix_gather(const void* clean_slab, const void* noise_slab, int fm
 
 int fsn_launch_mix_level(const float* c, const float* nz, const fsn_mix_item* items, int B, int L, float eps, float* noisy,
                          float* clean, hipStream_t s) {
-    hipLaunchKernelGGL(mix_level_kernel, dim3(B), dim3(kLevelThreads), 0, s, c, nz, items, L, (double)eps, noisy, clean);
+    hipLaunchKernelGGL(mix_level_kernel<false>, dim3(B), dim3(kLevelThreads), 0, s, c, nz, items, L, (double)eps, noisy, clean,
+                       static_cast<const float*>(nullptr), static_cast<const int*>(nullptr), static_cast<float*>(nullptr));
     return fsn_check_launch("mix_level_kernel");
+}
+
+int fsn_launch_mix_level_target(const float* c, const float* nz, const float* c2, const int* t_len, const fsn_mix_item* items,
+                                int B, int L, float eps, float* noisy, float* clean, float* target, hipStream_t s) {
+    hipLaunchKernelGGL(mix_level_kernel<true>, dim3(B), dim3(kLevelThreads), 0, s, c, nz, items, L, (double)eps, noisy, clean,
+                       c2, t_len, target);
+    return fsn_check_launch("mix_level_kernel<target>");
+}
+
+int fsn_launch_rir_shorten(const void* h_slab, int fmt, const void* h_off, int off_stride, const void* h_len, int len_stride,
+                           int B, const fsn_mix_target* targets, float* out, int ld, float* win, int* idx, long* t_off,
+                           int* t_len, hipStream_t s) {
+    const Taps taps{static_cast<const char*>(h_off), static_cast<const char*>(h_len), off_stride, len_stride};
+    hipLaunchKernelGGL(rir_shorten_kernel, dim3(B), dim3(kShortenThreads), 0, s, h_slab, fmt, taps, targets, out, ld, win, idx,
+                       t_off, t_len);
+    return fsn_check_launch("rir_shorten_kernel");
 }

@@ -935,6 +935,52 @@ int fsn_mix_pairs(const void* clean_slab, const void* noise_slab, const void* ri
                   const fsn_mix_item* items, const fsn_mix_seg* segs, int n_segs, int B, int L, float eps, float* noisy,
                   float* clean, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- dereverberation targets : audio_zen/acoustics/rvb.py (reverberation_time_shortening) ---------------------------
+ * The training target of "Speech Dereverberation With a Reverberation Time Shortening Target" (Zhou, Zhu, Li 2022): the
+ * clean row convolved with a response whose tail, from after_max samples behind its peak on, decays faster.  Added
+ * without a new FSN_ABI_VERSION (additive; a binding looks the three symbols up by name).  Every pointer is a DEVICE
+ * pointer, the descriptor tables included; the calls copy nothing, never synchronise and can be captured in a graph.
+ *
+ * fsn_rir_shorten, per row b: the response h_b = h_slab[h_off[b], h_off[b] + h_len[b]) in either slab format, exactly
+ * as fsn_conv_rows takes it, and a descriptor targets[b]:
+ *   mode 0            out = h                                                    (the response, copied)
+ *   mode 1 shortened  idx = the FIRST index of max |h_b| over the WHOLE response (np.argmax(np.abs(rir))),
+ *                     N1 = idx + after_max, win[n] = 1 for n < N1 and 10^(-q (n - N1)) from N1 on, formed in fp64 and
+ *                     rounded to fp32; out[n] = fp32(h[n]) * win[n] as ONE fp32 product - the reference's arithmetic, a
+ *                     float32 window times a float32 response
+ *   mode 2 early      win[n] = 0 from N1 on: the direct path and what arrives within after_max samples of it
+ * The host forms q = 3 / (target_T60 sr) - 3 / (original_T60 sr) and after_max = floor(time_after_max sr); q is a double
+ * because its rounding error in fp32 would grow into win through exponents of 100 and more.  One workgroup per response:
+ * the arg-max is a fixed-order reduction over (value, lowest index) pairs, the window and the product follow in the same
+ * launch.  out [B][ld] (zeros behind h_len[b]); win [B][ld] (NULL: not wanted; zeros behind h_len[b]); idx [B] (NULL: not
+ * wanted; 0 for an empty response).  max_h_len states the longest response of the table: the host cannot see h_len, and
+ * a longer row is cut at ld - nothing is written outside [B][ld].  The descriptors are in device memory too: a mode
+ * outside 0 - 2 cannot be refused by the host and turns its row (out, win) into NaN; the packers of fullsubnet_amd/mix.py
+ * refuse it before anything is uploaded.
+ * Refused without a launch (fsn_last_error has the reason): a NULL h_slab, h_off, h_len, targets or out, B < 1,
+ * max_h_len < 0, ld < max_h_len, an unknown slab_format.
+ *
+ * fsn_mix_pairs_target: fsn_mix_pairs plus a third output.  noisy and clean are EXACTLY what fsn_mix_pairs writes for
+ * the same items - every level scalar of steps 2 - 5 still comes from the reverberant row - and clean may be NULL.
+ * target = conv(clean row, shortened response)[:L] times the scalar chain the clean row gets (1 / (max|c| + eps), the
+ * target_dbfs factor, the mixture's level factor, the clip divisor), rounded to fp32 once: the shortened counterpart of
+ * `clean` at the same gain, time-aligned with the mixture, and noisy - clean is untouched.  Rows with rir_len == 0 or
+ * mode 0 get target == clean bit for bit.  The second convolution runs on the plan of the first with the shortened taps
+ * (fp32, in the workspace); silence and all-zero responses give exact zeros, a response the workspace's transform cannot
+ * carry gives NaN in all three outputs, and a descriptor gives the same bits in any row of any batch. */
+typedef struct fsn_mix_target {
+    double q;      /* decay added per sample, in decades: win = 10^(-q (n - N1)) */
+    int after_max; /* samples behind the peak that stay untouched */
+    int mode;      /* 0: the response as it is, 1: shortened, 2: early */
+} fsn_mix_target;
+int fsn_rir_shorten(const void* h_slab, int slab_format, const long* h_off, const int* h_len, int B, int max_h_len,
+                    const fsn_mix_target* targets, float* out, int ld, float* win, int* idx, void* stream);
+size_t fsn_mix_target_workspace_bytes(int B, int L, int max_rir_len);
+int fsn_mix_pairs_target(const void* clean_slab, const void* noise_slab, const void* rir_slab, int slab_format,
+                         const fsn_mix_item* items, const fsn_mix_seg* segs, int n_segs, int B, int L, float eps,
+                         const fsn_mix_target* targets, float* noisy, float* clean, float* target, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* ---- validation metrics on the device : audio_zen/metrics.py (STOI, SI_SDR) ------------------------------------------
  * Row b of clean / reference and of estimate [B][L_max] (fp32) holds lengths[b] samples (device pointer; a value is
  * clamped into [0, L_max]; NULL: every row holds L_max); nothing past a row's length is read.  All arithmetic is fp64,

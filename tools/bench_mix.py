@@ -1,4 +1,5 @@
-"""Time of one fsn_mix_pairs call (training pairs mixed on the device) on one MI355X, next to the host baseline:
+"""Time of one fsn_mix_pairs / fsn_mix_pairs_target call (training pairs mixed on the device) on one MI355X, next to the
+host baseline:
 
     python tools/bench_mix.py [--batches 16 32 48] [--taps 16000 64000] [--iters 50] [--commit SHA] [--write]
 
@@ -10,8 +11,11 @@ from torch.profiler's device activity over ten further calls ("not measured" if 
 stage are what the stage must move once (inputs read once, outputs written once) from the shapes, with the time they take
 at 6.3 TB/s.  The host baseline is the fp32 numpy port (tests/mix_reference.py: snr_mix in fp32, convolution through
 np.fft) of the same items on 16 worker processes, started before the device is touched.  The error ratios are the worst
-error / allowance of the sweeps of tests/test_gpu_mix.py, run here through the tests' own runners.  `--write` puts
-everything into profiles/mix_pairs.md."""
+error / allowance of the sweeps of tests/test_gpu_mix.py, run here through the tests' own runners.  The same batches
+with a dereverberation target on every reverberant row (response shortened to a T60 of 0.15 s) go through
+`fsn_mix_pairs_target`, timed in the same run next to `fsn_mix_pairs` on the same descriptors, with its own kernel split
+and the worst error / allowance of the target rows of tests/test_gpu_mix_target.py.  `--write` puts everything into
+profiles/mix_pairs.md."""
 import argparse
 import datetime
 import multiprocessing
@@ -29,6 +33,8 @@ L = 49152
 HBM = 6.3e12  # measured streaming rate of the box (README)
 STEP_MS = {16: 12.4, 32: 24.0, 48: 35.0}  # README: train_step_amp_shipped_batches
 KERNELS = ("mix_gather_kernel", "conv_cols_fwd_kernel", "conv_rows_kernel", "conv_cols_inv_kernel", "mix_level_kernel")
+TARGET_KERNELS = KERNELS + ("rir_shorten_kernel",)
+TARGET_T60 = 0.15
 
 
 def sources(taps, seed=1):
@@ -54,6 +60,14 @@ def draw(B, lists, seed=2):
     items = [draw_item(i % len(lists[0]), tables, cfg, py, npr) for i in range(B)]
     for it in items[round(0.75 * B):]:
         it.rir_index = -1
+    # the target descriptors (read by fsn_mix_pairs_target alone): the responses of `sources` decay by e every taps / 7
+    # samples, a T60 of taps ln(1000) / 7 samples
+    from fullsubnet_amd.mix import shortening_q
+    taps = len(lists[2][0])
+    for it in items[:round(0.75 * B)]:
+        it.target_mode, it.target_after_max = 1, int(0.002 * cfg.sr)
+        it.target_q = shortening_q(taps * np.log(1000.0) / 7.0 / cfg.sr, TARGET_T60, cfg.sr)
+        assert it.target_q > 0
     return items
 
 
@@ -96,7 +110,7 @@ def event_ms(fn, iters):
     return statistics.median(windows), min(windows), max(windows)
 
 
-def kernel_split(fn, calls=10):
+def kernel_split(fn, calls=10, kernels=KERNELS):
     """{kernel: us per call} from torch.profiler's device activity; {} when it reports none of the kernels."""
     import torch
     try:
@@ -107,7 +121,7 @@ def kernel_split(fn, calls=10):
             torch.cuda.synchronize()
         out = {}
         for ev in prof.key_averages():
-            for k in KERNELS:
+            for k in kernels:
                 if k in ev.key:
                     us = getattr(ev, "device_time_total", None)
                     if us is None:
@@ -154,6 +168,28 @@ def error_ratios():
     return worst(conv), len(conv), worst(mix), len(mix)
 
 
+def target_error_ratios():
+    """(worst error / allowance, its row, rows) of the shortened and early rows of tests/test_gpu_mix_target.py's sweep, and
+    the taps of the golden responses that are not bit-equal to the reference's (of how many)."""
+    import mix_reference as R
+    import mix_target_reference as T
+    import test_gpu_mix_target as TT
+    import fullsubnet_amd as fsn
+    lists = R.mix_sources()
+    items = T.sweep_items()
+    _, _, target = TT.pairs_target(fsn.MixBank(*lists, "cuda", fmt="f32"), [it for _, it in items])
+    ratios = {}
+    for b, (name, it) in enumerate(items):
+        _, _, t64, allow, mode = T.target_rows(it, *lists, R.MIX_L)
+        if mode != 0 and t64.any():
+            ratios[name] = T.check_target(name, target[b], t64, allow)
+    name = max(ratios, key=ratios.get)
+    cases = T.golden_cases(os.path.join(ROOT, "tests", "golden"))
+    out, win, idx = TT.rir_shorten([c["h"] for c in cases], [(c["q"], c["after_max"], 1) for c in cases], "f32", 6000)
+    differ = sum(T.check_shorten(c, out[b], win[b], idx[b]) for b, c in enumerate(cases))
+    return ratios[name], name, len(ratios), differ, 2 * sum(len(c["h"]) for c in cases)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[16, 32, 48])
@@ -177,15 +213,19 @@ def main():
     from fullsubnet_amd import _lib, mix
     if not torch.cuda.is_available():
         raise SystemExit("bench_mix.py measures on the device: no ROCm device here")
-    lines, split_lines = [], []
+    lines, split_lines, target_lines, target_split_lines = [], [], [], []
     for taps in args.taps:
         for fmt in ("f32", "i16"):
             bank = fsn.MixBank(*work[(taps, args.batches[0])][0], "cuda", fmt=fmt)
             for B in args.batches:
                 items = work[(taps, B)][1]
                 out = (torch.empty(B, L, device="cuda"), torch.empty(B, L, device="cuda"))
-                call = lambda: mix.mix_batch(bank, items, L, out=out)  # noqa: E731
+                call = lambda: mix.mix_batch(bank, items, L, out=out, target=False)  # noqa: E731
                 med, lo, hi = event_ms(call, args.iters)
+                tcall = lambda: mix.mix_batch(bank, items, L, out=out, target=True)  # noqa: E731
+                tmed, tlo, thi = event_ms(tcall, args.iters)
+                target_lines.append(f"| {B} | {taps} | {fmt} | {tmed:.3f} | {tlo:.3f} - {thi:.3f} | {med:.3f} | {tmed / med:.2f} x |")
+                print(target_lines[-1], flush=True)
                 # the convolution alone, on the rows of the same batch
                 tab, _, _, longest = mix.pack_items(bank, items, L)
                 x = torch.randn(B, L, device="cuda") * 0.1
@@ -210,13 +250,23 @@ def main():
                         t = f"{split[k]:.1f}" if k in split else "not measured"
                         split_lines.append(f"| {taps} | {fmt} | `{k}` | {t} | {nbytes[k] / 1e6:.1f} | {1e6 * nbytes[k] / HBM:.1f} |")
                         print(split_lines[-1], flush=True)
+                    split = kernel_split(tcall, kernels=TARGET_KERNELS)
+                    for k in TARGET_KERNELS:
+                        t = f"{split[k]:.1f}" if k in split else "not measured"
+                        target_split_lines.append(f"| {taps} | {fmt} | `{k}` | {t} |")
+                        print(target_split_lines[-1], flush=True)
             del bank
     (cw, cn, mw, mn) = error_ratios()
     ratios = [f"* convolution sweep ({cn} rows, L = 1 ... 131072, both slab formats): worst error / allowance "
               f"**{cw[1] / cw[2]:.3f}** ({cw[0]}: {cw[1]:.3e} of the peak of |h| * |x|, allowance {cw[2]:.3e})",
               f"* mix sweep ({mn} outputs at L = {4097}): worst error / allowance **{mw[1] / mw[2]:.3f}** "
               f"({mw[0]}: {mw[1]:.3e} of the row's peak, allowance {mw[2]:.3e})"]
-    print("\n".join(ratios))
+    tw, tname, tn, differ, of = target_error_ratios()
+    target_ratios = [f"* target rows ({tn} shortened and early rows at L = {4097}): worst error / allowance **{tw:.3f}** ({tname}); "
+                     "allowance: what the mix sweep allows `clean` on the row plus 2^-22 s conv(|x|, |h_s|)[n]",
+                     f"* `fsn_rir_shorten` on the reference's own responses (`tests/golden/rts_windows.npz`): {differ} of {of} "
+                     "values of `out` and `win` are not bit-equal to the reference's (allowed: 2^-22 |ref| + 2^-126 each)"]
+    print("\n".join(ratios + target_ratios))
     if args.write:
         stamp = datetime.date.today().isoformat()
         doc = [
@@ -235,7 +285,17 @@ def main():
             "| RIR taps | slab | kernel | us per call | MB | us at 6.3 TB/s |", "|---|---|---|---|---|---|"] + split_lines + [
             "", "The sub-transforms are radix-2 passes in LDS on fp64 data; the radix-8 wave-level passes of `fft_kernels.hip` "
             "were not ported to this plan and have no measured time here.", "",
-            "## Error against the fp64 port", ""] + ratios + [""]
+            "## Error against the fp64 port", ""] + ratios + [
+            "", "## Dereverberation targets: time per `fsn_mix_pairs_target` call", "",
+            "The same batches, every reverberant row with a target: its response shortened to a T60 of "
+            f"{TARGET_T60} s from 2 ms behind its peak on.  `target call`: `mix_batch(target=True)` = descriptor upload + "
+            "`fsn_mix_pairs_target` (three rows levelled, `clean` not written); `pairs call`: `fsn_mix_pairs` on the same "
+            "descriptors in the same run, the `call` column above.  The second convolution runs the four-step plan a second "
+            "time on the shortened taps; a variant that shares transform work between the two convolutions was not built, so "
+            "there is no figure for it.", "",
+            "| B | RIR taps | slab | target call (ms) | windows | pairs call (ms) | target / pairs |", "|---|---|---|---|---|---|---|"] + target_lines + [
+            "", "Per kernel at B = 32 (the three convolution kernels run twice per call and are summed):", "",
+            "| RIR taps | slab | kernel | us per call |", "|---|---|---|---|"] + target_split_lines + [""] + target_ratios + [""]
         path = os.path.join(ROOT, "profiles", "mix_pairs.md")
         with open(path, "w") as f:
             f.write("\n".join(doc))
