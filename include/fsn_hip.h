@@ -471,7 +471,7 @@ int fsn_gru2_forward(const float* x, long ldx, const float* w_ih0, const float* 
 
 /* Up to eight INDEPENDENT two-layer stacks over the same T frames: the band sections of
  * improved_fullsubnet/model.py:402-449, whose SequenceModels have B x {20, 25, 6, 4} rows and input widths 62 .. 180 at
- * 48 kHz.  Per stack the arguments of fsn_lstm2_forward.  When every stack has H0 = H1 = 384 and together they fill
+ * 48 kHz.  Per stack the arguments of fsn_lstm2_forward.  When every stack has H0 = H1 = 384, T >= 4 and together they fill
  * most of the chip (fsn_lstm2_multi_is_persistent: 3/4 .. 1 x CUs / 8 clusters of 64 rows) they run as ONE persistent
  * launch of the group kernel with one weight set per stack; otherwise one stack after the other as fsn_lstm2_forward
  * would (callers with small stacks do better to put them on one stream each).  Results equal fsn_lstm2_forward's per
